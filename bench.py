@@ -13,6 +13,12 @@ with overdrive character 0.5, reverb 0.1, rotary chorale, chord root 48+(i mod 2
 
 Launch: python bench.py --gpus N --steps K --warmup W   (N>1 under torch.distributed.run,
 one rank per GPU; instances shard across ranks, no data-path collective).
+
+A plain run sets up, warms up, times the K steps and prints the result line (value,
+ms_per_step); everything else the line can carry -- per-kernel and unloaded launch times,
+the roofline, the 64-block-chunk figure, max|err| against the CPU oracle per stage, the CPU
+baseline -- takes runs of its own after the timed region and is measured only with --full.
+--dump-outputs DIR writes what the last timed step rendered (dump_outputs below).
 """
 import argparse
 import json
@@ -74,6 +80,13 @@ def parse():
                     help="cfg3: BASELINE configs[2]/[3] (the metric's workload); cfg2: configs[1] (tonegen only, "
                          "use with --batch 256); cfg5: configs[4] per-GPU sub-batch (96 kHz, 7 tunings, random "
                          "drawbars) -- secondary lines, not the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else of the line: per-kernel "
+                         "and unloaded launch times, roofline, steady64, max|err| vs the CPU oracle per stage, "
+                         "CPU baseline (the options below size those legs; without --full none of them runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0's shard) as DIR/<name>.npy, float32: a "
+                         "fixed seeded sample of at most 64 MB (see dump_outputs)")
     ap.add_argument("--check", type=int, default=4, help="instances checked against the CPU oracle")
     ap.add_argument("--cpu-baseline", type=int, default=1)
     ap.add_argument("--cpu-instances", type=int, default=128)
@@ -151,6 +164,33 @@ def setup_instances(eng, wl, first_global, n):
                 eng.note(i, a, v)
             else:
                 eng.set_param(i, a, v)
+
+
+DUMP_ROWS = 16           # instances dumped whole
+DUMP_TAIL = 256          # last samples dumped of every instance
+DUMP_BUDGET = 64 << 20   # bytes, all files together
+
+
+def dump_outputs(path, outL, outR):
+    """--dump-outputs: the L / R device buffers a caller of render_device receives, as the
+    last timed step left them, sampled to stay under DUMP_BUDGET (float32 .npy files):
+      L.npy, R.npy            every sample of that step for DUMP_ROWS instances, chosen once
+                              by a generator seeded with 0 (rows.npy: their indices)
+      L_tail.npy, R_tail.npy  the step's last DUMP_TAIL samples of every instance
+    The workload is synthetic and seeded per instance, so the same arguments give the same
+    inputs, and two builds can be compared file for file."""
+    import numpy as np
+    B, nsamp = outL.shape
+    rows = np.sort(np.random.default_rng(0).choice(B, size=min(B, DUMP_ROWS), replace=False))
+    cols = min(nsamp, (DUMP_BUDGET * 3 // 4) // (8 * len(rows)))
+    tail = min(nsamp, DUMP_TAIL, (DUMP_BUDGET // 4 - 1024) // (8 * B))
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "rows.npy", rows.astype(np.float32))
+    for name, t in (("L", outL), ("R", outR)):
+        np.save(d / f"{name}.npy", t[rows.tolist(), nsamp - cols:].cpu().numpy().astype(np.float32, copy=False))
+        if tail:
+            np.save(d / f"{name}_tail.npy", t[:, nsamp - tail:].cpu().numpy().astype(np.float32, copy=False))
 
 
 def _cpu_worker(args):
@@ -420,6 +460,9 @@ def launch_ranks(n):
 
 def main():
     a = parse()
+    if a.dump_outputs and a.dry_run:
+        print("bench.py: --dump-outputs needs a render; --dry-run renders nothing", file=sys.stderr)
+        sys.exit(2)
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(launch_ranks(a.gpus))
     rank = int(os.environ.get("RANK", "0"))
@@ -511,6 +554,8 @@ def main():
     elapsed = reduce(time.perf_counter() - t0)
     total_samples = world * a.batch * nsamp * a.steps  # every rank's instances (shard sums to world * batch)
     value = total_samples / elapsed
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, outL, outR)
 
     kern, kern_iso, max_err, exact, per_stage, steady64 = {}, None, None, None, None, None
     # launch sets per step: the timed steps have no control deltas, so each chunk is up to the
@@ -518,7 +563,7 @@ def main():
     chunk = eng.chunks()[1] if not a.dry_run else 64
     launches = -(-a.blocks // chunk)
     ksteps = a.steps if a.kernel_steps is None else a.kernel_steps
-    if not a.dry_run:
+    if a.full and not a.dry_run:
         # per-kernel launch durations (HIP events on each launch's stream, inside the
         # engine), rendered exactly like the timed region (cross-chunk pipelining on, so a
         # duration includes the overlap with the neighbouring chunk's kernels); a separate
@@ -566,10 +611,10 @@ def main():
             taps = stage_taps(T, wl, first_global, a.check, total_blocks, a.blocks, device) if a.stage_check else None
             max_err, exact, per_stage = oracle_check(wl, first_global, a.check, total_blocks, a.blocks, gL, gR, taps)
     dry_sum = reduce(chk[0] % (1 << 50), "sum") if a.dry_run else None
-    max_err = reduce(max_err or 0.0) if (a.check and not a.dry_run) else None
+    max_err = reduce(max_err or 0.0) if (a.full and a.check and not a.dry_run) else None
 
     bank_entries = None
-    if a.chain == 1 and not a.dry_run:
+    if a.full and a.chain == 1 and not a.dry_run:
         # tonegen only (configs[1]) is L2-bound: every program entry of a
         # block gathers one wheel's 128 samples from the shared bank, 4 B per entry and
         # sample.  Entries per block: the device programs of up to 32 instances.
@@ -588,7 +633,7 @@ def main():
         roof = roofline(a, B, nsamp, elapsed, samples_launch, launches, algo, kern, kern_iso, bank_entries) \
             if kern else None
         cpu = cpu_baseline(a.cpu_instances, a.cpu_blocks, a.sr) \
-            if (a.cpu_baseline and world == 1 and a.workload == "cfg3" and not a.dry_run) else None
+            if (a.full and a.cpu_baseline and world == 1 and a.workload == "cfg3" and not a.dry_run) else None
         line = {
             "metric": "stereo samples/sec whole-node, batch=4096 full chain @48kHz; max|err| vs CPU",
             "value": value, "unit": "stereo samples/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -597,7 +642,8 @@ def main():
             "config": {"workload": wl.describe(a.batch, world, a.blocks),
                        "batch_per_gpu": a.batch, "blocks_per_step": a.blocks, "sample_rate": a.sr,
                        "parallelism": f"instance-sharded x{world} (no collective)"},
-            "max_err": max_err, "bit_exact_frac": exact, "checked_instances": a.check,
+            "full": a.full, "max_err": max_err, "bit_exact_frac": exact,
+            "checked_instances": a.check if a.full else 0,
             "max_err_per_stage": per_stage,
             "roofline": roof,
             "steady64": steady64,

@@ -7,7 +7,7 @@
                              5TET / duodene (tests/regression_test_data/*.scl mapped
                              with note 60 = 261.62556530059874 Hz, period from the scl)
   regression_test_data.tar.xz  the reference's DEBUG_TONEGEN_OSC fixture files
-  ref_vectors.npz            reference-compiled chain outputs (oracle/_ref) for the
+  ref_vectors_<i>.npz        reference-compiled chain outputs (oracle/_ref) for the
                              golden scenarios, with per-stage taps
 """
 import json

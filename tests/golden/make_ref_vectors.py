@@ -1,4 +1,4 @@
-"""Generate tests/golden/ref_vectors.npz: outputs of the reference's OWN translation
+"""Generate tests/golden/ref_vectors_<i>.npz: outputs of the reference's OWN translation
 units (oracle/_ref/libtbfref.so, compiled from /root/reference/src by `make -C oracle
 ref`) for fixed golden scenarios, with every stage tap.  Run here, where
 /root/reference exists; the file is data only (inputs = the case table below,
@@ -44,6 +44,20 @@ CASES = [
 ]
 
 
+# the vectors are stored in PARTS archives (case i in part i mod PARTS, the case table in
+# part 0) so that every committed file stays under 1 MiB
+PARTS = 3
+
+
+def load_vectors():
+    """Every array of the committed ref_vectors_<i>.npz parts, merged into one dict."""
+    out = {}
+    for i in range(PARTS):
+        with np.load(HERE / f"ref_vectors_{i}.npz") as z:
+            out.update({k: z[k] for k in z.files})
+    return out
+
+
 def scenario(kind, i):
     if kind == "bench":
         return S.bench_scenario(i)
@@ -76,9 +90,12 @@ def main():
             out[f"{name}/{k}"] = v.astype(np.float32)
         table.append({"name": name, "sr": sr, "tuning": tun, "tpl_seed": tseed, "inst_seed": iseed,
                       "scenario": [kind, arg], "nblocks": nb, "chain": chain})
-    out["cases"] = np.array(json.dumps(table))
-    np.savez_compressed(HERE / "ref_vectors.npz", **out)
-    print(f"wrote ref_vectors.npz: {len(table)} cases")
+    parts = [{k: v for k, v in out.items() if k.split("/")[0] in [t["name"] for t in table[i::PARTS]]}
+             for i in range(PARTS)]
+    parts[0]["cases"] = np.array(json.dumps(table))
+    for i, part in enumerate(parts):
+        np.savez_compressed(HERE / f"ref_vectors_{i}.npz", **part)
+    print(f"wrote ref_vectors_0..{PARTS - 1}.npz: {len(table)} cases")
 
 
 if __name__ == "__main__":

@@ -127,7 +127,7 @@ def test_gpu_full_chain_events(oracle):
 @pytest.mark.parametrize("debug_flags", [0, 1])
 def test_gpu_vs_committed_reference_vectors(debug_flags):
     """The HIP engine against the reference's own compiled chain (committed vectors,
-    tests/golden/ref_vectors.npz): 44.1/48/96 kHz (whirl ring W=512/1024), 12-TET /
+    tests/golden/ref_vectors_*.npz): 44.1/48/96 kHz (whirl ring W=512/1024), 12-TET /
     19-TET / p4 / bagpipe4 / duodene / 5TET templates, event scripts, config-5 random
     drawbars, the parameter sweep (overdrive character, reverb mix, percussion variants,
     clusters, pedal keys, rotary stop <-> fast).  debug_flags=1 (TBF_DEBUG_FORCE_SERIAL)
@@ -136,9 +136,9 @@ def test_gpu_vs_committed_reference_vectors(debug_flags):
     import json
     from pathlib import Path
     import tunebfree_amd as T
-    from golden.make_ref_vectors import scenario
+    from golden.make_ref_vectors import load_vectors, scenario
     gold = Path(__file__).resolve().parent / "golden"
-    z = np.load(gold / "ref_vectors.npz")
+    z = load_vectors()
     tunings = json.loads((gold / "tunings.json").read_text())
     worst = 0.0
     for c in json.loads(str(z["cases"])):
@@ -1997,3 +1997,44 @@ def test_gpu_sin_fast_paths_are_ocml_bits():
         same = got.view(np.uint64) == want.view(np.uint64)
         assert same.all(), (name, x[~same][:8], got[~same][:8], want[~same][:8])
     assert np.mean(np.abs(np.clip(x, -1, 1)) < 0.5) > 0.3  # the asin fast path was exercised
+
+
+def test_bench_plain_run_dumps_last_timed_step(tmp_path):
+    """bench.py at test size (8 instances, 4 blocks per step) as a plain run: the line
+    carries ms_per_step for exactly --steps steps and none of the --full legs, and
+    --dump-outputs holds the last timed step's L / R of the sampled instances and the
+    tail of every instance, float32 -- bit for bit the oracle's render of the same
+    instances over the warmup + timed blocks."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    import bench
+    root = Path(bench.__file__).resolve().parent
+    steps, warmup, batch, blocks = 2, 1, 8, 4
+    out = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+                          str(warmup), "--batch", str(batch), "--blocks", str(blocks), "--dump-outputs",
+                          str(tmp_path)], check=True, capture_output=True, text=True, timeout=120, cwd=str(root)).stdout
+    lines = [ln for ln in out.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["ms_per_step"] > 0 and d["full"] is False
+    assert d["value"] == pytest.approx(batch * blocks * 128 / (d["ms_per_step"] * 1e-3), rel=1e-9)
+    assert all(d[k] is None for k in ("roofline", "steady64", "cpu_baseline", "max_err", "max_err_per_stage"))
+    got = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert sorted(got) == ["L", "L_tail", "R", "R_tail", "rows"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= bench.DUMP_BUDGET
+    rows = got["rows"].astype(int)
+    assert rows.tolist() == list(range(batch))  # fewer instances than DUMP_ROWS: every one, in order
+    nsamp = blocks * 128
+    assert got["L"].shape == got["R"].shape == (batch, nsamp)
+    tail = min(nsamp, bench.DUMP_TAIL)
+    assert got["L_tail"].shape == got["R_tail"].shape == (batch, tail)
+    wl = bench.Workload("cfg3", 48000.0)
+    for j, g in enumerate(rows):
+        oL, oR, *_ = bench.oracle_run(wl, int(g), (warmup + steps) * blocks, blocks)
+        for name, o in (("L", oL), ("R", oR)):
+            assert np.array_equal(got[name][j].view(np.uint32), o.view(np.uint32)), (name, g)
+            assert np.array_equal(got[name + "_tail"][g].view(np.uint32), o[-tail:].view(np.uint32)), (name, g)
+    assert float(np.abs(got["L"]).max()) > 1e-3

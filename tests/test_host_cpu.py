@@ -564,6 +564,20 @@ def test_bench_world_size_mismatch_fails():
     assert "WORLD_SIZE=1" in out.stderr and not [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_bench_full_flag_and_dump_needs_render(tmp_path):
+    """The line says whether the --full legs ran; --dump-outputs with --dry-run (nothing
+    rendered, so nothing to write) is an error (exit 2) that writes no file."""
+    import subprocess
+    import sys
+    common = ["--dry-run", "1", "--steps", "1", "--warmup", "0", "--batch", "3"]
+    assert _bench_json(common)["full"] is False
+    assert _bench_json(common + ["--full"])["full"] is True
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py")] + common + ["--dump-outputs", str(tmp_path / "d")],
+                         capture_output=True, text=True, timeout=120, cwd=str(ROOT))
+    assert out.returncode == 2 and "--dump-outputs" in out.stderr, out.stderr[-2000:]
+    assert not (tmp_path / "d").exists()
+
+
 def test_drawbar_setting_out_of_range_ignored():
     """setDrawBar asserts 0 <= setting < 9 (src/tonegen.cpp:2741); the engine ignores a
     setting outside that (no drawbar change, no gain change), on the host front end and in

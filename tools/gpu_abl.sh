@@ -7,7 +7,7 @@ OUT=gpurun_out/${TAG:-abl}; mkdir -p $OUT; export TMPDIR=/tmp
 B="--cpu-baseline 0 --check 0 --stage-check 0 --steps 5 --warmup 2 --steady64 0"
 for v in base "$@"; do
 	if [ $v = base ]; then L=tunebfree_amd/libtbf.so; else L=tunebfree_amd/_variants/libtbf_$v.so; fi
-	timeout -k 10 300 env TBF_LIB=$L python3 bench.py $B > $OUT/$v.json 2> $OUT/$v.err; rc=$?
+	timeout -k 10 300 env TBF_LIB=$L python3 bench.py --full $B > $OUT/$v.json 2> $OUT/$v.err; rc=$?
 	echo "$v rc=$rc"; [ $rc -ne 0 ] && exit $rc
 	python3 -c "
 import json,sys

@@ -34,7 +34,7 @@ for r in $(seq 1 "${ROUNDS:-2}"); do
 	for vv in "${VARS[@]}"; do
 		v=${vv%%=*}
 		case "${PAR[$v]}" in FAILED*) continue ;; esac
-		env "$(venv "$vv")" TBF_LIB=$(lib "$vv") timeout -k 10 300 python3 bench.py $B > "$OUT/${v}_$r.json" 2> "$OUT/${v}_$r.err"
+		env "$(venv "$vv")" TBF_LIB=$(lib "$vv") timeout -k 10 300 python3 bench.py --full $B > "$OUT/${v}_$r.json" 2> "$OUT/${v}_$r.err"
 		rc=$?
 		if [ $rc -ne 0 ]; then echo "bench $v rc=$rc"; tail -5 "$OUT/${v}_$r.err"; [ $rc -ge 124 ] && exit $rc; continue; fi
 		python3 - "$OUT/${v}_$r.json" "$v" "$r" "${PAR[$v]}" <<'EOF' | tee -a "$OUT/summary.txt"

@@ -6,7 +6,7 @@ K=${1:-}
 timeout -k 10 600 python3 -u -m pytest tests -x -v -s -m gpu ${K:+-k "$K"} --timeout 240 --timeout-method thread > $OUT/tests.log 2>&1; rc=$?
 grep -E "passed|failed|FAILED|Error" $OUT/tests.log | tail -5; echo "tests rc=$rc"
 [ $rc -ge 124 ] && exit $rc
-timeout -k 10 300 python3 bench.py --cpu-baseline 0 --steps 10 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err; rc=$?; echo "bench rc=$rc"
+timeout -k 10 300 python3 bench.py --full --cpu-baseline 0 --steps 10 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err; rc=$?; echo "bench rc=$rc"
 [ $rc -ne 0 ] && exit $rc
 python3 - $OUT/bench.json <<'PY'
 import json,sys

@@ -10,7 +10,7 @@ BP="--steps 2 --warmup 1 --cpu-baseline 0 --check 0 --stage-check 0 --blocks 16"
 i=0; dirs=()
 for set in "$@"; do
 	i=$((i+1))
-	timeout -k 10 120 rocprofv3 --pmc $set -d "$OUT/p$i" -o run --output-format csv -- python3 bench.py $BP > "$OUT/p$i.log" 2>&1
+	timeout -k 10 120 rocprofv3 --pmc $set -d "$OUT/p$i" -o run --output-format csv -- python3 bench.py --full $BP > "$OUT/p$i.log" 2>&1
 	rc=$?; echo "pass $i rc=$rc"; [ $rc -ne 0 ] && { tail -5 "$OUT/p$i.log"; [ $rc -ge 124 ] && exit $rc; continue; }
 	dirs+=("$OUT/p$i")
 done
