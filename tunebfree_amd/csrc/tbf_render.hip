@@ -65,6 +65,12 @@
 #ifndef WH_SERIAL_PIPE
 #define WH_SERIAL_PIPE 1 /* k_whirl serial passes: next group's reads ahead of this group's chain */
 #endif
+#ifndef WH_PIN_READS
+#define WH_PIN_READS 1 /* motion_pass: the ring reads pinned ahead of the adds, one LDS round trip per pass */
+#endif
+#ifndef WH_NEXT_TABLES
+#define WH_NEXT_TABLES 1 /* k_whirl: the next ring group's table loads issued ahead of this group's ring passes */
+#endif
 #ifndef WH_PAD
 /* floats after each LDS ring / horn-A row: the rows of one serial pass 16-B aligned (its
  * 4-sample reads and writes) and each lane's 16 B on banks of its own */
@@ -3010,6 +3016,15 @@ __device__ __forceinline__ void motion_pass (float (*ring)[W + WH_PAD], const in
 		v[gi]  = ring[gi][i0[gi]];
 		w[gi]  = ring[gi][i1[gi]];
 	}
+#if WH_PIN_READS
+	/* the loaded values are pinned here, all reads issued: left to itself the compiler
+	 * sinks the adds and one of the reads into the owners' store branches below, and each
+	 * pass then waits out two or more LDS latencies (a read and a full lgkmcnt(0) drain
+	 * inside each exec-masked block) instead of one */
+#pragma unroll
+	for (int gi = 0; gi < RG; gi++)
+		asm volatile ("" : "+v"(v[gi]), "+v"(w[gi]));
+#endif
 #pragma unroll
 	for (int gi = 0; gi < RG; gi++) {
 		const uint64_t eq = eqm[gi][q], s1 = s1m[gi][q];
@@ -3041,9 +3056,8 @@ __device__ __forceinline__ void motion_pass (float (*ring)[W + WH_PAD], const in
  * temp[-2] are lane-parallel afterwards (wh_outputs).  scrub applies the block-end NaN
  * scrub (src/whirl.cpp:1622-1630) to the incoming state first. */
 template <bool WRAP>
-__device__ __forceinline__ void wh_serial (float* r, uint32_t base, uint32_t m, float* fz, float a1, float a2, bool scrub)
+__device__ __forceinline__ void wh_serial (float* r, uint32_t base, uint32_t m, float& z0, float& z1, float a1, float a2, bool scrub)
 {
-	float z0 = fz[0], z1 = fz[1];
 	if (scrub) {
 		if (isnan (z0))
 			z0 = 0.f;
@@ -3107,6 +3121,13 @@ __device__ __forceinline__ void wh_serial (float* r, uint32_t base, uint32_t m, 
 		}
 	}
 #endif
+}
+/* the same with the state in memory */
+template <bool WRAP>
+__device__ __forceinline__ void wh_serial (float* r, uint32_t base, uint32_t m, float* fz, float a1, float a2, bool scrub)
+{
+	float z0 = fz[0], z1 = fz[1];
+	wh_serial<WRAP> (r, base, m, z0, z1, a1, a2, scrub);
 	fz[0] = z0;
 	fz[1] = z1;
 }
@@ -3114,9 +3135,8 @@ __device__ __forceinline__ void wh_serial (float* r, uint32_t base, uint32_t m, 
 /* wh_serial<false> on a 16-B aligned row, 4 samples per LDS read / write (ds_read_b128 /
  * ds_write_b128: 32 LDS instructions per pass instead of 128); the same operations in the
  * same order, the next group of 8 read while this one's recurrence runs */
-__device__ __forceinline__ void wh_serial_v (float* r, float* fz, float a1, float a2, bool scrub)
+__device__ __forceinline__ void wh_serial_v (float* r, float& z0, float& z1, float a1, float a2, bool scrub)
 {
-	float z0 = fz[0], z1 = fz[1];
 	if (scrub) {
 		if (isnan (z0))
 			z0 = 0.f;
@@ -3152,6 +3172,11 @@ __device__ __forceinline__ void wh_serial_v (float* r, float* fz, float a1, floa
 		run (xb, g + 1);
 	}
 	PRIO_DOWN ();
+}
+__device__ __forceinline__ void wh_serial_v (float* r, float* fz, float a1, float a2, bool scrub)
+{
+	float z0 = fz[0], z1 = fz[1];
+	wh_serial_v (r, z0, z1, a1, a2, scrub);
 	fz[0] = z0;
 	fz[1] = z1;
 }
@@ -3184,6 +3209,103 @@ __device__ __forceinline__ void wh_flush (const WhOut& o)
 	*o.r = o.vr;
 }
 
+/* k_whirl's wave-uniform state, in registers (scalar ones, through readfirstlane /
+ * readlane) for the whole launch: as LDS words each was written by one lane and read back
+ * by all, a dependent LDS round trip at every use in every sub-block.  The LDS copy sm.st
+ * is brought up to date where something wants it: the rotor words before whirl_speed's
+ * non-steady path (which also owns the AcDc flags and the targets, kept in LDS alone), and
+ * everything at launch end (wh_reg_store). */
+struct WhReg {
+	uint32_t outpos;
+	double   hornAngle, drumAngle, hornIncr, drumIncr;
+	int      live;  /* hornAcDc or drumAcDc is non-zero */
+	int      brk;   /* bit 0 / 1: the parameter set has a horn / drum brake position */
+	int      brake; /* whirl_speed's brake word of this block */
+	int      ap, aReady; /* horn A's row parity; ab[ap ^ 1] holds this sub-block's horn A output */
+	int      ran;   /* a block of this launch went through the rotors (the history rows are newer than st.adx) */
+	float    z[4];  /* FILTER_C carries: the last lane's xf, x1, xin, xd1 */
+	float    fz0, fz1; /* per lane: lane f < 4 holds the state z0, z1 of serial filter f (st.fz[f]) */
+};
+
+__device__ __forceinline__ uint32_t uni (uint32_t v) { return __builtin_amdgcn_readfirstlane (v); }
+__device__ __forceinline__ int      uni (int v) { return __builtin_amdgcn_readfirstlane (v); }
+__device__ __forceinline__ float    uni (float v) { return __int_as_float (__builtin_amdgcn_readfirstlane (__float_as_int (v))); }
+__device__ __forceinline__ double   uni (double v)
+{
+	const unsigned long long u  = __double_as_longlong (v);
+	const unsigned           lo = __builtin_amdgcn_readfirstlane ((unsigned)u), hi = __builtin_amdgcn_readfirstlane ((unsigned)(u >> 32));
+	return __longlong_as_double ((long long)(((unsigned long long)hi << 32) | lo));
+}
+__device__ __forceinline__ float rlf (float v, int l) { return __int_as_float (rl (__float_as_int (v), l)); }
+
+/* the rotor words and what whirl_speed's steady test needs, from the LDS state */
+__device__ __forceinline__ void wh_reg_rotor (const tbf_wh_state& st, WhReg& R)
+{
+	R.hornAngle = uni (st.hornAngle);
+	R.drumAngle = uni (st.drumAngle);
+	R.hornIncr  = uni (st.hornIncr);
+	R.drumIncr  = uni (st.drumIncr);
+	R.live      = uni (st.hornAcDc | st.drumAcDc);
+}
+__device__ __forceinline__ void wh_reg_brk (const tbf_wh_state& st, WhReg& R)
+{
+	R.brk = uni ((st.prm.hnBrakePos > 0 ? 1 : 0) | (st.prm.drBrakePos > 0 ? 2 : 0));
+}
+
+/* launch start: the state from LDS (copied from memory, all lanes past the copy), and the
+ * history rows' heads [0..3] (the last four samples of the previous sub-block) from st.adx */
+template <int W>
+__device__ __forceinline__ void wh_reg_load (WhLds<W>& sm, WhReg& R)
+{
+	const tbf_wh_state& st   = sm.st;
+	const int           lane = threadIdx.x;
+	R.outpos                 = uni (st.outpos);
+	wh_reg_rotor (st, R);
+	wh_reg_brk (st, R);
+	R.brake = R.ap = R.aReady = R.ran = 0;
+#pragma unroll
+	for (int i = 0; i < 4; i++)
+		R.z[i] = uni (st.z[i]);
+	R.fz0 = R.fz1 = 0.f;
+	if (lane < 4) {
+		R.fz0       = st.fz[lane][0];
+		R.fz1       = st.fz[lane][1];
+		sm.xf[lane] = st.adx[0][(st.adi[0] + 3 - lane) & 7];
+		sm.x1[lane] = st.adx[1][(st.adi[1] + 3 - lane) & 7];
+		sm.x2[lane] = st.adx[2][(st.adi[2] + 3 - lane) & 7];
+	}
+	wave_sync ();
+}
+
+/* launch end: the LDS state as a launch that kept it there would leave it */
+template <int W>
+__device__ __forceinline__ void wh_reg_store (WhLds<W>& sm, const WhReg& R)
+{
+	tbf_wh_state& st   = sm.st;
+	const int     lane = threadIdx.x;
+	wave_sync ();
+	if (lane == 0) {
+		st.outpos    = R.outpos;
+		st.hornAngle = R.hornAngle;
+		st.drumAngle = R.drumAngle;
+		st.hornIncr  = R.hornIncr;
+		st.drumIncr  = R.drumIncr;
+#pragma unroll
+		for (int i = 0; i < 4; i++)
+			st.z[i] = R.z[i];
+	}
+	if (lane < 4) {
+		st.fz[lane][0] = R.fz0;
+		st.fz[lane][1] = R.fz1;
+	}
+	if (R.ran && lane < 24) { /* history k = lane / 8, entry j = lane % 8, one lane each */
+		const int    k = lane >> 3, j = lane & 7;
+		const float* h = k == 0 ? sm.xf : (k == 1 ? sm.x1 : sm.x2);
+		st.adx[k][(st.adi[k] + j) & 7] = h[4 + TBF_SUB - 1 - j];
+	}
+	wave_sync ();
+}
+
 /* whirlProc2 (src/whirl.cpp:1191-1638) + whirlProc3 mic mix (1653-1681).  in0 / in1: this
  * block's input (samples lane, lane + 64); the next block's is loaded from inNext into
  * nx0 / nx1 during the first sub-block (inNext may be this block's own input when there
@@ -3191,7 +3313,7 @@ __device__ __forceinline__ void wh_flush (const WhOut& o)
 template <int W>
 __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypass, const int revOpt, const tbf_inst_const& K,
                              const float in0, const float in1, const float* __restrict__ inNext, float& nx0, float& nx1,
-                             const bool hasNext, float* __restrict__ oL, float* __restrict__ oR, WhOut& pend)
+                             const bool hasNext, float* __restrict__ oL, float* __restrict__ oR, WhOut& pend, WhReg& R)
 {
 	const int     lane  = threadIdx.x;
 	tbf_wh_state& st    = sm.st;
@@ -3218,14 +3340,29 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 		pend.vr = in1 * K.mic[4] + in1 * K.mic[5] + 0.f * K.mic[6] + 0.f * K.mic[7];
 		return;
 	}
-	if (lane == 0) {
-		int brake;
-		/* a control entry carrying a rotary selection is used for exactly one block */
-		whirl_speed (st, K, revOpt, brake);
-		sm.brake = brake;
+	/* whirl_speed changes nothing while no rotary selection arrives, neither rotor is
+	 * accelerating and no brake can engage (a brake needs a set position and a rotor at
+	 * rest): a wave-uniform test on registers.  Otherwise lane 0 runs it on the LDS state. */
+	const bool steady = revOpt < 0 && !R.live && (!(R.brk & 1) || R.hornIncr != 0) && (!(R.brk & 2) || R.drumIncr != 0);
+	R.brake           = 0;
+	R.ran             = 1;
+	if (WH_RARE (!steady)) {
+		if (lane == 0) {
+			int brake;
+			st.hornAngle = R.hornAngle;
+			st.drumAngle = R.drumAngle;
+			st.hornIncr  = R.hornIncr;
+			st.drumIncr  = R.drumIncr;
+			/* a control entry carrying a rotary selection is used for exactly one block */
+			whirl_speed (st, K, revOpt, brake);
+			sm.brake = brake;
+		}
+		wave_sync ();
+		wh_reg_rotor (st, R);
+		R.brake = uni (sm.brake);
+		wave_sync ();
 	}
-	wave_sync ();
-	const double   hornIncr = st.hornIncr, drumIncr = st.drumIncr;
+	const double   hornIncr = R.hornIncr, drumIncr = R.drumIncr;
 	const uint32_t WM       = (uint32_t)W - 1u;
 	/* the horn filters' coefficients of this block (the runtime set in the state); serial
 	 * filter coefficients: lane 0 horn A, lane 1 horn B, lanes 2-3 drum shelf */
@@ -3241,8 +3378,8 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 
 	for (int sb = 0; sb < TBF_BLK / TBF_SUB; sb++) {
 		const int      n      = lane;
-		const uint32_t outpos = (st.outpos + (uint32_t)n) & 2047u;
-		const int32_t  unwrap = (int32_t)(st.outpos + (uint32_t)n - outpos); /* 0 or 2048 */
+		const uint32_t outpos = (R.outpos + (uint32_t)n) & 2047u;
+		const int32_t  unwrap = (int32_t)(R.outpos + (uint32_t)n - outpos); /* 0 or 2048 */
 		const float    xin    = (float)((double)(sb == 0 ? in0 : in1) + 1e-14);
 		/* ring reads + clear at outpos: before this sub-block's writes, which land >= 79
 		 * slots ahead (src/whirl.cpp:1585-1600); the drum rings' outputs are read by the
@@ -3251,30 +3388,24 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 		const float    hlv = sm.wring[0][o], hrv = sm.wring[1][o];
 		sm.wring[0][o]     = 0.f;
 		sm.wring[1][o]     = 0.f;
-		if (lane < 4) {
-			const int i = lane;
-			sm.xf[i] = st.adx[0][(st.adi[0] + 3 - i) & 7];
-			sm.x1[i] = st.adx[1][(st.adi[1] + 3 - i) & 7];
-			sm.x2[i] = st.adx[2][(st.adi[2] + 3 - i) & 7];
-		}
 		/* DF2 biquads: horn B runs on horn A's output, so A runs one sub-block ahead and
 		 * one serial pass advances A over the next sub-block (lane 0), B over this one into
 		 * xf (lane 1) and the drum shelves over this one's ring outputs, in place (lanes 2,
 		 * 3).  A's own pass over this sub-block runs only when it is not ahead (launch
 		 * start, after a bypassed block or a new coefficient set). */
-		const int  ap    = sm.ap;
+		const int  ap    = R.ap;
 		const bool aNext = sb + 1 < TBF_BLK / TBF_SUB || hasNext;
 #ifndef WH_ABL_HORN
-		if (WH_RARE (!sm.aReady))
+		if (WH_RARE (!R.aReady))
 			sm.ab[ap ^ 1][n] = xin;
 		if (aNext)
 			sm.ab[ap][n] = (float)((double)(sb + 1 < TBF_BLK / TBF_SUB ? in1 : nx0) + 1e-14);
 		wave_sync ();
-		if (WH_RARE (!sm.aReady)) {
-			const float z0 = st.fz[0][0], z1 = st.fz[0][1];
+		if (WH_RARE (!R.aReady)) {
+			const float z0 = rlf (R.fz0, 0), z1 = rlf (R.fz1, 0);
 #ifndef WH_NO_SERIAL
 			if (lane == 0)
-				wh_serial_v (sm.ab[ap ^ 1], st.fz[0], ha[0], ha[1], false);
+				wh_serial_v (sm.ab[ap ^ 1], R.fz0, R.fz1, ha[0], ha[1], false);
 #endif
 			wave_sync ();
 			sm.ab[ap ^ 1][n] = wh_output (sm.ab[ap ^ 1][n], z0, z1, ha);
@@ -3286,14 +3417,14 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 		float      zs[4][2];
 #pragma unroll
 		for (int f = 0; f < 4; f++) {
-			zs[f][0] = st.fz[f][0];
-			zs[f][1] = st.fz[f][1];
+			zs[f][0] = rlf (R.fz0, f);
+			zs[f][1] = rlf (R.fz1, f);
 		}
 		if (scrubA) {
 			zs[0][0] = isnan (zs[0][0]) ? 0.f : zs[0][0];
 			zs[0][1] = isnan (zs[0][1]) ? 0.f : zs[0][1];
 		}
-		const uint32_t wb   = st.outpos & WM; /* the drum rings' window: wave-uniform */
+		const uint32_t wb   = R.outpos & WM; /* the drum rings' window: wave-uniform */
 		const bool     wrap = wb + TBF_SUB > (uint32_t)W;
 #ifdef WH_NO_SERIAL /* timing experiment only (wrong output): k_whirl without its serial filter passes */
 		if (false) {
@@ -3304,9 +3435,9 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 #endif
 			float* row = lane == 0 ? sm.ab[ap] : (lane == 1 ? sm.ab[ap ^ 1] : sm.wring[lane]);
 			if (WH_RARE (wrap))
-				wh_serial<true> (row, lane < 2 ? 0u : wb, lane < 2 ? ~0u : WM, st.fz[lane], fa0, fa1, lane == 0 && scrubA);
+				wh_serial<true> (row, lane < 2 ? 0u : wb, lane < 2 ? ~0u : WM, R.fz0, R.fz1, fa0, fa1, lane == 0 && scrubA);
 			else
-				wh_serial_v (row + (lane < 2 ? 0u : wb), st.fz[lane], fa0, fa1, lane == 0 && scrubA);
+				wh_serial_v (row + (lane < 2 ? 0u : wb), R.fz0, R.fz1, fa0, fa1, lane == 0 && scrubA);
 		}
 		wave_sync ();
 		/* the filter outputs: horn B -> xf, horn A of the next sub-block in place, the drum
@@ -3322,10 +3453,8 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 		const float dR = wh_output (sm.wring[3][o], zs[3][0], zs[3][1], K.drf);
 		sm.wring[2][o] = 0.f;
 		sm.wring[3][o] = 0.f;
-		if (lane == 0) {
-			sm.aReady = aNext;
-			sm.ap     = ap ^ 1;
-		}
+		R.aReady = aNext;
+		R.ap     = ap ^ 1;
 		/* rotor angles, angle = fmod (angle + incr, 1) per sample (src/whirl.cpp:1428-1429):
 		 * inside one binade of the angle every sum lands on the same grid, so the run is
 		 * a0 + n D exactly (phase_run); otherwise lanes 1, 2 replay the recurrence into
@@ -3333,7 +3462,7 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 		double ha, da;
 		{
 			double       Dh, Dd;
-			const double h0 = st.hornAngle, d0 = st.drumAngle;
+			const double h0 = R.hornAngle, d0 = R.drumAngle;
 			const bool   frc = (P.dbg & TBF_DEBUG_FORCE_SERIAL) != 0;
 			const bool   okh = phase_run (h0, hornIncr, TBF_SUB, Dh) && !frc;
 			const bool   okd = phase_run (d0, drumIncr, TBF_SUB, Dd) && !frc;
@@ -3355,38 +3484,38 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 				he = okh ? he : a;
 				de = okd ? de : b;
 			}
-			wave_sync (); /* every lane has read the start angles */
-			if (lane == 0) {
-				st.hornAngle = he;
-				st.drumAngle = de;
-			}
+			R.hornAngle = uni (he);
+			R.drumAngle = uni (de);
 		}
 		wave_sync ();
 		/* reflection filters FILTER_C (src/whirl.cpp:1472-1477), lane-parallel */
 		const float xf   = sm.xf[n + 4];
-		const float xfp  = n == 0 ? st.z[0] : sm.xf[n + 3];
+		const float xfp  = n == 0 ? R.z[0] : sm.xf[n + 3];
 		const float x1v  = (float)((0.4 * xf) + (0.4 * xfp));
 		sm.x1[n + 4]     = x1v;
-		const float xdp  = lane_shr1_or (xin, st.z[2]); /* the previous sample's input */
+		const float xdp  = lane_shr1_or (xin, R.z[2]); /* the previous sample's input */
 		const float xd1v = (float)((0.4 * xin) + (0.4 * xdp));
 		wave_sync ();
-		const float x1p  = n == 0 ? st.z[1] : sm.x1[n + 3];
+		const float x1p  = n == 0 ? R.z[1] : sm.x1[n + 3];
 		const float x2v  = (float)((0.4 * x1v) + (0.4 * x1p));
 		sm.x2[n + 4]     = x2v;
-		const float xd1p = lane_shr1_or (xd1v, st.z[3]);
+		const float xd1p = lane_shr1_or (xd1v, R.z[3]);
 		const float xd2v = (float)((0.4 * xd1v) + (0.4 * xd1p));
 		wave_sync ();
 
 		/* ---- rings (HL, HR, DL, DR) in groups of WH_RG: the group's motions first (their
 		 * table loads in flight together), then each ring's ordered adds ---- */
-#pragma unroll
-		for (int r0 = 0; r0 < 4; r0 += WH_RG) {
-			int   mu[WH_RG][3];
-			float ma[WH_RG][3], mb[WH_RG][3];
+		/* a ring group's table positions and table loads need the rotor angles alone, and their
+		 * registers are free once the group's motions are formed: the next group's loads go out
+		 * then, ahead of this group's ring passes, and fly under them (WH_NEXT_TABLES) */
+		float h1v[WH_RG][3];
+		f2u   dpv[WH_RG][3];
+		f4u   b4v[2][3];
+		float b5v[2][3];
+		auto  tables = [&] (const int r0) {
 			/* the table positions of all 12 motions, then every table load (18) in flight
 			 * together, then the arithmetic: issued motion by motion, each motion's loads
 			 * were waited for before the next motion's were issued */
-			float h1v[WH_RG][3];
 #pragma unroll
 			for (int gi = 0; gi < WH_RG; gi++)
 #pragma unroll
@@ -3399,9 +3528,6 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 					else /* DR_MOTION, src/whirl.cpp:1457 */
 						h1v[gi][q] = (float)__builtin_fma (da, 16384.0, (double)K.hornPhase[p]);
 				}
-			f2u   dpv[WH_RG][3];
-			f4u   b4v[2][3];
-			float b5v[2][3];
 #pragma unroll
 			for (int gi = 0; gi < WH_RG; gi++)
 #pragma unroll
@@ -3418,6 +3544,13 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 						b5v[gi][q]        = b[4];
 					}
 				}
+		};
+#pragma unroll
+		for (int r0 = 0; r0 < 4; r0 += WH_RG) {
+			int   mu[WH_RG][3];
+			float ma[WH_RG][3], mb[WH_RG][3];
+			if (!(WH_NEXT_TABLES && r0 > 0))
+				tables (r0);
 			/* behind the table loads: the next block's input (used from the second
 			 * sub-block on; the second sub-block loads it again, so that every sub-block
 			 * issues the same memory operations in the same order and each wait is
@@ -3459,6 +3592,8 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 					mb[gi][q]      = qq;
 				}
 			}
+			if (WH_NEXT_TABLES && r0 + WH_RG < 4)
+				tables (r0 + WH_RG);
 			/* fast path preconditions (wave votes), per ring: each motion's slot
 			 * non-decreasing in n with groups of <= 2 equal slots, and the ring's motions
 			 * >= 2 slots apart in source order at every sample (so passes farthest-first
@@ -3537,38 +3672,32 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 			pend.vr          = hL * K.mic[4] + hR * K.mic[5] + dL * K.mic[6] + dR * K.mic[7];
 		}
 		/* ---- carry filter taps and histories ---- */
-		if (lane == NL - 1) {
-			st.z[0] = xf;
-			st.z[1] = x1v;
-			st.z[2] = xin;
-			st.z[3] = xd1v;
+		R.z[0] = rlf (xf, NL - 1);
+		R.z[1] = rlf (x1v, NL - 1);
+		R.z[2] = rlf (xin, NL - 1);
+		R.z[3] = rlf (xd1v, NL - 1);
+		/* the rows' last four samples become the next sub-block's heads [0..3], from the
+		 * registers that hold them (every read of the rows is behind the ring passes' syncs) */
+		if (lane >= NL - 4) {
+			sm.xf[n - (NL - 4)] = xf;
+			sm.x1[n - (NL - 4)] = x1v;
+			sm.x2[n - (NL - 4)] = x2v;
 		}
-		wave_sync ();
-		if (lane < 24) { /* history k = lane / 8, entry j = lane % 8, one lane each */
-			const int    k = lane >> 3, j = lane & 7;
-			const float* h = k == 0 ? sm.xf : (k == 1 ? sm.x1 : sm.x2);
-			st.adx[k][(st.adi[k] + j) & 7] = h[4 + TBF_SUB - 1 - j];
-		}
-		if (lane == 0)
-			st.outpos = (st.outpos + TBF_SUB) & 2047u;
+		R.outpos = (R.outpos + TBF_SUB) & 2047u;
 		wave_sync ();
 	}
-	/* NaN scrub (src/whirl.cpp:1622-1630), a lane per value: lanes 0..7 the filter states
-	 * fz (horn A's only when it did not run ahead: then it got its scrub when it crossed
-	 * into the next block), lanes 8..11 z */
-	if (lane < 8) {
-		const int f = lane >> 1, j = lane & 1;
-		if ((f > 0 || !sm.aReady) && isnan (st.fz[f][j]))
-			st.fz[f][j] = 0.f;
-	} else if (lane < 12) {
-		if (isnan (st.z[lane - 8]))
-			st.z[lane - 8] = 0.f;
+	/* NaN scrub (src/whirl.cpp:1622-1630): the filter states fz in their lanes (horn A's
+	 * only when it did not run ahead: then it got its scrub when it crossed into the next
+	 * block) and the carries z */
+	if (lane > 0 || !R.aReady) {
+		R.fz0 = isnan (R.fz0) ? 0.f : R.fz0;
+		R.fz1 = isnan (R.fz1) ? 0.f : R.fz1;
 	}
-	if (lane == 0) {
-		if (sm.brake & 1) st.hornIncr = 0;
-		if (sm.brake & 2) st.drumIncr = 0;
-	}
-	wave_sync ();
+#pragma unroll
+	for (int i = 0; i < 4; i++)
+		R.z[i] = isnan (R.z[i]) ? 0.f : R.z[i];
+	if (R.brake & 1) R.hornIncr = 0;
+	if (R.brake & 2) R.drumIncr = 0;
 }
 
 static_assert (sizeof (tbf_wh_params) % 4 == 0 && sizeof (tbf_wh_params) <= 4 * NL, "one dword per lane");
@@ -3585,13 +3714,11 @@ k_whirl (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf_s
 	tbf_wh_state*         S  = &P.st[inst].wh;
 	float*                wr = P.wring + (size_t)inst * 4 * W;
 	copy_words (&sm.st, S);
-	if (threadIdx.x == 0) {
-		sm.aReady = 0;
-		sm.ap     = 0;
-	}
 	for (uint32_t i = threadIdx.x; i < 4u * W; i += NL)
 		sm.wring[i / W][i % W] = wr[i];
 	wave_sync ();
+	WhReg R;
+	wh_reg_load (sm, R);
 	/* the input (lane n: samples n and n + 64 of a block) is loaded one block ahead, in
 	 * the block's first sub-block behind its table loads (stage_whirl), so its latency
 	 * overlaps a whole sub-block and no wait for it waits for output stores */
@@ -3629,19 +3756,20 @@ k_whirl (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf_s
 			if (threadIdx.x < sizeof (tbf_wh_params) / 4)
 				((uint32_t*)&sm.st.prm)[threadIdx.x] = src[threadIdx.x];
 			wave_sync ();
+			wh_reg_brk (sm.st, R);
 		}
 		/* horn filter A may run ahead into the next block unless that one is bypassed or
 		 * changes its coefficients */
 		const int  nx      = blk_lane ((int)blk + 1);
 		const bool hasNext = more && !rl (byv, nx) && !rl (wsv, nx);
 		stage_whirl<W> (P, sm, rl (byv, blk_lane ((int)blk)) != 0, rl (rvv, blk_lane ((int)blk)), K, c0, c1,
-		                inBase + (size_t)(more ? blk + 1 : blk) * TBF_BLK, n0, n1, hasNext, oL, oR, pend);
+		                inBase + (size_t)(more ? blk + 1 : blk) * TBF_BLK, n0, n1, hasNext, oL, oR, pend, R);
 		c0 = n0;
 		c1 = n1;
 	}
 	if (P.nBlocks > 0)
 		wh_flush (pend);
-	wave_sync ();
+	wh_reg_store (sm, R);
 	copy_words (S, &sm.st);
 	for (uint32_t i = threadIdx.x; i < 4u * W; i += NL)
 		wr[i] = sm.wring[i / W][i % W];
