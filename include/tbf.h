@@ -164,7 +164,10 @@ int tbf_render (tbf_engine* e, uint32_t nblocks, float* outL, float* outR, uint6
  * complete when `stream` reaches this point.  A NULL stream is NOT the legacy default
  * stream: a caller that consumes the outputs on another stream (e.g. torch's current
  * stream, whose handle is 0 on the default stream) must pass that stream's real handle
- * or call tbf_synchronize () first. */
+ * or call tbf_synchronize () first.
+ * stride and pointers need only float alignment: the kernels store the outputs one float
+ * at a time, so any stride >= nblocks*128 (odd ones included) and any 4-byte-aligned
+ * d_outL / d_outR are valid, and nothing outside [0, nblocks*128) of a row is written. */
 int tbf_render_device (tbf_engine* e, uint32_t nblocks, float* d_outL, float* d_outR, uint64_t stride,
                        void* stream);
 
@@ -258,6 +261,20 @@ int tbf_debug_chunks (const tbf_engine* e, uint32_t* delta_blocks, uint32_t* ste
 /* chunks with events since the engine was created, by the front end that stepped them:
  * the device's (k_front) and the host's */
 int tbf_debug_front_chunks (const tbf_engine* e, uint64_t* device_chunks, uint64_t* host_chunks);
+/* test hook: launches of each kernel variant since the engine was created, counted on the
+ * host where the engine launches a stage, from the fields the launch switches on.  Writes
+ * min (cap, TBF_LAUNCH_KINDS) counts in the order below and returns TBF_LAUNCH_KINDS; a
+ * host engine (device -1) launches nothing and reports zeros. */
+enum {
+	TBF_LAUNCH_TONEGEN        = 0, /* k_tonegen, one block range per instance */
+	TBF_LAUNCH_TONEGEN_RANGES = 1, /* k_tonegen, an instance's blocks split over several waves */
+	TBF_LAUNCH_RV_CORE        = 2, /* k_rv_core, the streaming reverb network */
+	TBF_LAUNCH_RV_CORE_LDS    = 3, /* k_rv_core_lds */
+	TBF_LAUNCH_WHIRL          = 4, /* k_whirl */
+	TBF_LAUNCH_WHIRL_SPLIT    = 5, /* k_whirl_split */
+	TBF_LAUNCH_KINDS          = 6
+};
+int tbf_debug_launches (const tbf_engine* e, uint64_t* counts, uint32_t cap);
 /* the longest render chunk without control deltas, in blocks (64 .. 2048, default 512).
  * The stage buffers hold one chunk per instance (56 B per instance and sample at the
  * default stage groups: 15 GB at 4096 instances and 512 blocks, 60 GB at 2048) and

@@ -46,6 +46,27 @@ def oracle_run(lib, tpl, seeds, scens, nblocks, chain=0, templates=None):
     return [np.stack(x) for x in (Ls, Rs, As, Bs, Cs)]
 
 
+def assert_bits(got, ref, what):
+    """The parity gate: `got` equals `ref` bit for bit (uint32 views of float32 arrays of
+    one shape, [instances, samples] or one instance's [samples]).  Prints the max|err| /
+    bit-exact line either way; on a mismatch fails with the number of differing samples,
+    the first differing (instance, block, sample in block), both values there and max|err|."""
+    got = np.ascontiguousarray(got, np.float32)
+    ref = np.ascontiguousarray(ref, np.float32)
+    assert got.shape == ref.shape, f"{what}: shape {got.shape} != reference {ref.shape}"
+    err, exact = compare(got, ref)
+    print(f"{what}: max|err|={err:.3g} bit-exact={exact:.6f}")
+    g2 = got.reshape(1, -1) if got.ndim < 2 else got.reshape(got.shape[0], -1)
+    r2 = ref.reshape(g2.shape)
+    diff = g2.view(np.uint32) != r2.view(np.uint32)
+    if diff.any():
+        i, s = (int(x) for x in np.argwhere(diff)[0])
+        raise AssertionError(
+            f"{what}: {int(diff.sum())} of {diff.size} samples differ; first at instance {i}, block {s // 128}, "
+            f"sample {s % 128}: got {g2[i, s]!r} (0x{int(g2.view(np.uint32)[i, s]):08x}), reference {r2[i, s]!r} "
+            f"(0x{int(r2.view(np.uint32)[i, s]):08x}); max|err|={err:.3g}")
+
+
 def compare(a, b):
     a = np.asarray(a, np.float32)
     b = np.asarray(b, np.float32)

@@ -1,46 +1,147 @@
 """GPU parity: the HIP render path (through the C-ABI) against the CPU oracle.
 
-Gate (BASELINE.json north_star): max|err| <= 1e-5 per float32 sample vs the CPU
-chain.  The float32 stages are computed in the reference's literal operation order,
-so the expected outcome is bit-identity; the only licensed source of difference is
-FP64 libm (GPU sin/asin vs glibc), reported as the bit-exact fraction.
+Gate: bit-identity with the CPU chain at every comparison (enginerun.assert_bits), at
+the outputs and at the tone-generator / preamp / reverb stage taps.  The float32 stages
+are computed in the reference's literal operation order; the only source of difference
+that could be licensed is FP64 libm (GPU sin/asin vs glibc) at the preamp or reverb tap
+(BASELINE.json north_star allows max|err| <= 1e-5 there), and no comparison here needs it.
+
+Kernel dispatch.  The engine picks k_whirl_split and splits k_tonegen's blocks over
+several waves for small batches, so a test of a few instances does not run what a
+4096-instance batch runs.  The tests marked @dispatches run under both: "small" is the
+engine's own choice at the test's size (test_x), "full" forces what a full batch launches
+(test_x_full; TBF_WHIRL_SPLIT=0: k_whirl<W>, TBF_TG_SPLIT=1: one block range per instance),
+and each asserts through Engine.launches() that it ran the kernels its name says.
 """
+import contextlib
+import functools
+import inspect
+import os
+
 import numpy as np
 import pytest
 
 import scenarios as S
-from enginerun import compare, engine_run, oracle_run
+from enginerun import assert_bits, engine_run, oracle_run
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-5
+
+DISPATCH = {"small": {}, "full": {"TBF_WHIRL_SPLIT": "0", "TBF_TG_SPLIT": "1"}}
 
 
-def _engine(chain=0, sr=48000.0, debug_flags=0):
+def dispatches(fn):
+    """A test fn(..., dispatch) run under both dispatches: as two tests, so that the
+    "small" one keeps the name and ids the test had before it took a dispatch (it is that
+    test), and the "full" one is <name>_full with the same ids."""
+    sig = inspect.signature(fn)
+    sig = sig.replace(parameters=[p for p in sig.parameters.values() if p.name != "dispatch"])
+
+    def bind(dispatch, name):
+        @functools.wraps(fn)  # the marks (parametrize) come along in __dict__
+        def test(**kw):
+            return fn(dispatch=dispatch, **kw)
+        del test.__wrapped__
+        test.__signature__ = sig
+        test.__name__ = test.__qualname__ = name
+        return test
+    inspect.getmodule(fn).__dict__[fn.__name__ + "_full"] = bind("full", fn.__name__ + "_full")
+    return bind("small", fn.__name__)
+# the engine's chain modes that stop at a stage tap, and the oracle_run index of that stage
+TAPS = ((1, 2, "tonegen"), (2, 3, "preamp"), (3, 4, "reverb"))
+
+
+@contextlib.contextmanager
+def _environ(env):
+    """the engine reads its switches from the environment when it is created: set them
+    around that, and put back what was there"""
+    old = {k: os.environ.get(k) for k in (env or {})}
+    os.environ.update(env or {})
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def _engine(chain=0, sr=48000.0, debug_flags=0, env=None):
     import tunebfree_amd as T
-    return T.Engine(sample_rate=sr, device=0, chain=chain, debug_flags=debug_flags)
+    with _environ(env):
+        return T.Engine(sample_rate=sr, device=0, chain=chain, debug_flags=debug_flags)
 
 
-def _setup(oracle, n, scen_fn, chain=0, tpl_seed=7, sr=48000.0, debug_flags=0, cfg=None):
+def _ran(eng, dispatch, chain=0, **more):
+    """The engine launched what the test's id says.  full: k_whirl only (chain 0) and
+    k_tonegen never with more than one block range.  small (every such test has at most
+    48 instances): k_whirl_split only.  more: kernel names that must have run (True) or
+    must not (False)."""
+    c = eng.launches()
+    assert c["k_tonegen"] + c["k_tonegen_ranges"] > 0, c
+    if dispatch == "full":
+        assert c["k_tonegen_ranges"] == 0 and c["k_whirl_split"] == 0, (dispatch, c)
+        assert (c["k_whirl"] > 0) == (chain == 0), (dispatch, chain, c)
+    else:
+        assert c["k_whirl"] == 0 and (c["k_whirl_split"] > 0) == (chain == 0), (dispatch, chain, c)
+    if chain in (0, 3):
+        assert c["k_rv_core"] + c["k_rv_core_lds"] > 0, c
+    else:
+        assert c["k_rv_core"] + c["k_rv_core_lds"] == 0, c
+    for k, want in more.items():
+        assert (c[k] > 0) == want, (k, want, c)
+    return c
+
+
+def _all_taps(what, dispatch, ref, make, run, check=None, **more):
+    """Render one script through engines of chain 1, 2, 3 and 0 (make(chain) -> engine,
+    run(engine) -> L, R) and check, bit for bit, the tone-generator, preamp and reverb
+    taps against the oracle's A, B, C and the outputs against its L, R
+    (ref = oracle_run's [L, R, A, B, C]); each engine ran the dispatch's kernels.
+    check(engine) sees the chain-0 engine after its render."""
+    for chain, idx, tap in TAPS:
+        eng = make(chain)
+        L, _ = run(eng)
+        assert_bits(L, ref[idx], f"{what} [{dispatch}] {tap} tap")
+        _ran(eng, dispatch, chain)
+        eng.close()
+    eng = make(0)
+    L, R = run(eng)
+    assert_bits(L, ref[0], f"{what} [{dispatch}] L")
+    assert_bits(R, ref[1], f"{what} [{dispatch}] R")
+    c = _ran(eng, dispatch, 0, **more)
+    if check:
+        check(eng)
+    eng.close()
+    return c
+
+
+def _setup(oracle, n, scen_fn, chain=0, tpl_seed=7, sr=48000.0, debug_flags=0, cfg=None, env=None):
     from orc_bind import Cfg, Template
-    eng = _engine(chain, sr, debug_flags)
+    eng = _engine(chain, sr, debug_flags, env)
     if cfg is not None:  # as a cfg file's text, through tbf_config_parse
         items = list(cfg.items()) if isinstance(cfg, dict) else list(cfg)
         assert eng.config_parse("# cfg\n" + "".join(f"{k} = {v}\n" for k, v in items)) == len(items)
     tid = eng.template(seed=tpl_seed)
     seeds = [1000 + 17 * i for i in range(n)]
     eng.add_instances([tid] * n, seeds)
+    if oracle is None:
+        return eng
     tpl = Template(oracle, sr=sr, seed=tpl_seed, cfg=None if cfg is None else Cfg(oracle, cfg))
     scens = [scen_fn(i) for i in range(n)]
     return eng, tpl, seeds, scens
+
+
+def _organ(n, **kw):
+    """_setup's engine alone (same template, seeds and cfg), for a script's further engines"""
+    return _setup(None, n, None, **kw)
 
 
 def test_gpu_tonegen_only_bitexact(oracle):
     eng, tpl, seeds, scens = _setup(oracle, 8, lambda i: S.bench_scenario(i, full=False), chain=1)
     L, R = engine_run(eng, scens, 24)
     oL, oR, oA, _, _ = oracle_run(oracle, tpl, seeds, scens, 24, chain=1)
-    err, exact = compare(L, oA)
-    print(f"tonegen max|err|={err:.3g} bit-exact={exact:.6f}")
-    assert err == 0.0 and exact == 1.0
+    assert_bits(L, oA, "tonegen")
     assert np.array_equal(L, R)
 
 
@@ -69,70 +170,82 @@ def test_gpu_tonegen_block_ranges(oracle):
         pick = [0, 13, 39]
         res = oracle_run(oracle, tpl, [seeds[i] for i in pick], [scens[i] for i in pick], 105, chain=chain)
         ref = res[2] if chain == 1 else res[0]
-        err, exact = compare(outs[0][0][pick], ref)
-        print(f"chain {chain} (Jazz-1 {full}): max|err|={err:.3g} bit-exact={exact:.6f}")
-        assert err <= TOL
+        assert_bits(outs[0][0][pick], ref, f"chain {chain} (Jazz-1 {full})")
         for o in outs[1:]:
             assert all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(outs[0], o))
 
 
+_REFS = {}
+
+
+def _ref_once(key, fn):
+    """the oracle's render of a test's script, computed once and shared by the test's
+    dispatch cases (never modified)"""
+    if key not in _REFS:
+        _REFS[key] = fn()
+        for a in _REFS[key]:
+            a.setflags(write=False)
+    return _REFS[key]
+
+
+@dispatches
 @pytest.mark.parametrize("tap,idx", [(2, 3), (3, 4)])
-def test_gpu_stage_taps(oracle, tap, idx):
-    eng, tpl, seeds, scens = _setup(oracle, 6, S.bench_scenario, chain=tap)
+def test_gpu_stage_taps(oracle, tap, idx, dispatch):
+    eng, tpl, seeds, scens = _setup(oracle, 6, S.bench_scenario, chain=tap, env=DISPATCH[dispatch])
     L, _ = engine_run(eng, scens, 32)
-    ref = oracle_run(oracle, tpl, seeds, scens, 32)[idx]
-    err, exact = compare(L, ref)
-    print(f"tap {tap}: max|err|={err:.3g} bit-exact={exact:.6f}")
-    assert err <= TOL
+    ref = _ref_once("stage_taps", lambda: oracle_run(oracle, tpl, seeds, scens, 32))[idx]
+    assert_bits(L, ref, f"tap {tap} [{dispatch}]")
+    _ran(eng, dispatch, tap)
 
 
-def test_gpu_full_chain_bench(oracle):
-    eng, tpl, seeds, scens = _setup(oracle, 8, S.bench_scenario)
+@dispatches
+def test_gpu_full_chain_bench(oracle, dispatch):
+    eng, tpl, seeds, scens = _setup(oracle, 8, S.bench_scenario, env=DISPATCH[dispatch])
     L, R = engine_run(eng, scens, 64)
-    oL, oR, *_ = oracle_run(oracle, tpl, seeds, scens, 64)
-    eL, xL = compare(L, oL)
-    eR, xR = compare(R, oR)
-    print(f"full chain: max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL
+    oL, oR, *_ = _ref_once("full_chain_bench", lambda: oracle_run(oracle, tpl, seeds, scens, 64))
+    assert_bits(L, oL, f"full chain [{dispatch}] L")
+    assert_bits(R, oR, f"full chain [{dispatch}] R")
+    _ran(eng, dispatch)
 
 
-def test_gpu_full_chain_odd_batch_mixed_scenarios(oracle):
-    """k_rv_pre and k_rv_post serve 32 instances per workgroup (a chain per lane): a batch
-    of 37 leaves the second workgroup with 5, and neighbouring instances with different
-    scripts (events, quiet ones, reverb-heavy) must not leak into each other."""
+@dispatches
+def test_gpu_full_chain_odd_batch_mixed_scenarios(oracle, dispatch):
+    """k_mixpre and k_rv_pre serve 28 instances per workgroup and k_rv_post 16 (a chain per
+    lane): a batch of 37 leaves their last workgroups with 9 and 5, and neighbouring
+    instances with different scripts (events, quiet ones, reverb-heavy) must not leak into
+    each other: every stage tap and the outputs, bit for bit."""
     def scen(i):
         if i in (2, 33):
             return []  # silent instances between playing ones
         return S.event_scenario(i) if i % 2 else S.bench_scenario(i)
-    eng, tpl, seeds, scens = _setup(oracle, 37, scen)
-    L, R = engine_run(eng, scens, 40)
-    oL, oR, *_ = oracle_run(oracle, tpl, seeds, scens, 40)
-    eL, xL = compare(L, oL)
-    eR, xR = compare(R, oR)
-    print(f"odd batch: max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL
-    assert float(np.abs(L[1]).max()) > 1e-3 and float(np.abs(L[3]).max()) > 1e-3
+    env = DISPATCH[dispatch]
+    eng, tpl, seeds, scens = _setup(oracle, 37, scen, chain=1, env=env)
+    ref = _ref_once("odd_batch", lambda: oracle_run(oracle, tpl, seeds, scens, 40))
+    _all_taps("odd batch", dispatch, ref, lambda chain: eng if chain == 1 else _organ(37, chain=chain, env=env),
+              lambda e: engine_run(e, scens, 40))
+    assert float(np.abs(ref[0][1]).max()) > 1e-3 and float(np.abs(ref[0][3]).max()) > 1e-3
 
 
-def test_gpu_full_chain_events(oracle):
-    eng, tpl, seeds, scens = _setup(oracle, 6, S.event_scenario)
-    L, R = engine_run(eng, scens, 72)
-    oL, oR, *_ = oracle_run(oracle, tpl, seeds, scens, 72)
-    eL, xL = compare(L, oL)
-    eR, xR = compare(R, oR)
-    print(f"events: max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL
+@dispatches
+def test_gpu_full_chain_events(oracle, dispatch):
+    """The event script through every stage tap and the outputs, bit for bit."""
+    env = DISPATCH[dispatch]
+    eng, tpl, seeds, scens = _setup(oracle, 6, S.event_scenario, chain=1, env=env)
+    ref = _ref_once("events", lambda: oracle_run(oracle, tpl, seeds, scens, 72))
+    _all_taps("events", dispatch, ref, lambda chain: eng if chain == 1 else _organ(6, chain=chain, env=env),
+              lambda e: engine_run(e, scens, 72))
 
 
+@dispatches
 @pytest.mark.parametrize("debug_flags", [0, 1])
-def test_gpu_vs_committed_reference_vectors(debug_flags):
+def test_gpu_vs_committed_reference_vectors(debug_flags, dispatch):
     """The HIP engine against the reference's own compiled chain (committed vectors,
     tests/golden/ref_vectors_*.npz): 44.1/48/96 kHz (whirl ring W=512/1024), 12-TET /
     19-TET / p4 / bagpipe4 / duodene / 5TET templates, event scripts, config-5 random
     drawbars, the parameter sweep (overdrive character, reverb mix, percussion variants,
     clusters, pedal keys, rotary stop <-> fast).  debug_flags=1 (TBF_DEBUG_FORCE_SERIAL)
     runs every guarded stage on its serial replay instead of the lane-parallel fast
-    path: both must match."""
+    path: both must match, bit for bit."""
     import json
     from pathlib import Path
     import tunebfree_amd as T
@@ -140,37 +253,34 @@ def test_gpu_vs_committed_reference_vectors(debug_flags):
     gold = Path(__file__).resolve().parent / "golden"
     z = load_vectors()
     tunings = json.loads((gold / "tunings.json").read_text())
-    worst = 0.0
     for c in json.loads(str(z["cases"])):
-        eng = T.Engine(sample_rate=c["sr"], device=0, chain=c["chain"], debug_flags=debug_flags)
+        eng = _engine(c["chain"], c["sr"], debug_flags, DISPATCH[dispatch])
         m = None if c["tuning"] is None else np.array(tunings[c["tuning"]], np.float64)
         tid = eng.template(mts128=m, seed=c["tpl_seed"])
         eng.add_instances([tid], [c["inst_seed"]])
         L, R = engine_run(eng, [scenario(*c["scenario"])], c["nblocks"])
         for got, k in ((L[0], "L"), (R[0], "R")):
-            err, exact = compare(got, z[f"{c['name']}/{k}"])
-            print(f"{c['name']}/{k}: max|err|={err:.3g} bit-exact={exact:.6f}")
-            worst = max(worst, err)
+            assert_bits(got, z[f"{c['name']}/{k}"], f"{c['name']}/{k} [{dispatch}]")
+        _ran(eng, dispatch, c["chain"])
         flags = eng.error_flags()
         print(f"{c['name']}: paths taken 0x{flags:x}")
         if debug_flags and c["chain"] == 0:
             assert flags & (T.engine.PATH_WH_ANGLE | T.engine.PATH_WH_MOTION | T.engine.PATH_RV_PHASE) == \
                 T.engine.PATH_WH_ANGLE | T.engine.PATH_WH_MOTION | T.engine.PATH_RV_PHASE, hex(flags)
         eng.close()
-    assert worst <= TOL
 
 
-def test_gpu_config5_mixed_tunings_96k(oracle):
+@dispatches
+def test_gpu_config5_mixed_tunings_96k(oracle, dispatch):
     """BASELINE config 5 shape at test size: 96 kHz, one shared template per tuning
     (7 tunings of the reference's tests), per-instance random drawbars, several
-    templates interleaved inside one launch."""
+    templates interleaved inside one launch (96 kHz: the 1024-sample whirl ring)."""
     import json
     from pathlib import Path
-    import tunebfree_amd as T
     from orc_bind import Template
     tunings = json.loads((Path(__file__).resolve().parent / "golden" / "tunings.json").read_text())
     names = sorted(tunings, key=lambda k: (tunings[k] is not None, k))
-    eng = T.Engine(sample_rate=96000.0, device=0)
+    eng = _engine(sr=96000.0, env=DISPATCH[dispatch])
     tids, tpls = {}, {}
     for j, nm in enumerate(names):
         m = None if tunings[nm] is None else np.array(tunings[nm], np.float64)
@@ -182,15 +292,15 @@ def test_gpu_config5_mixed_tunings_96k(oracle):
     eng.add_instances([tids[p] for p in pick], seeds)
     scens = [S.random_drawbar_scenario(i) for i in range(n)]
     L, R = engine_run(eng, scens, 24)
-    worst, ex = 0.0, []
-    for i in range(n):
-        oL, oR, *_ = oracle_run(oracle, tpls[pick[i]], [seeds[i]], [scens[i]], 24)
-        for a, b in ((L[i], oL[0]), (R[i], oR[0])):
-            e, x = compare(a, b)
-            worst = max(worst, e)
-            ex.append(x)
-    print(f"config5: {n} instances, {len(names)} tunings, max|err|={worst:.3g} bit-exact={min(ex):.6f}")
-    assert worst <= TOL
+    def ref():
+        rows = [oracle_run(oracle, tpls[pick[i]], [seeds[i]], [scens[i]], 24) for i in range(n)]
+        return [np.concatenate([r[k] for r in rows]) for k in range(2)]
+    oL, oR = _ref_once("config5", ref)
+    assert_bits(L, oL, f"config5 ({n} instances, {len(names)} tunings) [{dispatch}] L")
+    assert_bits(R, oR, f"config5 [{dispatch}] R")
+    assert eng.layout()["wring_len"] == 1024
+    _ran(eng, dispatch)
+    eng.close()
 
 
 def test_gpu_program_install_matches_clap_script(oracle):
@@ -207,10 +317,8 @@ def test_gpu_program_install_matches_clap_script(oracle):
         script.append([(0, "note", k, 1) for k in S.chord_for(i)])
     L, R = engine_run(eng, script, 40)
     oL, oR, *_ = oracle_run(oracle, tpl, seeds, scens, 40)
-    eL, xL = compare(L, oL)
-    eR, xR = compare(R, oR)
-    print(f"program install: max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(L, oL, "program install L")
+    assert_bits(R, oR, "program install R")
 
 
 def _script_events(eng, scens):
@@ -237,19 +345,18 @@ def test_gpu_render_events_one_call(oracle):
     eng.render_events_device(nb, _script_events(eng, scens), L.data_ptr(), R.data_ptr(), nb * 128)
     eng.synchronize()
     oL, oR, *_ = oracle_run(oracle, tpl, seeds, scens, nb)
-    eL, xL = compare(L.cpu().numpy(), oL)
-    eR, xR = compare(R.cpu().numpy(), oR)
-    print(f"render_events: max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(L.cpu().numpy(), oL, "render_events L")
+    assert_bits(R.cpu().numpy(), oR, "render_events R")
 
 
-def test_gpu_render_events_dense_across_chunks(oracle):
+@dispatches
+def test_gpu_render_events_dense_across_chunks(oracle, dispatch):
     """Events on many blocks and across the 64-block chunk boundary (notes every 7
     blocks, MIDI control functions, a programme change, whirl bypass toggles), split
     over two calls."""
     import torch
     from test_control_cpu import PGM
-    eng, tpl, seeds, scens = _setup(oracle, 3, S.bench_scenario)
+    eng, tpl, seeds, scens = _setup(oracle, 3, S.bench_scenario, env=DISPATCH[dispatch])
     assert eng.program_parse(PGM) == 4
     cid = eng.control_id("upper.drawbar4")
     assert cid >= 0 and eng.control_id("nope") < 0
@@ -284,11 +391,10 @@ def test_gpu_render_events_dense_across_chunks(oracle):
     eng.render_events_device(100, first, L.data_ptr(), R.data_ptr(), nb * 128)
     eng.render_events_device(60, rest, L[:, 100 * 128:].data_ptr(), R[:, 100 * 128:].data_ptr(), nb * 128)
     eng.synchronize()
-    oL, oR, *_ = oracle_run(oracle, tpl, seeds, oscen, nb)
-    eL, xL = compare(L.cpu().numpy(), oL)
-    eR, xR = compare(R.cpu().numpy(), oR)
-    print(f"dense events: max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL
+    oL, oR, *_ = _ref_once("dense_events", lambda: oracle_run(oracle, tpl, seeds, oscen, nb))
+    assert_bits(L.cpu().numpy(), oL, f"dense events [{dispatch}] L")
+    assert_bits(R.cpu().numpy(), oR, f"dense events [{dispatch}] R")
+    _ran(eng, dispatch)
 
 
 def test_gpu_dense_events_threaded_host_control(oracle):
@@ -351,10 +457,8 @@ def test_gpu_dense_events_threaded_host_control(oracle):
     sample = [0, 1, 3, 599, 1000, n - 1]
     tpl = Template(oracle, seed=7)
     oL, oR, *_ = oracle_run(oracle, tpl, [seeds[i] for i in sample], [sorted(oscen[i], key=lambda r: r[0]) for i in sample], nb)
-    eL, xL = compare(outs[0][0][sample], oL)
-    eR, xR = compare(outs[0][1][sample], oR)
-    print(f"threaded dense events vs oracle ({len(sample)} instances): max|err| L={eL:.3g} R={eR:.3g}")
-    assert max(eL, eR) <= TOL
+    assert_bits(outs[0][0][sample], oL, "threaded dense events vs oracle L")
+    assert_bits(outs[0][1][sample], oR, "threaded dense events vs oracle R")
 
 
 def test_gpu_mixed_events_threaded_full_and_patched_entries(oracle):
@@ -419,10 +523,8 @@ def test_gpu_mixed_events_threaded_full_and_patched_entries(oracle):
     sample = [0, 1, 2, 35, 700, n - 1]
     tpl = Template(oracle, seed=7)
     oL, oR, *_ = oracle_run(oracle, tpl, [seeds[i] for i in sample], [sorted(oscen[i], key=lambda r: r[0]) for i in sample], nb)
-    eL, xL = compare(outs[0][0][sample], oL)
-    eR, xR = compare(outs[0][1][sample], oR)
-    print(f"mixed events, threaded vs oracle: max|err| L={eL:.3g} R={eR:.3g} bit-exact {xL:.6f} {xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(outs[0][0][sample], oL, "mixed events, threaded vs oracle L")
+    assert_bits(outs[0][1][sample], oR, "mixed events, threaded vs oracle R")
 
 
 def test_gpu_device_front_end_note_chunks(oracle):
@@ -493,10 +595,8 @@ def test_gpu_device_front_end_note_chunks(oracle):
     sample = [0, 1, 2, 3, 550, n - 1]
     tpl = Template(oracle, seed=7)
     oL, oR, *_ = oracle_run(oracle, tpl, [seeds[i] for i in sample], [sorted(oscen[i], key=lambda r: r[0]) for i in sample], nb)
-    eL, xL = compare(outs[0][0][sample], oL)
-    eR, xR = compare(outs[0][1][sample], oR)
-    print(f"device front end vs oracle: max|err| L={eL:.3g} R={eR:.3g} bit-exact {xL:.6f} {xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(outs[0][0][sample], oL, "device front end vs oracle L")
+    assert_bits(outs[0][1][sample], oR, "device front end vs oracle R")
 
 
 def test_gpu_device_front_end_param_events(oracle):
@@ -567,10 +667,8 @@ def test_gpu_device_front_end_param_events(oracle):
     sample = [0, 1, 2, 3, 550, n - 1]
     tpl = Template(oracle, seed=7)
     oL, oR, *_ = oracle_run(oracle, tpl, [seeds[i] for i in sample], [sorted(oscen[i], key=lambda r: r[0]) for i in sample], nb)
-    eL, xL = compare(outs[0][0][sample], oL)
-    eR, xR = compare(outs[0][1][sample], oR)
-    print(f"device front end (params) vs oracle: max|err| L={eL:.3g} R={eR:.3g} bit-exact {xL:.6f} {xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(outs[0][0][sample], oL, "device front end (params) vs oracle L")
+    assert_bits(outs[0][1][sample], oR, "device front end (params) vs oracle R")
 
 
 def test_gpu_device_front_end_effect_events(oracle):
@@ -660,10 +758,8 @@ def test_gpu_device_front_end_effect_events(oracle):
     sample = [0, 1, 2, 7, 550, n - 1]
     tpl = Template(oracle, seed=7)
     oL, oR, *_ = oracle_run(oracle, tpl, [seeds[i] for i in sample], [oscen[i] for i in sample], nb)
-    eL, xL = compare(outs[0][0][sample], oL)
-    eR, xR = compare(outs[0][1][sample], oR)
-    print(f"device front end (effects) vs oracle: max|err| L={eL:.3g} R={eR:.3g} bit-exact {xL:.6f} {xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(outs[0][0][sample], oL, "device front end (effects) vs oracle L")
+    assert_bits(outs[0][1][sample], oR, "device front end (effects) vs oracle R")
 
 
 def test_gpu_device_front_end_small_chunks(oracle):
@@ -728,10 +824,8 @@ def test_gpu_device_front_end_small_chunks(oracle):
     sample = [0, 3, 41, n - 1]
     tpl = Template(oracle, seed=7)
     oL, oR, *_ = oracle_run(oracle, tpl, [seeds[i] for i in sample], [oscen[i] for i in sample], nb)
-    eL, xL = compare(outs[0][0][sample], oL)
-    eR, xR = compare(outs[0][1][sample], oR)
-    print(f"small device front-end chunks vs oracle: max|err| L={eL:.3g} R={eR:.3g} bit-exact {xL:.6f} {xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(outs[0][0][sample], oL, "small device front-end chunks vs oracle L")
+    assert_bits(outs[0][1][sample], oR, "small device front-end chunks vs oracle R")
 
 
 def test_gpu_steady_chunks(oracle):
@@ -781,10 +875,8 @@ def test_gpu_steady_chunks(oracle):
     tpl = Template(oracle, seed=7)
     oL, oR, *_ = oracle_run(oracle, tpl, [seeds[i] for i in sample], [sorted(oscen[i], key=lambda r: r[0]) for i in sample],
                             nb1 + nb2)
-    eL, xL = compare(outs[0][0][sample], oL)
-    eR, xR = compare(outs[0][1][sample], oR)
-    print(f"steady chunks vs oracle: max|err| L={eL:.3g} R={eR:.3g} bit-exact {xL:.6f} {xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(outs[0][0][sample], oL, "steady chunks vs oracle L")
+    assert_bits(outs[0][1][sample], oR, "steady chunks vs oracle R")
 
 
 def test_gpu_set_steady_chunk_at_runtime(oracle):
@@ -838,10 +930,8 @@ def test_gpu_set_steady_chunk_at_runtime(oracle):
     assert np.array_equal(outs[0][1].view(np.uint32), outs[1][1].view(np.uint32))
     pick = [0, 11, n - 1]
     oL, oR, *_ = oracle_run(oracle, Template(oracle, seed=7), [seeds[i] for i in pick], [scens[i] for i in pick], total)
-    eL, xL = compare(outs[0][0][pick], oL)
-    eR, xR = compare(outs[0][1][pick], oR)
-    print(f"set_steady_chunk at runtime vs oracle: max|err| L={eL:.3g} R={eR:.3g} bit-exact {xL:.6f} {xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(outs[0][0][pick], oL, "set_steady_chunk at runtime vs oracle L")
+    assert_bits(outs[0][1][pick], oR, "set_steady_chunk at runtime vs oracle R")
 
 
 def test_gpu_threaded_host_control_reports_errors():
@@ -926,6 +1016,10 @@ def test_gpu_engine_switches_bitexact(oracle):
                                  nb * 128)
         eng.synchronize()
         outs.append((L.cpu().numpy(), R.cpu().numpy()))
+        c = eng.launches()  # calls of 40 and 32 blocks: the LDS network kernel unless switched off
+        streaming = env.get("TBF_RV_LDS") == "0"
+        assert (c["k_rv_core"] > 0, c["k_rv_core_lds"] > 0) == (streaming, not streaming), (env, c)
+        assert c["k_whirl"] > 0 and c["k_whirl_split"] == 0, c  # 1100 instances: a full batch's whirl kernel
         eng.close()
         del L, R
     for env, (l, r) in zip(switches[1:], outs[1:]):
@@ -938,10 +1032,8 @@ def test_gpu_engine_switches_bitexact(oracle):
     sample = [0, 1, 4, 550, 1099]
     tpl = Template(oracle, seed=7)
     oL, oR, *_ = oracle_run(oracle, tpl, [seeds[i] for i in sample], [sorted(oscen[i], key=lambda r: r[0]) for i in sample], nb)
-    eL, _ = compare(outs[0][0][sample], oL)
-    eR, _ = compare(outs[0][1][sample], oR)
-    print(f"switches scenario vs oracle ({len(sample)} instances): max|err| L={eL:.3g} R={eR:.3g}")
-    assert max(eL, eR) <= TOL
+    assert_bits(outs[0][0][sample], oL, "switches scenario vs oracle L")
+    assert_bits(outs[0][1][sample], oR, "switches scenario vs oracle R")
 
 
 def test_gpu_synth_sound_irregular_periods(oracle, tunings):
@@ -994,11 +1086,8 @@ def test_gpu_synth_sound_irregular_periods(oracle, tunings):
     L, R = np.concatenate(outL, axis=1), np.concatenate(outR, axis=1)
     nb = -(-consumed // 128)
     oL, oR, *_ = oracle_run(oracle, t12, seeds, oscen, nb, templates=[t12, t19])
-    eL, xL = compare(L, oL[:, :consumed])
-    eR, xR = compare(R, oR[:, :consumed])
-    print(f"synth_sound {len(periods)} periods / {consumed} frames: max|err| L={eL:.3g} R={eR:.3g} "
-          f"bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(L, oL[:, :consumed], f"synth_sound {len(periods)} periods / {consumed} frames L")
+    assert_bits(R, oR[:, :consumed], "synth_sound R")
     eng.close()
 
 
@@ -1066,11 +1155,8 @@ def test_gpu_lv2_synth_sound_run_loop(oracle):
     R = np.concatenate([o[1] for o in out])[None]
     nb = -(-served // 128)
     oL, oR, *_ = oracle_run(oracle, tpl, [3001], oscen, nb)
-    eL, xL = compare(L, oL[:, :served])
-    eR, xR = compare(R, oR[:, :served])
-    print(f"lv2 run loop: {served} frames, {len(oscen[0])} events: max|err| L={eL:.3g} R={eR:.3g} "
-          f"bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(L, oL[:, :served], "lv2 run loop L")
+    assert_bits(R, oR[:, :served], "lv2 run loop R")
     eng.close()
 
 
@@ -1101,7 +1187,6 @@ def test_gpu_cli_host_synth_sound(oracle, tmp_path):
         pos += n * nf * 2
         done += nf
     tpl = Template(oracle, seed=5)
-    worst = 0.0
     for i in range(n):
         ch = Chain(oracle, tpl, 5 + 1000 + i)
         for (kind, a, v) in S.jazz1_params():
@@ -1109,9 +1194,8 @@ def test_gpu_cli_host_synth_sound(oracle, tmp_path):
         for k in (60, 64, 67, 72):
             ch.note(k, 1)
         oL, oR = ch.render(nb)
-        worst = max(worst, compare(L[i], oL)[0], compare(R[i], oR)[0])
-    print(f"cli host: max|err|={worst:.3g}")
-    assert worst <= TOL
+        assert_bits(L[i], oL, f"cli host, instance {i} L")
+        assert_bits(R[i], oR, f"cli host, instance {i} R")
 
 
 def _random_mts(seed):
@@ -1340,10 +1424,8 @@ def test_gpu_pipelined_chunks_across_calls(oracle):
     gR = np.concatenate([R0, R.cpu().numpy(), R2], axis=1)
     total = 1 + nb * calls + 3
     oL, oR, *_ = oracle_run(oracle, tpl, seeds, scens, total)
-    eL, xL = compare(gL, oL)
-    eR, xR = compare(gR, oR)
-    print(f"pipelined: {total} blocks, max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(gL, oL, "pipelined L")
+    assert_bits(gR, oR, "pipelined R")
 
 
 def test_gpu_reverb_network_group_boundaries(oracle):
@@ -1365,14 +1447,15 @@ def test_gpu_reverb_network_group_boundaries(oracle):
                 os.environ.pop(k, None)
         parts = [engine_run(eng, scens, 1)]  # block 0 carries the scenario's events
         parts += [eng.render(nb) for nb in calls]
+        c = eng.launches()
+        # block 0 and the 7-block call stream; with the LDS kernel on, the other six calls take it
+        assert (c["k_rv_core"], c["k_rv_core_lds"]) == ((8, 0) if env else (2, 6)), (env, c)
         eng.close()
         outs.append((np.concatenate([p[0] for p in parts], axis=1), np.concatenate([p[1] for p in parts], axis=1)))
     total = 1 + sum(calls)
     oL, oR, *_ = oracle_run(oracle, tpl, seeds, scens, total)
-    eL, xL = compare(outs[0][0], oL)
-    eR, xR = compare(outs[0][1], oR)
-    print(f"group boundaries: {total} blocks, max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(outs[0][0], oL, "group boundaries L")
+    assert_bits(outs[0][1], oR, "group boundaries R")
     for a, b in zip(outs[0], outs[1]):
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
@@ -1402,6 +1485,9 @@ def test_gpu_reverb_phase_binade_crossing(oracle):
                 eng.debug_reverb_phase(i, c, l, v - 0.0131 * i)
         parts = [engine_run(eng, scens, split[0])] + [eng.render(k) for k in split[1:]]
         assert eng.error_flags() & 8, "no phase run left its closed form: the crossing was not exercised"
+        c = eng.launches()
+        want = (len(split), 0) if env else (sum(k < 8 for k in split), sum(k >= 8 for k in split))
+        assert (c["k_rv_core"], c["k_rv_core_lds"]) == want, (env, split, c)
         eng.close()
         runs.append((np.concatenate([p[0] for p in parts], axis=1), np.concatenate([p[1] for p in parts], axis=1)))
     fn = oracle.orc_debug_rv_phase
@@ -1414,10 +1500,8 @@ def test_gpu_reverb_phase_binade_crossing(oracle):
         L, R, *_ = S.run(ch, sc, nb, stages=True)
         oL.append(L)
         oR.append(R)
-    eL, xL = compare(runs[0][0], np.stack(oL))
-    eR, xR = compare(runs[0][1], np.stack(oR))
-    print(f"binade crossing: max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(runs[0][0], np.stack(oL), "binade crossing L")
+    assert_bits(runs[0][1], np.stack(oR), "binade crossing R")
     for k, r in enumerate(runs[1:], 1):
         same = all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(runs[0], r))
         print(f"variant {k}: bit-identical to the single LDS call: {same}")
@@ -1437,10 +1521,8 @@ def test_gpu_full_size_bench_batch(oracle):
     assert L.shape == (n, nb * 128) and np.all(np.isfinite(L)) and np.all(np.isfinite(R))
     pick = [0, 1, 1023, 1365, 2047, 2048, 2730, 4094, 4095]
     oL, oR, *_ = oracle_run(oracle, tpl, [seeds[i] for i in pick], [scens[i] for i in pick], nb)
-    eL, xL = compare(L[pick], oL)
-    eR, xR = compare(R[pick], oR)
-    print(f"full size: max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(L[pick], oL, "full size L")
+    assert_bits(R[pick], oR, "full size R")
 
     half = n // 2
     import tunebfree_amd as T
@@ -1470,39 +1552,40 @@ def test_gpu_full_size_bench_batch(oracle):
     oL, oR, *_ = oracle_run(oracle, tpl, [seeds[i] for i in pick], [scens[i] for i in pick], 3 * nb)
     gL = np.concatenate([m[0][pick] for m in more], axis=1)
     gR = np.concatenate([m[1][pick] for m in more], axis=1)
-    eL, xL = compare(gL, oL[:, nb * 128:])
-    eR, xR = compare(gR, oR[:, nb * 128:])
-    print(f"steady calls: max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(gL, oL[:, nb * 128:], "steady calls L")
+    assert_bits(gR, oR[:, nb * 128:], "steady calls R")
 
 
+@dispatches
 @pytest.mark.parametrize("debug_flags", [0, 1])
-def test_gpu_parameter_sweep(oracle, debug_flags):
+def test_gpu_parameter_sweep(oracle, debug_flags, dispatch):
     """Parameter regions the bench registration does not reach (scenarios.sweep_scenario):
     overdrive character 0 / 0.3 / 0.9 / 1.0 and clean, reverb mix 0 / 0.7 / 1.0,
     percussion normal/soft x fast/slow x 2nd/3rd with retriggers, 13-key clusters,
     pedal keys 256..383 with pedal drawbars, rotary stop <-> fast transitions; 12
-    instances in one engine against the oracle, with the fast paths and with every
-    guarded stage forced onto its serial replay (TBF_DEBUG_FORCE_SERIAL)."""
+    instances in one engine against the oracle at every stage tap and the outputs, with
+    the fast paths and with every guarded stage forced onto its serial replay
+    (TBF_DEBUG_FORCE_SERIAL)."""
     import tunebfree_amd as T
     n, nb = 12, 72
-    eng, tpl, seeds, scens = _setup(oracle, n, S.sweep_scenario, debug_flags=debug_flags)
-    L, R = engine_run(eng, scens, nb)
-    oL, oR, oA, oB, oC = oracle_run(oracle, tpl, seeds, scens, nb)
-    eL, xL = compare(L, oL)
-    eR, xR = compare(R, oR)
-    flags = eng.error_flags()
-    print(f"sweep (debug {debug_flags}): max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f} "
-          f"paths 0x{flags:x}")
-    assert max(eL, eR) <= TOL
+    kw = dict(debug_flags=debug_flags, env=DISPATCH[dispatch])
+    eng, tpl, seeds, scens = _setup(oracle, n, S.sweep_scenario, chain=1, **kw)
+    ref = _ref_once("sweep", lambda: oracle_run(oracle, tpl, seeds, scens, nb))
+
+    def check(e):
+        flags = e.error_flags()
+        print(f"sweep (debug {debug_flags}): paths 0x{flags:x}")
+        if debug_flags:
+            want = T.engine.PATH_VIB_SERIAL | T.engine.PATH_WH_ANGLE | T.engine.PATH_WH_MOTION | T.engine.PATH_RV_PHASE
+            assert flags & want == want, hex(flags)
+    _all_taps(f"sweep (debug {debug_flags})", dispatch, ref,
+              lambda chain: eng if chain == 1 else _organ(n, chain=chain, **kw), lambda e: engine_run(e, scens, nb), check)
     for i in range(n):  # every instance sounds (no silent pass through a broken stage)
-        assert float(np.abs(oL[i]).max()) > 1e-3
-    if debug_flags:
-        want = T.engine.PATH_VIB_SERIAL | T.engine.PATH_WH_ANGLE | T.engine.PATH_WH_MOTION | T.engine.PATH_RV_PHASE
-        assert flags & want == want, hex(flags)
+        assert float(np.abs(ref[0][i]).max()) > 1e-3
 
 
-def test_gpu_random_character_and_reverb_mix(oracle):
+@dispatches
+def test_gpu_random_character_and_reverb_mix(oracle, dispatch):
     """seeded random overdrive character (0..1) and reverb mix (0..1)
     per instance, changed mid-render, against the oracle: the overdrive's FP64 sin
     passes and the reverb's sin / asin on the device library across continuous parameter
@@ -1517,13 +1600,12 @@ def test_gpu_random_character_and_reverb_mix(oracle):
         ev += [(0, "note", k, 1) for k in S.chord_for(i)]
         ev += [(24, "param", S.P_CHARACTER, float(ch[i, 1])), (24, "param", S.P_REVERB, float(rv[i, 1]))]
         return ev
-    eng, tpl, seeds, scens = _setup(oracle, n, scen)
+    eng, tpl, seeds, scens = _setup(oracle, n, scen, env=DISPATCH[dispatch])
     L, R = engine_run(eng, scens, nb)
-    oL, oR, *_ = oracle_run(oracle, tpl, seeds, scens, nb)
-    eL, xL = compare(L, oL)
-    eR, xR = compare(R, oR)
-    print(f"random character / reverb: max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL and min(xL, xR) == 1.0
+    oL, oR, *_ = _ref_once("random_character", lambda: oracle_run(oracle, tpl, seeds, scens, nb))
+    assert_bits(L, oL, f"random character / reverb [{dispatch}] L")
+    assert_bits(R, oR, f"random character / reverb [{dispatch}] R")
+    _ran(eng, dispatch)
 
 
 def test_gpu_whirl_control_functions(oracle):
@@ -1540,10 +1622,8 @@ def test_gpu_whirl_control_functions(oracle):
     eng, tpl, seeds, scens = _setup(oracle, n, S.whirl_control_scenario)
     L, R = engine_run(eng, scens, nb)
     oL, oR, *_ = oracle_run(oracle, tpl, seeds, scens, nb)
-    eL, xL = compare(L, oL)
-    eR, xR = compare(R, oR)
-    print(f"whirl control functions: max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) == 0.0 and min(xL, xR) == 1.0
+    assert_bits(L, oL, "whirl control functions L")
+    assert_bits(R, oR, "whirl control functions R")
     eng.close()
 
 
@@ -1555,7 +1635,7 @@ def test_gpu_whirl_split_kernel(oracle, rate):
     setters, a bypass toggle) at 48 kHz (ring of 512 samples) and 96 kHz (1024), with and
     without forced serial replays; and against the oracle.  (The engine picks k_whirl_split
     by itself at rings > 512 samples or <= 1 instance per CU, TBF_WHIRL_SPLIT=0 / 1 force
-    either; most GPU tests here run small batches, so they run k_whirl_split.)"""
+    either; the tests marked @dispatches run both.)"""
     import os
     import torch
     import tunebfree_amd as T
@@ -1601,10 +1681,8 @@ def test_gpu_whirl_split_kernel(oracle, rate):
         sample = [0, 5, 13, n - 1]
         tpl = Template(oracle, seed=7)
         oL, oR, *_ = oracle_run(oracle, tpl, [seeds[i] for i in sample], [scens[i] for i in sample], nb)
-        eL, xL = compare(outs[("1", 0)][0][sample], oL)
-        eR, xR = compare(outs[("1", 0)][1][sample], oR)
-        print(f"k_whirl_split vs oracle: max|err| L={eL:.3g} R={eR:.3g} bit-exact {xL:.6f} {xR:.6f}")
-        assert max(eL, eR) <= TOL
+        assert_bits(outs[("1", 0)][0][sample], oL, "k_whirl_split vs oracle L")
+        assert_bits(outs[("1", 0)][1][sample], oR, "k_whirl_split vs oracle R")
 
 
 def test_gpu_whirl_control_events_threaded(oracle):
@@ -1651,10 +1729,8 @@ def test_gpu_whirl_control_events_threaded(oracle):
     sample = [0, 1, 219, 220, 221, 440, 659, 660, 880, 1099]  # both sides of the 220-instance ranges
     tpl = Template(oracle, seed=7)
     oL, oR, *_ = oracle_run(oracle, tpl, [seeds[i] for i in sample], [scens[i] for i in sample], nb)
-    eL, xL = compare(outs[0][0][sample], oL)
-    eR, xR = compare(outs[0][1][sample], oR)
-    print(f"whirl control events, threaded ({len(sample)} instances vs oracle): max|err| L={eL:.3g} R={eR:.3g}")
-    assert max(eL, eR) == 0.0 and min(xL, xR) == 1.0
+    assert_bits(outs[0][0][sample], oL, "whirl control events, threaded L")
+    assert_bits(outs[0][1][sample], oR, "whirl control events, threaded R")
 
 
 def _ring_window(max_ahead):
@@ -1666,73 +1742,77 @@ def _ring_window(max_ahead):
     return w
 
 
-def test_gpu_cfg_widest_ring_96k(oracle):
-    """The largest compact whirl ring (k_whirl<2048>): 96 kHz with an 80 cm horn, 4
-    instances over the cfg script, against the oracle."""
+@dispatches
+def test_gpu_cfg_widest_ring_96k(oracle, dispatch):
+    """The largest compact whirl ring (k_whirl<2048> / k_whirl_split<2048>): 96 kHz with an
+    80 cm horn, 4 instances over the cfg script, against the oracle."""
     cfg = {"whirl.horn.radius": 80, "whirl.mic.distance": 60}
-    eng, tpl, seeds, scens = _setup(oracle, 4, S.cfg_scenario, sr=96000.0, cfg=cfg)
+    eng, tpl, seeds, scens = _setup(oracle, 4, S.cfg_scenario, sr=96000.0, cfg=cfg, env=DISPATCH[dispatch])
     lay = eng.layout()
     assert lay["wring_len"] == _ring_window(lay["max_ahead"]) == 2048, lay
     L, R = engine_run(eng, scens, 72)
-    oL, oR, *_ = oracle_run(oracle, tpl, seeds, scens, 72)
-    eL, xL = compare(L, oL)
-    eR, xR = compare(R, oR)
-    print(f"96k / 2048-sample ring: max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL
+    oL, oR, *_ = _ref_once("widest_ring", lambda: oracle_run(oracle, tpl, seeds, scens, 72))
+    assert_bits(L, oL, f"96k / 2048-sample ring [{dispatch}] L")
+    assert_bits(R, oR, f"96k / 2048-sample ring [{dispatch}] R")
+    _ran(eng, dispatch)
     eng.close()
 
 
+@dispatches
 @pytest.mark.parametrize("name", sorted(S.CFG_SETS))
-def test_gpu_cfg_keys(oracle, name):
+def test_gpu_cfg_keys(oracle, name, dispatch):
     """§8(f) row 4: each cfg key set (scenarios.CFG_SETS — whirl geometry, the three
     whirl filters, speed preset + rpm + brake positions, horn/drum mic mix and widths,
     scanner rate/depths, reverb.mix, percussion gains/buses, the four envelope models)
     given to the engine through tbf_config_parse before its templates and instances,
     against the oracle under the same orc_cfg (itself bit-identical to the reference's
-    own structs, test_oracle_cpu.py::test_oracle_cfg_vs_reference): every stage tap,
-    6 instances over the rotor stop -> fast -> brake -> slow script."""
+    own structs, test_oracle_cpu.py::test_oracle_cfg_vs_reference): every stage tap
+    (engines of chain 1, 2, 3) and the outputs, 6 instances over the rotor stop -> fast ->
+    brake -> slow script.  geometry_wide has the 1024-sample ring (k_whirl<1024> under
+    dispatch=full)."""
     n, nb = 6, 72
-    eng, tpl, seeds, scens = _setup(oracle, n, S.cfg_scenario, cfg=S.CFG_SETS[name])
+    kw = dict(cfg=S.CFG_SETS[name], env=DISPATCH[dispatch])
+    eng, tpl, seeds, scens = _setup(oracle, n, S.cfg_scenario, chain=1, **kw)
     lay = eng.layout()
     assert lay["wring_len"] == _ring_window(lay["max_ahead"]) == (1024 if name == "geometry_wide" else 512), lay
-    L, R = engine_run(eng, scens, nb)
-    oL, oR, oA, oB, oC = oracle_run(oracle, tpl, seeds, scens, nb)
-    eL, xL = compare(L, oL)
-    eR, xR = compare(R, oR)
-    print(f"cfg {name}: max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL
+    ref = _ref_once(("cfg", name), lambda: oracle_run(oracle, tpl, seeds, scens, nb))
+    _all_taps(f"cfg {name}", dispatch, ref, lambda chain: eng if chain == 1 else _organ(n, chain=chain, **kw),
+              lambda e: engine_run(e, scens, nb))
     for i in range(n):
-        assert float(np.abs(oL[i]).max()) > 1e-3
-    eng.close()
+        assert float(np.abs(ref[0][i]).max()) > 1e-3
 
 
-def test_gpu_retune_mid_phrase(oracle, tunings):
+@dispatches
+def test_gpu_retune_mid_phrase(oracle, tunings, dispatch):
     """§8(f) row 3, the MTS-ESP retune (tbf_instance_retune = the CLAP reinitToneGen,
     src/clap.cpp:129-157): 6 instances switch mid-phrase to a 19-TET template built on
     the device (tbf_templates_create) and later back to their 12-TET template; held keys
     drop, drawbars / vibrato come back from the CLAP parameters (their defaults where
     never set), the routing word stays, preamp / reverb / whirl state goes on.  Against
     the oracle's orc_inst_retune (itself bit-identical to the reference's own calls,
-    test_oracle_cpu.py::test_oracle_retune_vs_reference), every stage tap."""
+    test_oracle_cpu.py::test_oracle_retune_vs_reference), every stage tap (engines of
+    chain 1, 2, 3) and the outputs."""
     from orc_bind import Template
     m19 = np.asarray(tunings["19TET"], np.float64)
     n, nb = 6, 64
-    eng = _engine()
-    tid12 = eng.template(seed=7)
-    tid19 = eng.templates([8], mts128=m19[None])[0]
     seeds = [1000 + 17 * i for i in range(n)]
-    eng.add_instances([tid12] * n, seeds)
-    t12, t19 = Template(oracle, seed=7), Template(oracle, mts128=m19, seed=8)
     scens = [S.retune_scenario(i, at=20, to=1) + [(44, "retune", 0, 0), (44, "note", 62 + i, 1)] for i in range(n)]
-    L, R = engine_run(eng, scens, nb, tids=[tid12, tid19])
-    oL, oR, *_ = oracle_run(oracle, t12, seeds, scens, nb, templates=[t12, t19])
-    eL, xL = compare(L, oL)
-    eR, xR = compare(R, oR)
-    print(f"retune: max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL
+    tids = {}
+
+    def make(chain):
+        eng = _engine(chain, env=DISPATCH[dispatch])
+        tids[0] = eng.template(seed=7)
+        tids[1] = eng.templates([8], mts128=m19[None])[0]
+        eng.add_instances([tids[0]] * n, seeds)
+        return eng
+
+    def ref():
+        t12, t19 = Template(oracle, seed=7), Template(oracle, mts128=m19, seed=8)
+        return oracle_run(oracle, t12, seeds, scens, nb, templates=[t12, t19])
+    ref = _ref_once("retune", ref)
+    _all_taps("retune", dispatch, ref, make, lambda e: engine_run(e, scens, nb, tids=[tids[0], tids[1]]))
     for i in range(n):
-        assert float(np.abs(oL[i, 21 * 128:44 * 128]).max()) > 1e-3  # the retuned organ sounds
-    eng.close()
+        assert float(np.abs(ref[0][i, 21 * 128:44 * 128]).max()) > 1e-3  # the retuned organ sounds
 
 
 @pytest.mark.parametrize("scen", ["events", "sweep", "reroute", "retune"])
@@ -1868,10 +1948,8 @@ def test_gpu_device_control_large_clusters(oracle):
     sample = [0, 1, 2, 29]
     tpl = Template(oracle, seed=7)
     oL, oR, *_ = oracle_run(oracle, tpl, [seeds[i] for i in sample], [sorted(oscen[i], key=lambda r: r[0]) for i in sample], nb)
-    eL, xL = compare(outs[0][0][sample], oL)
-    eR, xR = compare(outs[0][1][sample], oR)
-    print(f"large clusters vs oracle: max|err| L={eL:.3g} R={eR:.3g} bit-exact {xL:.6f} {xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(outs[0][0][sample], oL, "large clusters vs oracle L")
+    assert_bits(outs[0][1][sample], oR, "large clusters vs oracle R")
 
 
 def test_gpu_reroute_without_key_events(oracle):
@@ -1882,10 +1960,8 @@ def test_gpu_reroute_without_key_events(oracle):
     eng, tpl, seeds, scens = _setup(oracle, 4, S.reroute_scenario)
     L, R = engine_run(eng, scens, 56)
     oL, oR, *_ = oracle_run(oracle, tpl, seeds, scens, 56)
-    eL, xL = compare(L, oL)
-    eR, xR = compare(R, oR)
-    print(f"reroute: max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(L, oL, "reroute L")
+    assert_bits(R, oR, "reroute R")
 
 
 def test_gpu_forced_serial_events_and_taps(oracle):
@@ -1895,17 +1971,13 @@ def test_gpu_forced_serial_events_and_taps(oracle):
     eng, tpl, seeds, scens = _setup(oracle, 4, S.event_scenario, debug_flags=1)
     L, R = engine_run(eng, scens, 72)
     oL, oR, *_ = oracle_run(oracle, tpl, seeds, scens, 72)
-    eL, xL = compare(L, oL)
-    eR, xR = compare(R, oR)
-    print(f"forced events: max|err| L={eL:.3g} R={eR:.3g} bit-exact L={xL:.6f} R={xR:.6f}")
-    assert max(eL, eR) <= TOL
+    assert_bits(L, oL, "forced events L")
+    assert_bits(R, oR, "forced events R")
     for tap, idx in ((2, 3), (3, 4)):
         eng, tpl, seeds, scens = _setup(oracle, 3, S.sweep_scenario, chain=tap, debug_flags=1)
         L, _ = engine_run(eng, scens, 40)
         ref = oracle_run(oracle, tpl, seeds, scens, 40)[idx]
-        err, exact = compare(L, ref)
-        print(f"forced tap {tap}: max|err|={err:.3g} bit-exact={exact:.6f}")
-        assert err <= TOL
+        assert_bits(L, ref, f"forced tap {tap}")
 
 
 @pytest.mark.parametrize("via_events", [True, False])
@@ -1940,7 +2012,6 @@ def test_gpu_add_instances_after_render_then_events(oracle, via_events):
                for i in range(5)]
         L, R = engine_run(eng, sc5, nb)
     tpl = Template(oracle, seed=7)
-    bad = []
     for i in range(5):
         off = 10 if i < 3 else 0  # old instances: the call starts at their block 10
         sc = list(S.bench_scenario(i))
@@ -1950,14 +2021,8 @@ def test_gpu_add_instances_after_render_then_events(oracle, via_events):
         oL, oR, *_ = oracle_run(oracle, tpl, [seeds[i]], [sc], nb + off)
         gl = np.concatenate([L0[i], L[i]]) if off else L[i]
         gr = np.concatenate([R0[i], R[i]]) if off else R[i]
-        e1, x1 = compare(gl, oL[0])
-        e2, x2 = compare(gr, oR[0])
-        d = np.nonzero(gl.view(np.uint32) != oL[0].view(np.uint32))[0]
-        print(f"instance {i}: max|err| {max(e1, e2):.3g} bit-exact {min(x1, x2):.6f} "
-              f"first differing block {d[0] // 128 if len(d) else None}")
-        if max(e1, e2) > TOL:
-            bad.append(i)
-    assert not bad, bad
+        assert_bits(gl, oL[0], f"instance {i} L")
+        assert_bits(gr, oR[0], f"instance {i} R")
 
 
 def test_gpu_sin_fast_paths_are_ocml_bits():
@@ -2038,3 +2103,155 @@ def test_bench_plain_run_dumps_last_timed_step(tmp_path):
             assert np.array_equal(got[name][j].view(np.uint32), o.view(np.uint32)), (name, g)
             assert np.array_equal(got[name + "_tail"][g].view(np.uint32), o[-tail:].view(np.uint32)), (name, g)
     assert float(np.abs(got["L"]).max()) > 1e-3
+
+
+def _event_rows(scens, first=0, count=None):
+    """the tbf_event rows of the scripts' note / parameter events in blocks
+    [first, first + count), relative to `first`"""
+    rows = [(b - first, i, 0 if kind == "note" else 1, a, float(v)) for i, sc in enumerate(scens)
+            for (b, kind, a, v) in sc if b >= first and (count is None or b < first + count)]
+    return sorted(rows, key=lambda r: r[0])
+
+
+def test_gpu_steady_chunk_not_a_power_of_two(oracle):
+    """tbf.h promises bit-identical renders at every TBF_STEADY_CHUNK / tbf_set_steady_chunk
+    value in [64, 2048], not only at powers of two.  12 instances (event and bench scripts
+    alternating, events up to block 56), one tbf_render_events call of 300 blocks on the
+    full-batch kernels (dispatch=full), under chunks of 64, 65, 100 and 129 blocks: a
+    65-block launch is 130 sub-blocks = 11 x 11 + 9 in k_rv_core_lds, a 100-block one 200 =
+    18 x 11 + 2, and the stage buffers take a stride that is no power of two.  Every run
+    equals the 64-block run bit for bit, and 4 instances equal the oracle.  Then an engine
+    at the default chunk is set to 100 at run time (tbf_set_steady_chunk returns 100,
+    tbf_debug_chunks reports it) and renders 130 more blocks (100 + 30) and then 5 (under 8:
+    the streaming k_rv_core on the 100-block stage stride), like the 64-block engine.  The
+    launch counts are those of the chunk rule: the 64 blocks with events, then chunks of the
+    set length while more than 64 blocks remain, then the rest."""
+    import torch
+    from orc_bind import Template
+    n, nb, more, tail = 12, 300, 130, 5
+    seeds = [4000 + i for i in range(n)]
+    scens = [S.event_scenario(i) if i % 2 else S.bench_scenario(i) for i in range(n)]
+    assert max(b for sc in scens for (b, *_r) in sc) == 56
+    total = nb + more + tail
+    L = torch.zeros((n, total * 128), dtype=torch.float32, device="cuda")
+    R = torch.zeros_like(L)
+    stride = total * 128
+
+    def chunks(first, blocks, steady):
+        """chunk lengths of a call: `first` blocks with events, then steady chunks"""
+        lens, b = [first] * (first > 0), first
+        while b < blocks:
+            lens.append(min(steady, blocks - b) if blocks - b > 64 else blocks - b)
+            b += lens[-1]
+        return lens
+
+    def counts(lens):
+        """(launches, those of the streaming reverb network: chunks under 8 blocks)"""
+        return len(lens), sum(k < 8 for k in lens)
+
+    def go_on(eng):
+        for off, k in ((nb, more), (nb + more, tail)):
+            eng.render_device(k, L[:, off * 128:].data_ptr(), R[:, off * 128:].data_ptr(), stride)
+        eng.synchronize()
+
+    def render(steady):
+        eng = _engine(env=dict(DISPATCH["full"], **({"TBF_STEADY_CHUNK": steady} if steady else {})))
+        tid = eng.template(seed=7)
+        eng.add_instances([tid] * n, seeds)
+        assert eng.chunks() == (64, int(steady or 512))
+        L.zero_(), R.zero_()
+        eng.render_events_device(nb, eng.events(_event_rows(scens)), L.data_ptr(), R.data_ptr(), stride)
+        eng.synchronize()
+        return eng
+
+    def out(upto):
+        return L[:, :upto * 128].cpu().numpy(), R[:, :upto * 128].cpu().numpy()
+
+    base = render("64")
+    go_on(base)
+    ref = out(total)
+    c = _ran(base, "full", k_rv_core_lds=True, k_rv_core=True)
+    assert (c["k_whirl"], c["k_rv_core"]) == counts(chunks(64, nb, 64) + chunks(0, more, 64) + [tail]), c
+    base.close()
+    for steady in ("65", "100", "129"):
+        eng = render(steady)
+        got = out(nb)
+        c = _ran(eng, "full", k_rv_core_lds=True, k_rv_core=False)
+        print(f"TBF_STEADY_CHUNK={steady}: launches {c}")
+        assert c["k_whirl"] == c["k_rv_core_lds"] == c["k_tonegen"] == len(chunks(64, nb, int(steady))), (steady, c)
+        eng.close()
+        for g, r, ch in zip(got, ref, "LR"):
+            assert_bits(g, r[:, :nb * 128], f"chunks of {steady} blocks vs 64: {ch}")
+    eng = render(None)
+    assert eng.set_steady_chunk(100) == 100 and eng.chunks() == (64, 100)
+    go_on(eng)
+    got = out(total)
+    c = _ran(eng, "full", k_rv_core_lds=True, k_rv_core=True)
+    assert (c["k_whirl"], c["k_rv_core"]) == counts(chunks(64, nb, 512) + chunks(0, more, 100) + [tail]), c
+    eng.close()
+    for g, r, ch in zip(got, ref, "LR"):
+        assert_bits(g, r, f"default chunk, then set_steady_chunk (100), vs 64: {ch}")
+    pick = [0, 1, 6, n - 1]
+    oL, oR, *_ = oracle_run(oracle, Template(oracle, seed=7), [seeds[i] for i in pick], [scens[i] for i in pick], total)
+    assert_bits(ref[0][pick], oL, "64-block chunks vs oracle L")
+    assert_bits(ref[1][pick], oR, "64-block chunks vs oracle R")
+
+
+SENTINEL = 0x7FC0BEEF  # a quiet NaN no render produces
+
+
+@pytest.mark.parametrize("chain,dispatch", [(0, "full"), (0, "small"), (1, "small"), (2, "small"), (3, "small")])
+def test_gpu_nothing_written_outside_the_rows(chain, dispatch):
+    """tbf.h: stride and output pointers need only float alignment, and instance i writes
+    out[i * stride + 0 .. nblocks*128) only.  5 instances (event and bench scripts) rendered
+    in calls of 1, 7 and 65 blocks continued on one engine, through tbf_render_device and
+    through tbf_render_events, into buffers filled with a NaN sentinel before each call, at
+    a pointer 3 floats into the allocation and row strides of nblocks*128 + 1 and + 132: the
+    rows equal, bit for bit, the same calls into exact-size buffers, and every word before,
+    between and after the rows still holds the sentinel.  (k_whirl holds back its first
+    store of a launch; a row's first and last samples sit one word from its neighbours'.)
+    The full chain under both kernel dispatches and the three stage taps, whose outputs
+    k_tonegen / k_mixpre, k_mixpre and k_rv_post store."""
+    import torch
+    n, calls = 5, ((0, 1), (1, 7), (8, 65))
+    seeds = [1000 + 17 * i for i in range(n)]
+    scens = [S.event_scenario(i) if i % 2 else S.bench_scenario(i) for i in range(n)]
+
+    def run(events, pad):
+        """yields, per call, (first block, blocks, L words, R words, row stride) with the
+        outputs read back as int32 words of the whole allocation"""
+        eng = _organ(n, chain=chain, env=DISPATCH[dispatch])
+        for (s, k) in calls:
+            stride = k * 128 + (pad or 0)
+            size = 3 + (n - 1) * stride + k * 128 + 200 if pad is not None else n * k * 128
+            off = 3 if pad is not None else 0
+            bufs = [torch.full((size,), SENTINEL, dtype=torch.int32, device="cuda") for _ in range(2)]
+            ptrs = [b.data_ptr() + 4 * off for b in bufs]
+            if events:
+                eng.render_events_device(k, eng.events(_event_rows(scens, s, k)), ptrs[0], ptrs[1], stride)
+            else:  # the call's events at its first block, through tbf_note / tbf_set_param
+                for (_b, i, kind, a, v) in _event_rows(scens, s, k):
+                    (eng.set_param if kind else eng.note)(i, a, v)
+                eng.render_device(k, ptrs[0], ptrs[1], stride)
+            eng.synchronize()
+            yield s, k, bufs[0].cpu().numpy(), bufs[1].cpu().numpy(), stride
+        _ran(eng, dispatch, chain)
+        eng.close()
+
+    for events in (False, True):
+        plain = [(wl.view(np.float32).reshape(n, -1), wr.view(np.float32).reshape(n, -1))
+                 for (_s, _k, wl, wr, _st) in run(events, None)]
+        assert all(np.isfinite(p[0]).all() and np.isfinite(p[1]).all() for p in plain)
+        assert float(np.abs(plain[-1][0]).max()) > 1e-3  # it sounds
+        for pad in (1, 132):
+            for (s, k, wl, wr, stride), want in zip(run(events, pad), plain):
+                for words, ref, ch in ((wl, want[0], "L"), (wr, want[1], "R")):
+                    what = f"{'render_events' if events else 'render_device'}, chain {chain}, {k} blocks at {s}, " \
+                           f"stride {stride}: {ch}"
+                    rows = np.zeros(words.size, bool)
+                    for i in range(n):
+                        rows[3 + i * stride: 3 + i * stride + k * 128] = True
+                    hit = np.nonzero(~rows & (words != SENTINEL))[0]
+                    assert hit.size == 0, f"{what}: {hit.size} words outside the rows written, first at word " \
+                                          f"{hit[0]} (row stride {stride}, rows start at word 3)"
+                    assert_bits(words[rows].view(np.float32).reshape(n, k * 128), ref, what)

@@ -9,11 +9,10 @@ launch edges, bypassed blocks, new parameter sets and rotor selections where tha
 loaded, written back or bypassed."""
 import os
 
-import numpy as np
 import pytest
 
 import scenarios as S
-from enginerun import oracle_run
+from enginerun import assert_bits, oracle_run
 
 pytestmark = pytest.mark.gpu
 
@@ -61,9 +60,7 @@ def _render(scens, calls, rate=48000.0, dbg=0, split="0", steady=None):
 
 def _same(a, b, what):
     for ch in (0, 1):
-        x, y = a[ch].view(np.uint32), b[ch].view(np.uint32)
-        bad = np.argwhere(x != y)
-        assert bad.size == 0, f"{what}: channel {ch}, {len(bad)} samples differ, first at (instance, sample) {tuple(bad[0])}"
+        assert_bits(a[ch], b[ch], f"{what}: {'LR'[ch]}")
 
 
 def _oracle(oracle, scens, nb, rate=48000.0):

@@ -205,6 +205,59 @@ def test_render_refuses_without_device():
     eng.close()
 
 
+def test_host_engine_launches_are_zero():
+    """tbf_debug_launches on a host engine (device -1): nothing is ever launched, so every
+    kernel variant's count is 0, before and after a refused render; the index order is
+    the documented one, and a short or empty count array is honoured."""
+    eng = T.Engine(device=-1)
+    assert tuple(eng.launches()) == ("k_tonegen", "k_tonegen_ranges", "k_rv_core", "k_rv_core_lds", "k_whirl",
+                                     "k_whirl_split")
+    assert all(v == 0 for v in eng.launches().values())
+    tid = eng.template(seed=1)
+    eng.add_instances([tid], [1])
+    with pytest.raises(T.TbfError):
+        eng.render(1)
+    assert all(v == 0 for v in eng.launches().values())
+    fn = T.load_library().tbf_debug_launches
+    fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]
+    two = np.full(3, 77, np.uint64)
+    assert fn(eng._h, two.ctypes.data, 2) == 6 and two.tolist() == [0, 0, 77]
+    assert fn(eng._h, None, 0) == 6
+    assert fn(eng._h, None, 2) < 0 and fn(None, two.ctypes.data, 2) < 0
+    eng.close()
+
+
+def test_assert_bits_reports_first_differing_sample():
+    """enginerun.assert_bits, the GPU parity gate: identical arrays pass (NaN payloads and
+    signed zeros compared as bits), one flipped mantissa bit fails and is reported at its
+    (instance, block, sample in block) with both values and the count, and a shape mismatch
+    fails."""
+    from enginerun import assert_bits
+    rng = np.random.default_rng(3)
+    ref = rng.standard_normal((5, 3 * 128)).astype(np.float32)
+    ref[1, 7] = np.nan
+    ref[2, 9] = -0.0
+    assert_bits(ref.copy(), ref, "same")
+    assert_bits(ref[3].copy(), ref[3], "one row")
+    got = ref.copy()
+    got.view(np.uint32)[3, 2 * 128 + 17] ^= 1
+    with pytest.raises(AssertionError) as ei:
+        assert_bits(got, ref, "flip")
+    msg = str(ei.value)
+    assert "flip: 1 of 1920 samples differ" in msg and "instance 3, block 2, sample 17" in msg, msg
+    assert repr(got[3, 273]) in msg and repr(ref[3, 273]) in msg and "max|err|=" in msg, msg
+    got.view(np.uint32)[4, 5] ^= 1 << 31  # a later one: the count grows, the first stays
+    with pytest.raises(AssertionError, match=r"2 of 1920 samples differ; first at instance 3, block 2, sample 17"):
+        assert_bits(got, ref, "flip")
+    zero = np.zeros((1, 128), np.float32)
+    with pytest.raises(AssertionError, match="instance 0, block 0, sample 0"):
+        assert_bits(-zero, zero, "signed zero")
+    with pytest.raises(AssertionError, match="shape"):
+        assert_bits(ref[:, :128], ref, "shape")
+    with pytest.raises(AssertionError, match="shape"):
+        assert_bits(ref.reshape(-1), ref, "shape")
+
+
 def test_param_and_note_validation():
     eng = T.Engine(device=-1)
     tid = eng.template(seed=1)

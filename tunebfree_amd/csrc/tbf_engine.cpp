@@ -2109,6 +2109,22 @@ static int stageBuffers (tbf_engine* e, uint32_t n, uint32_t nblocks, hipStream_
 	}
 }
 
+/* tbf_launch_stage, and the count of the kernel variant it picks (tbf_debug_launches): the
+ * same fields it switches on, read here on the host */
+static int launchStage (tbf_engine* e, const tbf_launch& P, int k, hipStream_t s)
+{
+	const int rc = tbf_launch_stage (&P, k, s);
+	if (rc || P.nInst == 0 || P.nBlocks == 0)
+		return rc;
+	if (k == 0)
+		e->launches[P.tgSplit > 1 && !P.ctlIdx ? TBF_LAUNCH_TONEGEN_RANGES : TBF_LAUNCH_TONEGEN]++;
+	else if (k == 3)
+		e->launches[P.rvLds && P.nBlocks >= RVL_MIN_BLOCKS ? TBF_LAUNCH_RV_CORE_LDS : TBF_LAUNCH_RV_CORE]++;
+	else if (k == 5)
+		e->launches[P.whSplit ? TBF_LAUNCH_WHIRL_SPLIT : TBF_LAUNCH_WHIRL]++;
+	return rc;
+}
+
 static int renderImpl (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, uint64_t stride, hipStream_t s,
                        const tbf_event* ev = nullptr, uint32_t nev = 0)
 {
@@ -2644,7 +2660,7 @@ static int renderImpl (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, ui
 					HIPCHK (hipEventCreate (&e1));
 					HIPCHK (hipEventRecord (e0, sk));
 				}
-				rc = tbf_launch_stage (&P, k, sk);
+				rc = launchStage (e, P, k, sk);
 				if (rc)
 					return fail (rc, std::string ("kernel launch failed: ") + hipGetErrorString (hipGetLastError ()));
 				if (e->timeOn) {
@@ -2667,7 +2683,7 @@ static int renderImpl (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, ui
 				HIPCHK (hipEventCreate (&e1));
 				HIPCHK (hipEventRecord (e0, s));
 			}
-			rc = tbf_launch_stage (&P, k, s);
+			rc = launchStage (e, P, k, s);
 			if (rc)
 				return fail (rc, std::string ("kernel launch failed: ") + hipGetErrorString (hipGetLastError ()));
 			if (e->timeOn) {
@@ -2932,6 +2948,15 @@ int tbf_debug_front_chunks (const tbf_engine* e, uint64_t* device_chunks, uint64
 	return 0;
 }
 
+int tbf_debug_launches (const tbf_engine* e, uint64_t* counts, uint32_t cap)
+{
+	if (!e || (!counts && cap))
+		return fail (-22, "null argument");
+	for (uint32_t i = 0; i < cap && i < TBF_LAUNCH_KINDS; i++)
+		counts[i] = e->launches[i];
+	return TBF_LAUNCH_KINDS;
+}
+
 int tbf_set_steady_chunk (tbf_engine* e, uint32_t blocks)
 {
 	if (!e)
@@ -2946,7 +2971,7 @@ int tbf_set_steady_chunk (tbf_engine* e, uint32_t blocks)
 		if (hipSetDevice (e->cfg.device) == hipSuccess && hipMemGetInfo (&freeB, &totalB) == hipSuccess) {
 			const size_t held = (e->mid0.cap + e->mid1.cap + e->mid2.cap) * sizeof (float) + (e->rvA.cap + e->rvB.cap) * sizeof (double);
 			while (e->steadyChunk > TBF_CHUNK && stageFootprint (e, n, e->steadyChunk) > freeB + held)
-				e->steadyChunk /= 2;
+				e->steadyChunk = std::max (e->steadyChunk / 2, (uint32_t)TBF_CHUNK); /* 100 -> 64, not 50 */
 		} else
 			(void)hipGetLastError ();
 	}

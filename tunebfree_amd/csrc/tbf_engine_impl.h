@@ -375,6 +375,9 @@ struct tbf_engine {
 	 * chunk parity */
 	uint32_t                                stageBlocks = 0, stageN = 0;
 	uint64_t                                frontChunks[2] = {0, 0}; /* chunks with events: device, host front end */
+	/* kernel variants launched (tbf_debug_launches, TBF_LAUNCH_*): k_tonegen with one block
+	 * range / several, k_rv_core, k_rv_core_lds, k_whirl, k_whirl_split */
+	uint64_t                                launches[6] = {0, 0, 0, 0, 0, 0};
 	bool                                    stageDbl[5] = {true, true, true, true, true}; /* mid0 mid1 rvA rvB mid2 */
 	/* programme table (.pgm), src/program.h:26 MAXPROGS; pgm.controller.offset */
 	std::vector<Programme>                  progs = std::vector<Programme> (129);

@@ -1768,7 +1768,6 @@ constexpr int rvl_lofs (int l) { return l == 0 ? 0 : rvl_lofs (l - 1) + ((RVL_DL
 constexpr int RVL_LOFS[12] = {rvl_lofs (0), rvl_lofs (1), rvl_lofs (2),  rvl_lofs (3),  rvl_lofs (4),  rvl_lofs (5),
                               rvl_lofs (6), rvl_lofs (7), rvl_lofs (8), rvl_lofs (9), rvl_lofs (10), rvl_lofs (11)};
 #define RVL_RING (rvl_lofs (12)) /* LDS ring doubles of a channel's lines 0..11 with their mirrors */
-#define RVL_MIN_BLOCKS 8 /* shorter launches take the streaming k_rv_core */
 #define RVL_THREADS (NL * (RVL_G + 1)) /* RVL_G worker waves + the planner wave */
 
 struct RvLds {
@@ -2172,9 +2171,12 @@ __device__ __forceinline__ void rvl_pair (const tbf_launch& P, const tbf_inst_co
 					const double old = sm.ring[RVL_LOFS[l] + RVL_C (l) + n + 1]; /* <= d + 64: mirror */
 #if RVL_FAST2
 					/* a0 - old 0.5 then (.) 0.5 + old: both products by 0.5 are exact unless an
-					 * operand is subnormal (< 2.2e-308; the input's denormal guard,
-					 * src/reverb.cpp:343-346, keeps the network's values above ~1e-25), so one fma
-					 * each gives the reference's values */
+					 * operand is subnormal (< 2.2e-308), so one fma each gives the reference's
+					 * values.  The input's denormal guard (src/reverb.cpp:343-346) keeps the input
+					 * above ~1e-25 only before `*= wet` (src/reverb.cpp:371): at a mix above 0 the
+					 * network's values stay far from subnormal for any rendered length; at mix 0 the
+					 * network's input is exactly 0 and its rings only decay, reaching FP64 subnormals
+					 * after minutes of rendered decay, far below what the float outputs resolve */
 					const double a = __builtin_fma (old, -0.5, a0);
 					apw[l - 8]     = a;
 					ap[l - 8]      = __builtin_fma (a, 0.5, old);

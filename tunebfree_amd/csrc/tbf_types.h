@@ -244,6 +244,9 @@ typedef struct tbf_rv_chan { /* one channel of the feedback network: k_rv_core w
 #ifndef TBF_STEADY_DEFAULT
 #define TBF_STEADY_DEFAULT 512
 #endif
+/* reverb network launches shorter than this take the streaming k_rv_core (tbf_launch_stage;
+ * tbf_debug_launches counts by the same rule) */
+#define RVL_MIN_BLOCKS 8
 /* each reverb line of the slab starts on a 128-B boundary (16 doubles): a wave's 64
  * consecutive doubles then cover exactly four whole cache lines */
 #define TBF_RING_ALIGN 16

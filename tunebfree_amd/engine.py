@@ -68,6 +68,9 @@ SIGNATURES = {
 EV_NOTE, EV_PARAM, EV_CONTROL, EV_PROGRAM = 0, 1, 2, 3
 EVENT_DTYPE = np.dtype([("block", "<u4"), ("inst", "<u4"), ("kind", "<i4"), ("id", "<i4"), ("value", "<f8")])
 
+# tbf_debug_launches index order (include/tbf.h TBF_LAUNCH_*)
+LAUNCH_KINDS = ("k_tonegen", "k_tonegen_ranges", "k_rv_core", "k_rv_core_lds", "k_whirl", "k_whirl_split")
+
 _lib = None
 
 
@@ -143,6 +146,16 @@ class Engine:
         d, h = C.c_uint64(), C.c_uint64()
         _check(f(self._h, C.byref(d), C.byref(h)))
         return d.value, h.value
+
+    def launches(self):
+        """tbf_debug_launches: launches of each kernel variant since the engine was created,
+        keyed by LAUNCH_KINDS ("k_tonegen": one block range per instance, "k_tonegen_ranges":
+        several); a host engine reports zeros."""
+        f = self._lib.tbf_debug_launches
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]
+        cnt = np.zeros(len(LAUNCH_KINDS), np.uint64)
+        assert _check(f(self._h, cnt.ctypes.data, len(cnt))) == len(LAUNCH_KINDS)
+        return {k: int(c) for k, c in zip(LAUNCH_KINDS, cnt)}
 
     def set_steady_chunk(self, blocks):
         """tbf_set_steady_chunk: the longest chunk without control deltas (64..2048 blocks),
