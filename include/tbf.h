@@ -275,6 +275,9 @@ enum {
 	TBF_LAUNCH_KINDS          = 6
 };
 int tbf_debug_launches (const tbf_engine* e, uint64_t* counts, uint32_t cap);
+/* test hook: k_rv_pre launches since the engine was created that ran ahead, on the k_whirl
+ * stream beside the previous chunk's k_rv_post (TBF_PRE_AHEAD=1; 0 otherwise) */
+int tbf_debug_pre_ahead (const tbf_engine* e, uint64_t* launches);
 /* the longest render chunk without control deltas, in blocks (64 .. 2048, default 512).
  * The stage buffers hold one chunk per instance (56 B per instance and sample at the
  * default stage groups: 15 GB at 4096 instances and 512 blocks, 60 GB at 2048) and

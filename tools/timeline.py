@@ -11,7 +11,7 @@ import json
 from collections import defaultdict
 
 SHORT = {"k_tonegen": "tg", "k_mixpre": "mp", "k_rv_pre": "pre", "k_rv_core_lds": "core", "k_rv_core": "core",
-         "k_rv_post": "post", "k_whirl": "wh", "k_tgctl": "ctl", "k_front": "front"}
+         "k_rv_post": "post", "k_whirl": "wh", "k_tgctl": "ctl", "k_front": "front", "k_rv_pre_ahead": "preA"}
 
 
 def main():
@@ -26,6 +26,8 @@ def main():
         name = r["Kernel_Name"].split("(")[0].replace("void ", "").split("<")[0]
         if name not in SHORT:
             continue
+        if name == "k_rv_pre" and int(r.get("Workgroup_Size_X") or 1024) <= 512:
+            name = "k_rv_pre_ahead"  # the launch shape that runs beside k_rv_post (its own grid)
         grid = int(r["Grid_Size_X"]) * int(r["Grid_Size_Y"]) * int(r["Grid_Size_Z"])
         ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), name, grid))
         gmax[name] = max(gmax[name], grid)

@@ -473,6 +473,8 @@ int tbf_engine_create (const tbf_engine_config* cfg, tbf_engine** out)
 		HIPCHK (hipEventCreateWithFlags (&e->upEvB, hipEventDisableTiming));
 		const char* pl = getenv ("TBF_PIPELINE");
 		e->pipeline    = !(pl && pl[0] == '0');
+		if (const char* pa = getenv ("TBF_PRE_AHEAD")) /* 0 / 1: the next chunk's k_rv_pre beside k_rv_post (A/B) */
+			e->preAhead = pa[0] == '1';
 		/* TBF_HOST_CONTROL=1: the per-wheel tone-generator control on the host (the
 		 * reference path for A/B); default: on the device (k_tgctl) */
 		const char* hc = getenv ("TBF_HOST_CONTROL");
@@ -1065,9 +1067,14 @@ int tbf_config_parse (tbf_engine* e, const char* text)
 } /* extern "C" */
 
 /* ------------------------------------------------------------------ device setup */
+/* launch the k_whirl that renderImpl holds back (tbf_engine.defPending), if any */
+static int issueDeferred (tbf_engine* e);
+
 /* wait for all pipelined stage work (before the host touches device buffers) */
 static int drainStages (tbf_engine* e)
 {
+	if (int rc = issueDeferred (e))
+		return rc;
 	if (!e->stagesBusy)
 		return 0;
 	for (hipStream_t q : e->gs)
@@ -1080,6 +1087,8 @@ static int drainStages (tbf_engine* e)
 /* make stream s wait for every pipelined stage launch so far */
 static int joinStages (tbf_engine* e, hipStream_t s)
 {
+	if (int rc = issueDeferred (e))
+		return rc;
 	if (!e->stagesBusy)
 		return 0;
 	for (hipStream_t q : e->gs) {
@@ -2125,8 +2134,67 @@ static int launchStage (tbf_engine* e, const tbf_launch& P, int k, hipStream_t s
 	return rc;
 }
 
+/* one pipelined stage launch on its stream: the optional timing events around it, then the
+ * events that later stages and chunks wait for */
+static int issueStage (tbf_engine* e, const tbf_launch& P, int k, hipStream_t sk, uint64_t cix)
+{
+	hipEvent_t e0 = nullptr, e1 = nullptr;
+	if (e->timeOn) {
+		HIPCHK (hipEventCreate (&e0));
+		HIPCHK (hipEventCreate (&e1));
+		HIPCHK (hipEventRecord (e0, sk));
+	}
+	const int rc = launchStage (e, P, k, sk);
+	if (rc)
+		return fail (rc, std::string ("kernel launch failed: ") + hipGetErrorString (hipGetLastError ()));
+	if (e->timeOn) {
+		HIPCHK (hipEventRecord (e1, sk));
+		e->tev.push_back ({k, {e0, e1}});
+	}
+	HIPCHK (hipEventRecord (e->sdone[k], sk));
+	HIPCHK (hipEventRecord (e->pev[cix & 3][k], sk));
+	return 0;
+}
+
+/* The held-back k_whirl (k_rv_pre ahead): behind its chunk's k_rv_post, whose event sdone[4]
+ * still holds (the next chunk has issued no stage past 2), and behind the caller's stream
+ * when it is the call's first output stage.  Nothing has waited for its events yet: every
+ * such wait (the stage streams' joins, the buffer-parity waits of the chunk after next, the
+ * end of the call) issues it first. */
+static int issueDeferred (tbf_engine* e)
+{
+	if (!e->defPending)
+		return 0;
+	e->defPending  = false;
+	hipStream_t sk = e->gs[e->grp[TBF_NSTAGES - 1]];
+	if (!e->outWait) {
+		HIPCHK (hipEventRecord (e->sjoin, e->callS));
+		HIPCHK (hipStreamWaitEvent (sk, e->sjoin, 0));
+		e->outWait = true;
+	}
+	HIPCHK (hipStreamWaitEvent (sk, e->sdone[TBF_NSTAGES - 2], 0));
+	return issueStage (e, e->defP, TBF_NSTAGES - 1, sk, e->defCix);
+}
+
+static int renderBody (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, uint64_t stride, hipStream_t s,
+                       const tbf_event* ev, uint32_t nev);
+
+/* renderBody, and on every way out of it the held-back k_whirl: it never outlives the call */
 static int renderImpl (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, uint64_t stride, hipStream_t s,
                        const tbf_event* ev = nullptr, uint32_t nev = 0)
+{
+	e->callS   = s;
+	e->outWait = false;
+	const int rc = renderBody (e, nblocks, dL, dR, stride, s, ev, nev);
+	if (e->defPending) { /* an error return between two chunks */
+		(void)issueDeferred (e);
+		(void)hipStreamWaitEvent (s, e->sdone[TBF_NSTAGES - 1], 0);
+	}
+	return rc;
+}
+
+static int renderBody (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, uint64_t stride, hipStream_t s,
+                       const tbf_event* ev, uint32_t nev)
 {
 	int rc = ensureDevice (e);
 	if (rc)
@@ -2211,7 +2279,9 @@ static int renderImpl (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, ui
 	 * bracketed by events on its own stream (durations then include the overlap with the
 	 * other streams' kernels). */
 	const bool   pipe  = e->pipeline && e->cfg.chain_mode == TBF_CHAIN_FULL && !e->timeSerial;
-	bool         outWait = false; /* the output stage has waited for the caller's stream */
+	/* k_rv_pre ahead (tbf_engine.preAhead): with the default stage groups only */
+	static const int defGrp[TBF_NSTAGES] = {0, 0, 1, 1, 1, 2};
+	const bool       aheadOn = e->preAhead && pipe && std::equal (defGrp, defGrp + TBF_NSTAGES, e->grp);
 	const size_t dprogCap = DPROG_CAP (n);
 	e->chg.assign (n, 0);
 	/* after a chunk with control deltas: the instances' final entries become their current
@@ -2629,6 +2699,15 @@ static int renderImpl (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, ui
 		if (usWaited && piped) /* the stage streams now follow the uploads on us */
 			e->stagesBusy = true;
 		const int nst = tbf_chain_stages (P.chain);
+		/* k_rv_pre ahead: this chunk's k_rv_pre goes in front of the held-back k_whirl of the
+		 * chunk before when neither chunk has control deltas or uploads and this one takes
+		 * k_rv_core_lds (a shorter chunk's k_rv_pre is too small to matter); its own k_whirl
+		 * is held back when a chunk follows in this call.  Anything else runs as before, behind
+		 * the held-back launch. */
+		const bool plain = aheadOn && piped && !delta && !usWaited && nst == TBF_NSTAGES;
+		const bool ahead = plain && e->defPending && P.rvLds && len >= RVL_MIN_BLOCKS;
+		if (!ahead && (rc = issueDeferred (e)))
+			return rc;
 		if (piped) {
 			/* stage-group streams: every chunk's stage k on stream gs[grp[k]], so a stage runs
 			 * as soon as this chunk's previous stage and the previous chunk's same stage are
@@ -2637,39 +2716,45 @@ static int renderImpl (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, ui
 			 * output mid0 is read by k_mixpre, mid1 by k_rv_pre and k_rv_post, rvA by
 			 * k_rv_core, rvB by k_rv_post, mid2 by k_whirl) when they run on another stream. */
 			static const int readers[TBF_NSTAGES][2] = {{1, -1}, {2, 4}, {3, -1}, {4, -1}, {5, -1}, {-1, -1}};
-			auto strm = [&] (int k) { return e->gs[e->grp[k]]; };
+			auto strm = [&] (int k) { return e->gs[e->grp[k == 2 && ahead ? TBF_NSTAGES - 1 : k]]; };
 			for (int k = 0; k < nst; k++) {
 				hipStream_t sk = strm (k);
+				if (k == nst - 1 && plain && b0 + len < nblocks) { /* held back for the next chunk's k_rv_pre */
+					e->defP       = P;
+					e->defCix     = cix;
+					e->defPending = true;
+					break;
+				}
 				if (k == 0 && !e->stagesBusy) { /* after the caller's stream (uploads, earlier chunks) */
 					HIPCHK (hipEventRecord (e->sjoin, s));
 					HIPCHK (hipStreamWaitEvent (sk, e->sjoin, 0));
 				}
-				if (k == nst - 1 && !outWait) { /* the output stage writes the caller's buffers */
+				if (k == nst - 1 && !e->outWait) { /* the output stage writes the caller's buffers */
 					HIPCHK (hipEventRecord (e->sjoin, s));
 					HIPCHK (hipStreamWaitEvent (sk, e->sjoin, 0));
-					outWait = true;
+					e->outWait = true;
 				}
 				if (k > 0 && strm (k - 1) != sk)
 					HIPCHK (hipStreamWaitEvent (sk, e->sdone[k - 1], 0));
-				for (int r : readers[k])
-					if (r >= 0 && r < nst && strm (r) != sk)
-						HIPCHK (hipStreamWaitEvent (sk, e->pev[(cix + 2) & 3][r], 0));
-				hipEvent_t e0 = nullptr, e1 = nullptr;
-				if (e->timeOn) {
-					HIPCHK (hipEventCreate (&e0));
-					HIPCHK (hipEventCreate (&e1));
-					HIPCHK (hipEventRecord (e0, sk));
+				if (k == 2 && ahead) {
+					/* behind k_rv_core of the chunk before (sdone[3] is still its event): that
+					 * puts the launch in the k_rv_post phase, orders it behind that chunk's
+					 * k_rv_pre (the stage's state) and keeps rvA a single buffer */
+					HIPCHK (hipStreamWaitEvent (sk, e->sdone[3], 0));
+				} else
+					for (int r : readers[k])
+						if (r >= 0 && r < nst && strm (r) != sk)
+							HIPCHK (hipStreamWaitEvent (sk, e->pev[(cix + 2) & 3][r], 0));
+				P.preAhead = k == 2 && ahead;
+				if ((rc = issueStage (e, P, k, sk, cix)))
+					return rc;
+				if (k == 2 && ahead) {
+					e->aheadCount++;
+					if ((rc = issueDeferred (e))) /* k_whirl of the chunk before, behind it */
+						return rc;
 				}
-				rc = launchStage (e, P, k, sk);
-				if (rc)
-					return fail (rc, std::string ("kernel launch failed: ") + hipGetErrorString (hipGetLastError ()));
-				if (e->timeOn) {
-					HIPCHK (hipEventRecord (e1, sk));
-					e->tev.push_back ({k, {e0, e1}});
-				}
-				HIPCHK (hipEventRecord (e->sdone[k], sk));
-				HIPCHK (hipEventRecord (e->pev[cix & 3][k], sk));
 			}
+			P.preAhead = 0;
 			e->stagesBusy = true;
 			if (delta && (rc = endDelta ()))
 				return rc;
@@ -2700,6 +2785,8 @@ static int renderImpl (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, ui
 		if (rc)
 			return rc;
 	}
+	if ((rc = issueDeferred (e)))
+		return rc;
 	if (e->stagesBusy) {
 		/* the caller's stream waits for the last chunk's output stage (which follows
 		 * every earlier stage launch); later chunks keep overlapping from the streams */
@@ -2957,10 +3044,20 @@ int tbf_debug_launches (const tbf_engine* e, uint64_t* counts, uint32_t cap)
 	return TBF_LAUNCH_KINDS;
 }
 
+int tbf_debug_pre_ahead (const tbf_engine* e, uint64_t* launches)
+{
+	if (!e || !launches)
+		return fail (-22, "null argument");
+	*launches = e->aheadCount;
+	return 0;
+}
+
 int tbf_set_steady_chunk (tbf_engine* e, uint32_t blocks)
 {
 	if (!e)
 		return fail (-22, "null argument");
+	if (int rc = issueDeferred (e)) /* (renderImpl leaves none; before the buffers can change) */
+		return rc;
 	e->steadyChunk = std::min (std::max (blocks, (uint32_t)TBF_CHUNK), (uint32_t)TBF_STEADY_MAX);
 	/* clamped here to what the device can hold for the current instances (the stage
 	 * buffers' footprint against the free memory plus the buffers held now), so the value

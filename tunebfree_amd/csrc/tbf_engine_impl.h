@@ -360,6 +360,20 @@ struct tbf_engine {
 	 * mid2 by parity, 56 instead of 68 B per stereo sample, and the step 131.7 -> 128.3 ms
 	 * (profiles/r05/s20_groups) */
 	int                                     grp[TBF_NSTAGES] = {0, 0, 1, 1, 1, 2};
+	/* k_rv_pre ahead (TBF_PRE_AHEAD=1; default groups, full chain): chunk c + 1's k_rv_pre runs on
+	 * the k_whirl stream in front of k_whirl (c), behind k_mixpre (c + 1) and k_rv_core (c), so it
+	 * shares the CUs with k_rv_post (c) and not with k_whirl (c).  Chunks are issued
+	 * chunk-major, so k_whirl (c)'s launch is held back (def*) until chunk c + 1 has issued its
+	 * stage 2, or until anything else needs the streams complete (issueDeferred: joinStages,
+	 * drainStages, the end of the call).  It never outlives renderImpl.  Measured slower than
+	 * the default order, so off unless switched on. */
+	bool                                    preAhead   = false;
+	bool                                    defPending = false;   /* k_whirl of chunk defCix is held back */
+	tbf_launch                              defP;                 /* its launch */
+	uint64_t                                defCix     = 0;
+	hipStream_t                             callS      = nullptr; /* the caller's stream of the current renderImpl ... */
+	bool                                    outWait    = false;   /* ... which the output stage has waited for */
+	uint64_t                                aheadCount = 0;       /* k_rv_pre launches that ran ahead (tbf_debug_pre_ahead) */
 	bool                                    rvLdsOn  = true;  /* k_rv_core_lds when the rings fit (TBF_RV_LDS=0: k_rv_core) */
 	bool                                    rvLdsFit = false; /* the instances' rings fit k_rv_core_lds */
 	uint32_t                                rvGrid   = 0;     /* k_rv_core_lds persistent workgroups (TBF_RV_PERSIST=0: one per pair) */

@@ -1845,20 +1845,22 @@ __device__ __forceinline__ int rvl_slot_l (int l, const int (&cs)[12], int n)
 }
 
 /* rvl_write at slot rvl_slot<D> (c, n): the mirror (slots below RVL_MIR) is possible only when
- * c < RVL_MIR or the sub-block wraps, again a scalar test */
+ * c < RVL_MIR or the sub-block wraps, again a scalar test.  The rare block only adjusts the
+ * slot and writes the mirror, and the one ring write follows the join: the common case is a
+ * scalar compare, a branch not taken and the write.  With a ring write on either side of
+ * the test, the rare block lay inline behind the common write, which then took a second
+ * branch over it: 12 taken branches a worker and group. */
 template <int D>
 __device__ __forceinline__ void rvl_write_s (double* rg, int c, int n, double v)
 {
-	if (!RVL_RARE (c < RVL_MIR || c > D - (NL - 1))) { /* the common case: no wrap, no mirror */
-		rg[c + n] = v;
-	} else {
-		int i = c + n;
+	int i = c + n;
+	if (RVL_RARE (c < RVL_MIR || c > D - (NL - 1))) {
 		__asm__ __volatile__ ("" : "+v"(i)); /* a branch, not selects (rvl_slot) */
 		i -= (i > D) ? D + 1 : 0;
-		rg[i] = v;
 		if (i < RVL_MIR)
 			rg[i + D + 1] = v;
 	}
+	rg[i] = v;
 }
 
 /* lane n receives lane n-1's v, lane 0 receives first (FP64 lane_shr1_or: the DPP moves keep
@@ -2338,9 +2340,28 @@ k_rv_core_lds (const tbf_launch P, const tbf_inst_const* __restrict__ cst)
 #define RVC_TASKS RVC_CB          /* helper tasks per tile: one instance each */
 #define RVC_NTK (RVC_TASKS / RVC_H)
 static_assert (RVC_TASKS % RVC_H == 0, "helper tasks split evenly");
-#define RVC_THREADS (NL * (2 + RVC_H))
+#define RVC_THREADS_OF(h) (NL * (2 + (h)))
+#define RVC_THREADS RVC_THREADS_OF (RVC_H)
 static_assert (RVC_NC <= NL && RVC_T * 2 == NL && TBF_BLK % RVC_T == 0, "chain-block geometry");
-#define RVC_ROWS (RVC_NC + (RVC_NC < NL)) /* chain rows, + one that the serial and dither waves' idle lanes use */
+#define RVC_ROWS_OF(cb) (2 * (cb) + (2 * (cb) < NL)) /* chain rows, + one that the serial and dither waves' idle lanes use */
+#define RVC_ROWS RVC_ROWS_OF (RVC_CB)
+/* The shape of a k_rv_pre launch that runs ahead, beside the previous chunk's k_rv_post
+ * (tbf_launch.preAhead): a k_rv_post workgroup sits on every CU with 11 waves at 112 VGPRs
+ * and RvPostLds, which leaves 2 + 2 + 2 + 3 wave slots at 80 VGPRs and 50,584 B of
+ * LDS, so at most 8 waves (serial, dither, 6 helpers) and a chain block that fits (the
+ * static_assert behind RvPostLds).  Measured slower than k_rv_pre in its own phase
+ * (DESIGN.md section 4.7), so only TBF_PRE_AHEAD=1 launches it. */
+#ifndef RVA_CB
+#define RVA_CB 24
+#endif
+#ifndef RVA_H
+#define RVA_H 6
+#endif
+static_assert (RVA_CB % RVA_H == 0 && 2 * RVA_CB <= NL && 2 + RVA_H <= 8, "k_rv_pre ahead shape");
+#ifndef RVA_WPE
+#define RVA_WPE 6 /* the ahead shape's register budget as waves per SIMD: 512 / 6 -> 80 VGPRs */
+#endif
+#define RVC_WPE_OF(cb, h) ((cb) == RVC_CB && (h) == RVC_H ? 1 : RVA_WPE)
 
 /* one transposed-DF2 biquad step (biquadA/B/C, src/reverb.cpp:361-369, 733-741, 756-764) */
 __device__ __forceinline__ double rvc_bq (double x, double c0, double c1, double c2, double c3, double c4, double& s7,
@@ -2444,9 +2465,10 @@ __device__ __forceinline__ void rvc_serial_p (double* r0, const double* r1, cons
 	PRIO_DOWN ();
 }
 
+template <int ROWS>
 struct RvPreLds {
-	double   x[2][RVC_ROWS][RVC_S]; /* predelayed input -> biquadA output, in place */
-	uint32_t f[2][RVC_ROWS][RVC_S]; /* fpdL / fpdR of the sample delayM back (the predelay's input guard) */
+	double   x[2][ROWS][RVC_S]; /* predelayed input -> biquadA output, in place */
+	uint32_t f[2][ROWS][RVC_S]; /* fpdL / fpdR of the sample delayM back (the predelay's input guard) */
 };
 
 /* predelay, denormal guard, biquadA, sin (x * wet) (src/reverb.cpp:339-375) -> rvA.
@@ -2458,21 +2480,24 @@ struct RvPreLds {
  * stored at k + 2.  Each role runs its own loop with the same barriers.  The HBM reads
  * are unconditional (indices clamped): a read under a branch joins its register with the
  * old value, and that copy waits for the read right away. */
-__global__ void __launch_bounds__ (RVC_THREADS)
+template <int CB, int H>
+__global__ void __launch_bounds__ (RVC_THREADS_OF (H), RVC_WPE_OF (CB, H))
 k_rv_pre (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf_seg_ctl* __restrict__ ctl)
 {
-	__shared__ RvPreLds sm;
+	constexpr int NC = 2 * CB, NTK = CB / H, ROWS = RVC_ROWS_OF (CB);
+	static_assert (CB % H == 0 && NC <= NL, "chain-block geometry");
+	__shared__ RvPreLds<ROWS> sm;
 	const int      w = __builtin_amdgcn_readfirstlane (threadIdx.x >> 6), lane = threadIdx.x & (NL - 1);
-	const uint32_t inst0 = P.instBase + blockIdx.x * RVC_CB;
+	const uint32_t inst0 = P.instBase + blockIdx.x * CB;
 	if (inst0 >= P.nInst)
 		return;
-	const int nj  = (int)min ((uint32_t)RVC_CB, P.nInst - inst0);
+	const int nj  = (int)min ((uint32_t)CB, P.nInst - inst0);
 	const int nT  = (int)P.nBlocks * (TBF_BLK / RVC_T);
 	const int nIt = nT + 2;
 	/* waves 0, 1: lane = chain 2 j + c */
 	const int     cj = lane >> 1, cc = lane & 1;
 	const bool    cok = cj < nj;
-	const int     crow = lane < RVC_NC ? lane : RVC_NC; /* chain lanes past the block's chains: the idle row */
+	const int     crow = lane < NC ? lane : NC; /* chain lanes past the block's chains: the idle row */
 	tbf_rv_state* CS  = &P.st[inst0 + (cok ? cj : 0)].rv;
 	if (w == 0) {
 		const double* cf   = cst[inst0 + (cok ? cj : 0)].bq[0];
@@ -2525,25 +2550,32 @@ k_rv_pre (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf_
 		}
 		return;
 	}
-	/* helpers: task t = instance h + RVC_H t (wave-uniform); lane = channel hc, sample n.
+	/* helpers: task t = instance h + H t (wave-uniform); lane = channel hc, sample n.
 	 * HBM reads run two tiles ahead, into two register sets that alternate by iteration
 	 * parity (the loop is unrolled by two, so the sets stay static) */
 	const int    h = w - 2, hc = lane >> 5, n = lane & (RVC_T - 1);
-	float        pIn[2][RVC_NTK];
-	double       wetv[RVC_NTK];
-	int          dM[RVC_NTK], age[RVC_NTK];
-	uint32_t     pos[RVC_NTK];
-	const float* in[RVC_NTK];
-	float*       hst[RVC_NTK]; /* the predelay history */
-	double*      ra[RVC_NTK];
+	float        pIn[2][NTK];
+	double       wetv[NTK];
+	int          dM[NTK], age[NTK];
+	uint32_t     pos[NTK];
+	const float* in[NTK];
+	float*       hst[NTK]; /* the predelay history */
+	double*      ra[NTK];
+	/* more than one pair a wave (the ahead shape, whose launches have no control deltas: one
+	 * wet level for all blocks): the wet level and the output row as wave-uniform values
+	 * and one lane offset, which keeps the pairs' per-lane state inside the register budget */
+	constexpr bool UNI = NTK > 2;
+	double         wetS[NTK];
+	double*        raS[NTK];
+	const size_t   raOff = (size_t)hc * P.midStride + n;
 	/* the input delayM samples before sample k of the chunk (lane n: k = 32 tile + n) */
 	auto src = [&] (int t, int tile) {
 		const int p = tile * RVC_T + n - dM[t];
 		return p >= 0 ? in[t] + p : hst[t] + ((pos[t] + (uint32_t)p) & (TBF_PD_HIST - 1));
 	};
 #pragma unroll
-	for (int t = 0; t < RVC_NTK; t++) {
-		const int             j    = h + t * RVC_H;
+	for (int t = 0; t < NTK; t++) {
+		const int             j    = h + t * H;
 		const uint32_t        inst = inst0 + (j < nj ? j : nj - 1);
 		const tbf_inst_const& K    = cst[inst];
 		const tbf_rv_state&   S    = P.st[inst].rv;
@@ -2554,55 +2586,64 @@ k_rv_pre (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf_
 		age[t]  = min (max (S.pdAge, 0), dM[t]);
 		pos[t]  = S.pdPos;
 		wetv[t] = rvc_wet_lanes (P, ctl, inst);
+		wetS[t] = rld (wetv[t], 0);
+		raS[t]  = rv_buf (P.rvA, P, inst, 0);
 		pIn[0][t] = *src (t, 0);
 		pIn[1][t] = *src (t, min (1, nT - 1));
 	}
 	__syncthreads ();
-	auto step = [&] (const int it, float (&qIn)[RVC_NTK]) {
+	/* The tasks go two at a time (TP: the pair whose sines interleave in tbf_sin2), each pair
+	 * through the whole step before the next, so that only one pair's values are live: what
+	 * the ahead shape's four tasks a wave need to stay inside its register budget.  The
+	 * tasks touch disjoint rows, so their order within an iteration is free. */
+	constexpr int TP = 2;
+	auto step = [&] (const int it, float (&qIn)[NTK]) {
 		const int b = it & 1; /* tiles it and it - 2 share the buffer */
-		double    sv[RVC_NTK];
-		/* the filtered tile it - 2, read before tile it overwrites it */
 #pragma unroll
-		for (int t = 0; t < RVC_NTK; t++)
-			sv[t] = sm.x[b][2 * (h + t * RVC_H) + hc][n];
-		/* tile it: the predelayed samples (src/reverb.cpp:339-358): the input delayM back,
-		 * guarded with its dither state, or the zeroed ring's 0 before the instance's
-		 * first delayM samples */
-		if (it < nT) {
+		for (int t0 = 0; t0 < NTK; t0 += TP) {
+			double sv[TP];
+			/* the filtered tile it - 2, read before tile it overwrites it */
 #pragma unroll
-			for (int t = 0; t < RVC_NTK; t++) {
-				const int r = 2 * (h + t * RVC_H) + hc;
-				double    x = (double)qIn[t];
-				if (fabs (x) < 1.18e-23)
-					x = sm.f[b][r][n] * 1.18e-17;
-				const double xv = age[t] + it * RVC_T + n >= dM[t] ? x : 0.0;
-				sm.x[b][r][n] = xv;
+			for (int t = t0; t < t0 + TP && t < NTK; t++)
+				sv[t - t0] = sm.x[b][2 * (h + t * H) + hc][n];
+			/* tile it: the predelayed samples (src/reverb.cpp:339-358): the input delayM back,
+			 * guarded with its dither state, or the zeroed ring's 0 before the instance's
+			 * first delayM samples */
+			if (it < nT) {
+#pragma unroll
+				for (int t = t0; t < t0 + TP && t < NTK; t++) {
+					const int r = 2 * (h + t * H) + hc;
+					double    x = (double)qIn[t];
+					if (fabs (x) < 1.18e-23)
+						x = sm.f[b][r][n] * 1.18e-17;
+					const double xv = age[t] + it * RVC_T + n >= dM[t] ? x : 0.0;
+					sm.x[b][r][n] = xv;
+				}
 			}
-		}
-		/* HBM reads of tile it + 2 into the set just consumed (clamped past the last tile:
-		 * a harmless re-read, so the loads need no branch) */
-		const int tl = min (it + 2, nT - 1);
+			/* HBM reads of tile it + 2 into the set just consumed (clamped past the last tile:
+			 * a harmless re-read, so the loads need no branch) */
+			const int tl = min (it + 2, nT - 1);
 #pragma unroll
-		for (int t = 0; t < RVC_NTK; t++)
-			qIn[t] = *src (t, tl);
-		/* sin (x * wet) of tile it - 2 */
-		if (it >= 2) {
-			const int k2 = it - 2;
-			double    sx[RVC_NTK];
+			for (int t = t0; t < t0 + TP && t < NTK; t++)
+				qIn[t] = *src (t, tl);
+			/* sin (x * wet) of tile it - 2 */
+			if (it >= 2) {
+				const int k2 = it - 2;
+				double    sx[TP];
 #pragma unroll
-			for (int t = 0; t < RVC_NTK; t++)
-				sx[t] = sv[t] * rld (wetv[t], blk_lane ((k2 * RVC_T) / TBF_BLK));
-			/* the tasks' sines in pairs (tbf_sin2: their chains interleave) */
+				for (int t = t0; t < t0 + TP && t < NTK; t++)
+					sx[t - t0] = sv[t - t0] * (UNI ? wetS[t] : rld (wetv[t], blk_lane ((k2 * RVC_T) / TBF_BLK)));
+				if (t0 + 1 < NTK) /* the pair's sines together (tbf_sin2: their chains interleave) */
+					tbf_sin2 (sx[0], sx[1], sx[0], sx[1]);
+				else
+					sx[0] = tbf_sin (sx[0]);
 #pragma unroll
-			for (int t = 0; t + 1 < RVC_NTK; t += 2) {
-				tbf_sin2 (sx[t], sx[t + 1], sx[t], sx[t + 1]);
+				for (int t = t0; t < t0 + TP && t < NTK; t++)
+					if (h + t * H < nj)
+						(UNI ? raS[t] + raOff : ra[t])[(size_t)k2 * RVC_T] = sx[t - t0];
 			}
-			if (RVC_NTK & 1)
-				sx[RVC_NTK - 1] = tbf_sin (sx[RVC_NTK - 1]);
-#pragma unroll
-			for (int t = 0; t < RVC_NTK; t++)
-				if (h + t * RVC_H < nj)
-					ra[t][(size_t)k2 * RVC_T] = sx[t];
+			if (NTK > TP)
+				__builtin_amdgcn_sched_barrier (0);
 		}
 		__syncthreads ();
 	};
@@ -2616,8 +2657,8 @@ k_rv_pre (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf_
 	 * wave's program order), the position and the age */
 	const int nS = nT * RVC_T;
 #pragma unroll
-	for (int t = 0; t < RVC_NTK; t++) {
-		const int j = h + t * RVC_H;
+	for (int t = 0; t < NTK; t++) {
+		const int j = h + t * H;
 		if (j >= nj)
 			continue;
 		for (int m = max (0, nS - TBF_PD_HIST) + lane; m < nS; m += NL)
@@ -2671,6 +2712,8 @@ struct RvPostLds {
 	double   z1[2][RVP_ROWS][RVC_S], z2[2][RVP_ROWS][RVC_S]; /* x c1, x c2 of the asin output */
 	uint32_t f[2][RVP_ROWS][RVC_S]; /* fpdL / fpdR before each sample (entry RVC_T: after the tile) */
 };
+/* a k_rv_pre workgroup of the ahead shape shares a CU (160 KB of LDS) with one of k_rv_post's */
+static_assert (sizeof (RvPreLds<RVC_ROWS_OF (RVA_CB)>) + sizeof (RvPostLds) <= 160 * 1024, "k_rv_pre ahead shape: LDS beside k_rv_post");
 
 /* biquadB, clamp + asin, biquadC, dry mix, dither, (L + R) / sqrt 2 (src/reverb.cpp:733-787)
  * -> mid2.  A tile is loaded at iteration k (its HBM reads issued at k - 2), biquadB at
@@ -4336,6 +4379,8 @@ extern "C" int tbf_launch_stage (const tbf_launch* P, int k, hipStream_t stream)
 		return -22;
 	if ((k == 2 || k == 4 || k == 5) && P->nBlocks > NL && P->ctlIdx) /* per-block controls one per lane (blk_lane) */
 		return -22;
+	if (k == 2 && P->preAhead && P->ctlIdx) /* the ahead shape reads one wet level for all blocks */
+		return -22;
 	const dim3 grid (P->nInst), block (NL);
 	const dim3 cgrid ((P->nInst + RVC_CB - 1) / RVC_CB), cblock (RVC_THREADS);
 	if (k == 0)
@@ -4347,8 +4392,13 @@ extern "C" int tbf_launch_stage (const tbf_launch* P, int k, hipStream_t stream)
 	}
 	else if (k == 1)
 		hipLaunchKernelGGL (k_mixpre, dim3 ((P->nInst + MP_CB - 1) / MP_CB), dim3 (MP_THREADS), 0, stream, *P, P->ctl);
-	else if (k == 2)
-		hipLaunchKernelGGL (k_rv_pre, cgrid, cblock, 0, stream, *P, P->cst, P->ctl);
+	else if (k == 2) {
+		if (P->preAhead)
+			hipLaunchKernelGGL ((k_rv_pre<RVA_CB, RVA_H>), dim3 ((P->nInst + RVA_CB - 1) / RVA_CB),
+			                    dim3 (RVC_THREADS_OF (RVA_H)), 0, stream, *P, P->cst, P->ctl);
+		else
+			hipLaunchKernelGGL ((k_rv_pre<RVC_CB, RVC_H>), cgrid, cblock, 0, stream, *P, P->cst, P->ctl);
+	}
 	else if (k == 3)
 		/* the LDS kernel loads and stores a channel's 129.7 KB of rings per launch; the
 		 * streaming kernel moves 24.6 KB per block: below 8 blocks the streaming one

@@ -333,6 +333,7 @@ typedef struct tbf_launch {
 	uint32_t              nCtlInst;
 	uint32_t              rvLds;     /* 1: the reverb core with its rings resident in LDS (k_rv_core_lds) */
 	uint32_t              rvGrid;    /* k_rv_core_lds workgroups (persistent; 0: one per pair) */
+	uint32_t              preAhead;  /* 1: k_rv_pre in the shape that fits beside a k_rv_post workgroup (host side only) */
 	uint32_t              tgSplit;   /* k_tonegen block ranges per instance (chunks without deltas; <= nBlocks) */
 	uint8_t*              mixFixed;  /* tonegen only: [inst] 1 when k_tonegen wrote the chunk's output (the
 	                                  * mixdown's gain chases at a fixed point), so k_mixpre skips it */

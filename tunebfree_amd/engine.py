@@ -157,6 +157,15 @@ class Engine:
         assert _check(f(self._h, cnt.ctypes.data, len(cnt))) == len(LAUNCH_KINDS)
         return {k: int(c) for k, c in zip(LAUNCH_KINDS, cnt)}
 
+    def pre_ahead(self):
+        """tbf_debug_pre_ahead: k_rv_pre launches that ran ahead, beside the previous chunk's
+        k_rv_post (TBF_PRE_AHEAD=1)."""
+        f = self._lib.tbf_debug_pre_ahead
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_void_p]
+        n = C.c_uint64()
+        _check(f(self._h, C.byref(n)))
+        return n.value
+
     def set_steady_chunk(self, blocks):
         """tbf_set_steady_chunk: the longest chunk without control deltas (64..2048 blocks),
         which bounds the stage buffers; returns the value in effect."""
