@@ -65,6 +65,12 @@
 #ifndef WH_SERIAL_PIPE
 #define WH_SERIAL_PIPE 1 /* k_whirl serial passes: next group's reads ahead of this group's chain */
 #endif
+#ifndef WH_SERIAL_REGS
+#define WH_SERIAL_REGS 1 /* k_whirl / k_whirl_split serial passes fed from registers, one chain per DPP row (wh_serial_regs) */
+#endif
+#ifndef WH_SERIAL_PK
+#define WH_SERIAL_PK 1 /* wh_serial_regs: a1 t, a2 t by one packed multiply, three VALU a step (0: four) */
+#endif
 #ifndef WH_PIN_READS
 #define WH_PIN_READS 1 /* motion_pass: the ring reads pinned ahead of the adds, one LDS round trip per pass */
 #endif
@@ -3226,6 +3232,167 @@ __device__ __forceinline__ void wh_serial_v (float* r, float* fz, float a1, floa
 	fz[1] = z1;
 }
 
+#if WH_SERIAL_REGS
+/* The serial pass fed from registers, one chain per DPP row: chain f runs in lane 16 f and
+ * lane 16 f + j holds samples j, 16 + j, 32 + j, 48 + j of the chain's row (wh_chain_load:
+ * four ds_read_b32 for all chains together, one LDS round trip).  Step k takes x[k] from
+ * lane 16 f + (k & 15) of register k / 16 through the DPP operand of its subtract
+ * (row_shl, full EXEC: a DPP source lane disabled by EXEC would read as invalid), so the
+ * recurrence holds no LDS instruction and no wait; the row's other lanes compute values
+ * nobody reads.  The lane a chain runs in: */
+#define WH_FZL(f) (16 * (f))
+
+/* lane i receives lane i + S of its row of 16 (0 past the row's end), S = 1..15 */
+template <int S>
+__device__ __forceinline__ float row_shl (float v)
+{
+	return __int_as_float (__builtin_amdgcn_mov_dpp (__float_as_int (v), 0x100 + S, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float row_shl (float v, int s)
+{
+	switch (s & 15) {
+#define WH_RS(S) case S: return row_shl<S> (v);
+	WH_RS (1) WH_RS (2) WH_RS (3) WH_RS (4) WH_RS (5) WH_RS (6) WH_RS (7) WH_RS (8)
+	WH_RS (9) WH_RS (10) WH_RS (11) WH_RS (12) WH_RS (13) WH_RS (14) WH_RS (15)
+#undef WH_RS
+	default: return v;
+	}
+}
+
+/* element i of a chain's row is row[(base + i) & m]; without WRAP the caller has added
+ * base to row */
+template <bool WRAP>
+__device__ __forceinline__ void wh_chain_load (const float* row, uint32_t base, uint32_t m, float (&x)[4])
+{
+	const uint32_t j = threadIdx.x & 15u;
+#pragma unroll
+	for (int i = 0; i < 4; i++)
+		x[i] = WRAP ? row[(base + (uint32_t)(16 * i) + j) & m] : row[(uint32_t)(16 * i) + j];
+}
+
+typedef float f4v __attribute__ ((ext_vector_type (4)));
+typedef __attribute__ ((address_space (3))) float lds_float;
+/* four temps to 16-B aligned row + off (bytes, constant), from the lanes of mask alone: EXEC
+ * is set around the one write with scalar moves, so no branch and no wait comes with it
+ * (the write is not in the compiler's lgkmcnt count; a wave's LDS instructions complete in
+ * issue order, so every count the compiler waits for still covers what it means to) */
+template <int OFF>
+__device__ __forceinline__ void wh_chain_st4 (uint64_t mask, float* row, f4v t)
+{
+	uint64_t       sv;
+	const uint32_t a = (uint32_t)(uintptr_t)(lds_float*)row;
+	asm volatile ("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %1\n\tds_write_b128 %2, %3 offset:%4\n\ts_mov_b64 exec, %0"
+	              : "=&s"(sv)
+	              : "s"(mask), "v"(a), "v"(t), "n"(OFF)
+	              : "memory");
+}
+
+/* {a.x b, a.y b} with b the low or (HI) the high half of the pair bp: one v_pk_mul_f32, two
+ * IEEE multiplies.  The half is an operand modifier, so temp[n-1] is multiplied from the
+ * register the group's write needs it in; the compiler picks the low half only and copies
+ * every second temp to an even register first (a fourth VALU instruction on the chain).
+ * The compiler still puts its two wait states between this write and the DPP subtract that
+ * reads it (s_nop 1 after the statement). */
+template <bool HI>
+__device__ __forceinline__ f2v wh_pk_mul (f2v a, f2v bp)
+{
+	f2v p;
+	if (HI)
+		asm ("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(p) : "v"(a), "v"(bp));
+	else
+		asm ("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(p) : "v"(a), "v"(bp));
+	return p;
+}
+
+/* wh_serial over the chains of mask (bit 16 f: chain f is active), x from wh_chain_load:
+ * the same multiplies and subtracts in the same order, temp[n] = (x[n] - a1 temp[n-1]) -
+ * a2 temp[n-2].  a2 temp[n-1] is formed beside a1 temp[n-1] by one packed multiply (two
+ * IEEE multiplies) and used one step later, so a step is three VALU instructions.  z0, z1,
+ * a1, a2, scrub: per lane, read in lanes 16 f.  An inactive chain neither stores nor
+ * advances its state. */
+template <bool WRAP>
+__device__ __forceinline__ void wh_serial_regs (float* row, uint32_t base, uint32_t m, const float (&x)[4], const uint64_t mask_,
+                                                float& z0, float& z1, float a1, float a2, bool scrub)
+{
+	float s0 = z0, s1 = z1;
+	if (scrub) {
+		s0 = isnan (s0) ? 0.f : s0;
+		s1 = isnan (s1) ? 0.f : s1;
+	}
+	/* wave-uniform by construction; the writes' EXEC moves take it from scalar registers */
+	const uint64_t mask = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane ((uint32_t)mask_) |
+	                      ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane ((uint32_t)(mask_ >> 32)) << 32);
+	const bool     act  = lane_in (mask);
+	/* the row's four registers are pinned here: the one wait for them comes before the
+	 * chain, not at the first step that uses the third */
+	float xv[4] = {x[0], x[1], x[2], x[3]};
+	asm volatile ("" : "+v"(xv[0]), "+v"(xv[1]), "+v"(xv[2]), "+v"(xv[3]));
+	PRIO_UP ();
+#if WH_SERIAL_PK
+	const f2v A = {a1, a2};
+	float     q = a2 * s1; /* a2 temp[n-2] */
+#endif
+	/* the group's four temps in the registers its write takes them from; temp[n-1] is read
+	 * where it lies, as the low or the high half of a register pair (wh_pk_mul) */
+	f4v T;
+	T.w = s0;
+#pragma unroll
+	for (int g = 0; g < TBF_SUB / 4; g++) {
+		f4v N;
+#pragma unroll
+		for (int k = 0; k < 4; k++) {
+			const float xk = row_shl (xv[g >> 2], 4 * g + k);
+#if WH_SERIAL_PK
+			const f2v p = k == 0 ? wh_pk_mul<true> (A, T.zw) : (k == 1 ? wh_pk_mul<false> (A, N.xy) : (k == 2 ? wh_pk_mul<true> (A, N.xy) : wh_pk_mul<false> (A, N.zw)));
+			N[k]        = (xk - p.x) - q;
+			q           = p.y;
+#else
+			N[k] = xk - (a1 * s0) - (a2 * s1);
+#endif
+			s1 = s0;
+			s0 = N[k];
+		}
+		if (WRAP) {
+			if (act) {
+#pragma unroll
+				for (int k = 0; k < 4; k++)
+					row[(base + (uint32_t)(4 * g + k)) & m] = N[k];
+			}
+		} else {
+			switch (g) { /* the write's offset is an instruction field */
+#define WH_ST(G) case G: wh_chain_st4<16 * G> (mask, row, N); break;
+			WH_ST (0) WH_ST (1) WH_ST (2) WH_ST (3) WH_ST (4) WH_ST (5) WH_ST (6) WH_ST (7)
+			WH_ST (8) WH_ST (9) WH_ST (10) WH_ST (11) WH_ST (12) WH_ST (13) WH_ST (14) WH_ST (15)
+#undef WH_ST
+			}
+		}
+		T = N;
+	}
+	PRIO_DOWN ();
+	static_assert (TBF_SUB == 64, "four registers of 16 samples, 16 writes of 4");
+	z0 = act ? s0 : z0;
+	z1 = act ? s1 : z1;
+}
+/* the same with the states in memory, chain f's at fz[f], and the rows loaded here */
+template <bool WRAP>
+__device__ __forceinline__ void whs_serial_regs (float* row, uint32_t base, uint32_t m, const uint64_t mask, float (*fz)[2], float a1,
+                                                 float a2, bool scrub)
+{
+	const bool act = lane_in (mask);
+	const int  f   = act ? (int)(threadIdx.x & (NL - 1)) >> 4 : 0;
+	float      x[4];
+	wh_chain_load<WRAP> (row, base, m, x);
+	float z0 = fz[f][0], z1 = fz[f][1];
+	wh_serial_regs<WRAP> (row, base, m, x, mask, z0, z1, a1, a2, scrub);
+	if (act) {
+		fz[f][0] = z0;
+		fz[f][1] = z1;
+	}
+}
+#else
+#define WH_FZL(f) (f)
+#endif
+
 /* the filter outputs, lane n = sample n: t = temp[n], z0 / z1 = the state the pass started
  * from (temp[-1], temp[-2]); the neighbours' temps by DPP lane shifts */
 __device__ __forceinline__ float wh_output (float t, float z0, float z1, const float* c)
@@ -3269,7 +3436,7 @@ struct WhReg {
 	int      ap, aReady; /* horn A's row parity; ab[ap ^ 1] holds this sub-block's horn A output */
 	int      ran;   /* a block of this launch went through the rotors (the history rows are newer than st.adx) */
 	float    z[4];  /* FILTER_C carries: the last lane's xf, x1, xin, xd1 */
-	float    fz0, fz1; /* per lane: lane f < 4 holds the state z0, z1 of serial filter f (st.fz[f]) */
+	float    fz0, fz1; /* per lane: lane WH_FZL (f) holds the state z0, z1 of serial filter f < 4 (st.fz[f]) */
 };
 
 __device__ __forceinline__ uint32_t uni (uint32_t v) { return __builtin_amdgcn_readfirstlane (v); }
@@ -3312,9 +3479,17 @@ __device__ __forceinline__ void wh_reg_load (WhLds<W>& sm, WhReg& R)
 	for (int i = 0; i < 4; i++)
 		R.z[i] = uni (st.z[i]);
 	R.fz0 = R.fz1 = 0.f;
+#if WH_SERIAL_REGS
+	if ((lane & 15) == 0) {
+		R.fz0 = st.fz[lane >> 4][0];
+		R.fz1 = st.fz[lane >> 4][1];
+	}
+#endif
 	if (lane < 4) {
+#if !WH_SERIAL_REGS
 		R.fz0       = st.fz[lane][0];
 		R.fz1       = st.fz[lane][1];
+#endif
 		sm.xf[lane] = st.adx[0][(st.adi[0] + 3 - lane) & 7];
 		sm.x1[lane] = st.adx[1][(st.adi[1] + 3 - lane) & 7];
 		sm.x2[lane] = st.adx[2][(st.adi[2] + 3 - lane) & 7];
@@ -3339,10 +3514,17 @@ __device__ __forceinline__ void wh_reg_store (WhLds<W>& sm, const WhReg& R)
 		for (int i = 0; i < 4; i++)
 			st.z[i] = R.z[i];
 	}
+#if WH_SERIAL_REGS
+	if ((lane & 15) == 0) {
+		st.fz[lane >> 4][0] = R.fz0;
+		st.fz[lane >> 4][1] = R.fz1;
+	}
+#else
 	if (lane < 4) {
 		st.fz[lane][0] = R.fz0;
 		st.fz[lane][1] = R.fz1;
 	}
+#endif
 	if (R.ran && lane < 24) { /* history k = lane / 8, entry j = lane % 8, one lane each */
 		const int    k = lane >> 3, j = lane & 7;
 		const float* h = k == 0 ? sm.xf : (k == 1 ? sm.x1 : sm.x2);
@@ -3418,8 +3600,14 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 		hb[j] = st.prm.hbfw[j];
 	}
 	/* a1, a2 of the serial lanes' recurrences: lane 0 horn A, lane 1 horn B, lanes 2-3 drum shelves */
+#if WH_SERIAL_REGS
+	/* chain f in lane 16 f: the coefficients by DPP row */
+	const float fa0 = lane < 16 ? ha[0] : (lane < 32 ? hb[0] : K.drf[0]);
+	const float fa1 = lane < 16 ? ha[1] : (lane < 32 ? hb[1] : K.drf[1]);
+#else
 	const float fa0 = lane == 0 ? ha[0] : (lane == 1 ? hb[0] : K.drf[0]);
 	const float fa1 = lane == 0 ? ha[1] : (lane == 1 ? hb[1] : K.drf[1]);
+#endif
 
 	for (int sb = 0; sb < TBF_BLK / TBF_SUB; sb++) {
 		const int      n      = lane;
@@ -3434,9 +3622,9 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 		sm.wring[0][o]     = 0.f;
 		sm.wring[1][o]     = 0.f;
 		/* DF2 biquads: horn B runs on horn A's output, so A runs one sub-block ahead and
-		 * one serial pass advances A over the next sub-block (lane 0), B over this one into
-		 * xf (lane 1) and the drum shelves over this one's ring outputs, in place (lanes 2,
-		 * 3).  A's own pass over this sub-block runs only when it is not ahead (launch
+		 * one serial pass advances A over the next sub-block (chain 0), B over this one into
+		 * xf (chain 1) and the drum shelves over this one's ring outputs, in place (chains 2,
+		 * 3); chain f runs in lane WH_FZL (f).  A's own pass over this sub-block runs only when it is not ahead (launch
 		 * start, after a bypassed block or a new coefficient set). */
 		const int  ap    = R.ap;
 		const bool aNext = sb + 1 < TBF_BLK / TBF_SUB || hasNext;
@@ -3449,8 +3637,16 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 		if (WH_RARE (!R.aReady)) {
 			const float z0 = rlf (R.fz0, 0), z1 = rlf (R.fz1, 0);
 #ifndef WH_NO_SERIAL
+#if WH_SERIAL_REGS
+			{ /* horn A alone, over this sub-block: every row of lanes loads its row, chain 0 is the active one */
+				float xc[4];
+				wh_chain_load<false> (sm.ab[ap ^ 1], 0u, ~0u, xc);
+				wh_serial_regs<false> (sm.ab[ap ^ 1], 0u, ~0u, xc, 1ull, R.fz0, R.fz1, ha[0], ha[1], false);
+			}
+#else
 			if (lane == 0)
 				wh_serial_v (sm.ab[ap ^ 1], R.fz0, R.fz1, ha[0], ha[1], false);
+#endif
 #endif
 			wave_sync ();
 			sm.ab[ap ^ 1][n] = wh_output (sm.ab[ap ^ 1][n], z0, z1, ha);
@@ -3462,8 +3658,8 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 		float      zs[4][2];
 #pragma unroll
 		for (int f = 0; f < 4; f++) {
-			zs[f][0] = rlf (R.fz0, f);
-			zs[f][1] = rlf (R.fz1, f);
+			zs[f][0] = rlf (R.fz0, WH_FZL (f));
+			zs[f][1] = rlf (R.fz1, WH_FZL (f));
 		}
 		if (scrubA) {
 			zs[0][0] = isnan (zs[0][0]) ? 0.f : zs[0][0];
@@ -3471,6 +3667,29 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 		}
 		const uint32_t wb   = R.outpos & WM; /* the drum rings' window: wave-uniform */
 		const bool     wrap = wb + TBF_SUB > (uint32_t)W;
+#if WH_SERIAL_REGS && !defined(WH_NO_SERIAL)
+		{
+			/* chain f's row in the lanes of DPP row f; horn A's chain is inactive when there
+			 * is no next sub-block */
+#ifdef WH_ABL_HORN /* timing experiment only (wrong output): horn filters A, B not run in k_whirl */
+			const uint64_t chains = 0x0001000100000000ull;
+#else
+			const uint64_t chains = 0x0001000100010000ull | (aNext ? 1ull : 0ull);
+#endif
+			float* row = lane < 16 ? sm.ab[ap] : (lane < 32 ? sm.ab[ap ^ 1] : sm.wring[lane >> 4]);
+			float  xc[4];
+			if (WH_RARE (wrap)) {
+				/* (outpos advances by whole sub-blocks from 0, so no state reaches this) */
+				wh_chain_load<true> (row, lane < 32 ? 0u : wb, lane < 32 ? ~0u : WM, xc);
+				wh_serial_regs<true> (row, lane < 32 ? 0u : wb, lane < 32 ? ~0u : WM, xc, chains, R.fz0, R.fz1, fa0, fa1,
+				                      lane == 0 && scrubA);
+			} else {
+				row += lane < 32 ? 0u : wb;
+				wh_chain_load<false> (row, 0u, ~0u, xc);
+				wh_serial_regs<false> (row, 0u, ~0u, xc, chains, R.fz0, R.fz1, fa0, fa1, lane == 0 && scrubA);
+			}
+		}
+#else
 #ifdef WH_NO_SERIAL /* timing experiment only (wrong output): k_whirl without its serial filter passes */
 		if (false) {
 #elif defined(WH_ABL_HORN) /* timing experiment only (wrong output): horn filters A, B not run in k_whirl */
@@ -3484,6 +3703,7 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 			else
 				wh_serial_v (row + (lane < 2 ? 0u : wb), R.fz0, R.fz1, fa0, fa1, lane == 0 && scrubA);
 		}
+#endif
 		wave_sync ();
 		/* the filter outputs: horn B -> xf, horn A of the next sub-block in place, the drum
 		 * shelves' (then the ring slots are cleared) */
@@ -4116,8 +4336,12 @@ __device__ void whirl_horn (const tbf_launch& P, WhLds<W>& sm, const bool bypass
 		wave_sync ();
 		if (WH_RARE (!sm.aReady)) {
 			const float z0 = st.fz[0][0], z1 = st.fz[0][1];
+#if WH_SERIAL_REGS
+			whs_serial_regs<false> (sm.ab[ap ^ 1], 0u, ~0u, 1ull, st.fz, ha[0], ha[1], false);
+#else
 			if (lane == 0)
 				wh_serial_v (sm.ab[ap ^ 1], st.fz[0], ha[0], ha[1], false);
+#endif
 			wave_sync ();
 			sm.ab[ap ^ 1][n] = wh_output (sm.ab[ap ^ 1][n], z0, z1, ha);
 			wave_sync ();
@@ -4133,8 +4357,13 @@ __device__ void whirl_horn (const tbf_launch& P, WhLds<W>& sm, const bool bypass
 			zs[0][0] = isnan (zs[0][0]) ? 0.f : zs[0][0];
 			zs[0][1] = isnan (zs[0][1]) ? 0.f : zs[0][1];
 		}
+#if WH_SERIAL_REGS
+		whs_serial_regs<false> (lane < 16 ? sm.ab[ap] : sm.ab[ap ^ 1], 0u, ~0u, 0x10000ull | (aNext ? 1ull : 0ull), st.fz, fa0, fa1,
+		                        lane == 0 && scrubA);
+#else
 		if (lane < 2 && (lane > 0 || aNext))
 			wh_serial_v (lane == 0 ? sm.ab[ap] : sm.ab[ap ^ 1], st.fz[lane], fa0, fa1, lane == 0 && scrubA);
+#endif
 		wave_sync ();
 		sm.xf[4 + n] = wh_output (sm.ab[ap ^ 1][n], zs[1][0], zs[1][1], hb);
 		if (aNext)
@@ -4229,6 +4458,15 @@ __device__ void whirl_drum (const tbf_launch& P, WhLds<W>& sm, const bool bypass
 		const float z20 = st.fz[2][0], z21 = st.fz[2][1], z30 = st.fz[3][0], z31 = st.fz[3][1];
 		const uint32_t wb   = opos & WM; /* wave-uniform */
 		const bool     wrap = wb + TBF_SUB > (uint32_t)W;
+#if WH_SERIAL_REGS
+		{ /* chains 0, 1 (lanes 0, 16): DL, DR */
+			float* row = sm.wring[lane < 16 ? 2 : 3];
+			if (WH_RARE (wrap)) /* (outpos advances by whole sub-blocks from 0, so no state reaches this) */
+				whs_serial_regs<true> (row, wb, WM, 0x10001ull, &st.fz[2], K.drf[0], K.drf[1], false);
+			else
+				whs_serial_regs<false> (row + wb, 0u, ~0u, 0x10001ull, &st.fz[2], K.drf[0], K.drf[1], false);
+		}
+#else
 		if (lane < 2) {
 			float* row = sm.wring[2 + lane];
 			if (WH_RARE (wrap))
@@ -4236,6 +4474,7 @@ __device__ void whirl_drum (const tbf_launch& P, WhLds<W>& sm, const bool bypass
 			else
 				wh_serial_v (row + wb, st.fz[2 + lane], K.drf[0], K.drf[1], false);
 		}
+#endif
 		wave_sync ();
 		const float dL = wh_output (sm.wring[2][o], z20, z21, K.drf);
 		const float dR = wh_output (sm.wring[3][o], z30, z31, K.drf);
