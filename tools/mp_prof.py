@@ -29,7 +29,7 @@ def main():
         eng.render_device(nb, L.data_ptr(), R.data_ptr(), nb * 128)
         eng.synchronize()
     v = L[0, :64].cpu().numpy()
-    it = nb * 2 + 3  # 64-sample tiles (MP_WIDE), two per block
+    it = nb * 2 + 3  # 64-sample tiles, two per block
     print(f"per iteration (cycles), {it} iterations:")
     print(f"  helper 0: waveshaper {v[0] * 1e3 / it:8.0f}  products+loads {v[1] * 1e3 / it:8.0f}  barrier {v[2] * 1e3 / it:8.0f}")
     print(f"  serial  : work       {v[8] * 1e3 / it:8.0f}  barrier        {v[9] * 1e3 / it:8.0f}")

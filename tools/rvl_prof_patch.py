@@ -44,9 +44,9 @@ def main():
     body = sub(body, "\t\t\t__syncthreads ();\n\t\t\t/* ---- write phase ---- */",
                "\t\t\tt1 = RVP_T (); pt[2] += t1 - t0; t0 = t1;\n\t\t\t__syncthreads ();\n"
                "\t\t\tt1 = RVP_T (); pt[3] += t1 - t0; t0 = t1;\n\t\t\t/* ---- write phase ---- */")
-    body = sub(body, "#endif\n\t\t\t__syncthreads ();\n\t\t}\n#undef RVL_C",
-               "#endif\n\t\t\tt1 = RVP_T (); pt[4] += t1 - t0; t0 = t1;\n"
-               "\t\t\t__syncthreads ();\n\t\t\tt1 = RVP_T (); pt[5] += t1 - t0; t0 = t1;\n\t\t}\n#undef RVL_C")
+    body = sub(body, "RVL_DLY[l]);\n\t\t\t__syncthreads ();\n\t\t}\n\t} else {",
+               "RVL_DLY[l]);\n\t\t\tt1 = RVP_T (); pt[4] += t1 - t0; t0 = t1;\n"
+               "\t\t\t__syncthreads ();\n\t\t\tt1 = RVP_T (); pt[5] += t1 - t0; t0 = t1;\n\t\t}\n\t} else {")
     # the planner loop: planning as the "read phase", its two barriers
     body = sub(body, "\t\t\t__syncthreads ();\n\t\t\t__syncthreads ();\n\t\t}\n",
                "\t\t\tpt[7]++;\n\t\t\tt1 = RVP_T (); pt[2] += t1 - t0; t0 = t1;\n\t\t\t__syncthreads ();\n"

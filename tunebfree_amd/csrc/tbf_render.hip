@@ -36,22 +36,7 @@
 /* occupancy targets (waves per SIMD); LDS and VGPR budgets are sized for them */
 #define TG_WAVES 4
 #define TG_SPLIT_MAX 8 /* k_tonegen block ranges (waves) per instance */
-#ifndef TG_CACHE
-#define TG_CACHE 1 /* steady chunks: the program's wheels, lengths and offsets held in the lanes */
-#endif
-#ifndef TG_LDS_ALL
-#define TG_LDS_ALL 1 /* entries staged in LDS for steady chunks too (their per-block scalar loads: 21.8 -> 18.8 ms with TG_CACHE) */
-#endif
-#ifndef TG_ABL
-#define TG_ABL 0 /* timing experiments (wrong output): 1 bank reads from one row, 2 no scanner */
-#endif
 #define TG_PCAP 128    /* a delta chunk's program entries staged in LDS per block (longer: read from HBM) */
-#ifndef TG_GRFL
-#define TG_GRFL 0 /* 1: the entries' gains moved to scalar registers (v_readfirstlane) after their LDS reads */
-#endif
-#ifndef TG_LCACHE
-#define TG_LCACHE 1 /* TG_CACHE's per-entry bank position, end and length in LDS, not in the lanes */
-#endif
 #define RV_WAVES 3
 /* k_whirl: 4 waves per SIMD (128 VGPRs, 9.8 KB of LDS: 16 instances per CU, so 4096 run
  * at once on 256 CUs), motions and ring adds in 2 groups of 2 rings (4 rings per group
@@ -61,21 +46,6 @@
 #endif
 #ifndef WH_RG
 #define WH_RG 2 /* k_whirl rings per motion group (4 or 2) */
-#endif
-#ifndef WH_SERIAL_PIPE
-#define WH_SERIAL_PIPE 1 /* k_whirl serial passes: next group's reads ahead of this group's chain */
-#endif
-#ifndef WH_SERIAL_REGS
-#define WH_SERIAL_REGS 1 /* k_whirl / k_whirl_split serial passes fed from registers, one chain per DPP row (wh_serial_regs) */
-#endif
-#ifndef WH_SERIAL_PK
-#define WH_SERIAL_PK 1 /* wh_serial_regs: a1 t, a2 t by one packed multiply, three VALU a step (0: four) */
-#endif
-#ifndef WH_PIN_READS
-#define WH_PIN_READS 1 /* motion_pass: the ring reads pinned ahead of the adds, one LDS round trip per pass */
-#endif
-#ifndef WH_NEXT_TABLES
-#define WH_NEXT_TABLES 1 /* k_whirl: the next ring group's table loads issued ahead of this group's ring passes */
 #endif
 #ifndef WH_PAD
 /* floats after each LDS ring / horn-A row: the rows of one serial pass 16-B aligned (its
@@ -97,12 +67,10 @@ template <int K> struct IntC {
 /* ------------------------------------------------------------------ LDS layouts */
 struct TgLds {
 	tbf_tg_state st;
-#if TG_LCACHE
-	/* TG_CACHE, entry e < 2 NL: bank index of the wheel's current sample, and the wave's end
-	 * and length in the bank (a block advances the index by TBF_BLK, less the length past
-	 * the end) */
+	/* steady chunks (TgCache), entry e < 2 NL: bank index of the wheel's current sample, and
+	 * the wave's end and length in the bank (a block advances the index by TBF_BLK, less the
+	 * length past the end) */
 	uint32_t     cbase[2 * NL], cend[2 * NL], clen[2 * NL];
-#endif
 	float        swl[TBF_BLK];
 	float        vin[TBF_BLK];
 	float        prc[TBF_BLK];
@@ -127,7 +95,7 @@ struct TgLds {
 template <int W>
 struct WhLds {
 	tbf_wh_state st;
-	alignas (16) float wring[4][W + WH_PAD]; /* rows padded: the serial lanes 2, 3 read rings 2, 3 at the same index */
+	alignas (16) float wring[4][W + WH_PAD]; /* rows padded: the serial chains 2, 3 read rings 2, 3 at the same index */
 	float        xf[TBF_SUB + 4];
 	float        x1[TBF_SUB + 4];
 	float        x2[TBF_SUB + 4];
@@ -159,27 +127,6 @@ __device__ __forceinline__ void copy_words (T* dst, const T* src)
 		d[i] = s[i];
 }
 
-__device__ __forceinline__ uint32_t xorshift (uint32_t s)
-{
-	s ^= s << 13;
-	s ^= s >> 17;
-	s ^= s << 5;
-	return s;
-}
-
-/* xorshift32 state after a per-lane k steps from a uniform x0, from the nibble-sliced table
- * (xs_nib_table): one coalesced row load per nibble of x0, 8 in flight together */
-__device__ __forceinline__ uint32_t xs_jump_n (const uint32_t* __restrict__ J, uint32_t x0, int k)
-{
-	const uint32_t* N = J + 32 * TBF_XS_JUMP;
-	x0                = __builtin_amdgcn_readfirstlane (x0);
-	uint32_t v[8];
-#pragma unroll
-	for (int i = 0; i < 8; i++)
-		v[i] = N[(i * 16 + ((x0 >> (4 * i)) & 15u)) * TBF_XS_JUMP + k];
-	return ((v[0] ^ v[1]) ^ (v[2] ^ v[3])) ^ ((v[4] ^ v[5]) ^ (v[6] ^ v[7]));
-}
-
 /* lane l's value, wave-uniform (l uniform) */
 __device__ __forceinline__ int rl (int v, int l) { return __builtin_amdgcn_readlane (v, l); }
 
@@ -188,13 +135,6 @@ __device__ __forceinline__ double rld (double v, int l)
 	const unsigned long long u = __double_as_longlong (v);
 	const unsigned lo = __builtin_amdgcn_readlane ((unsigned)u, l), hi = __builtin_amdgcn_readlane ((unsigned)(u >> 32), l);
 	return __longlong_as_double ((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-__device__ __forceinline__ int wave_min (int v)
-{
-	for (int o = 32; o > 0; o >>= 1)
-		v = min (v, __shfl_xor (v, o));
-	return v;
 }
 
 __device__ __forceinline__ int wave_max (int v)
@@ -263,18 +203,6 @@ typedef float f4u __attribute__ ((ext_vector_type (4), aligned (4)));
  * src/whirl.cpp:1139, 1380-1381) and phases below 16384: so 0 <= x < 2^24, where fmodf
  * (x, 1) is x - floorf (x) exactly (the fractional bits).  NaN stays NaN either way. */
 __device__ __forceinline__ float frac1 (float x) { return x - floorf (x); }
-
-/* RBJ biquad, Direct Form II in float (EQ_IIR, src/whirl.cpp:1479-1485); coefficients
- * a1 a2 b0 b1 b2 in registers */
-__device__ __forceinline__ float eq_iir (float c0, float c1, float c2, float c3, float c4, float& z0, float& z1,
-                                         float x)
-{
-	float temp = x - (c0 * z0) - (c1 * z1);
-	float y    = (temp * c2) + (c3 * z0) + (c4 * z1);
-	z1         = z0;
-	z0         = temp;
-	return y;
-}
 
 /* One motion's ordered adds into a ring for a 64-sample sub-block (HN_MOTION /
  * DR_MOTION, src/whirl.cpp:1432-1469): sample n adds a_n into slot U_n and b_n into
@@ -355,20 +283,16 @@ __device__ __forceinline__ void motion_add (float* ring, int U, float a, float b
 /* ================================================================== k_tonegen */
 
 /* A chunk without control deltas plays one program on every block: its entries' wheels,
- * wave lengths and bank offsets are loaded once per launch into the lanes (entry lane and
- * lane + 64), and each block only advances the wheel positions in registers -- the per-block
- * prologue's chain of dependent loads (entry -> wheel position -> length and offset) is gone.
+ * wave lengths and bank offsets are resolved once per launch (a lane takes entries lane
+ * and lane + 64), and each block only advances the wheel positions -- the per-block prologue's
+ * chain of dependent loads (entry -> wheel position -> length and offset) is gone.
  * The positions go back to the state after the launch (tg_cache_store). */
 struct TgCache {
 	bool     on;
 	int      np;
 	bool     anyEnv;
-#if !TG_LCACHE
-	uint32_t w[2], len[2], off[2], pos[2];
-#endif
 };
 
-#if TG_LCACHE
 /* The positions live in LDS (sm.cbase / cend / clen): held in the lanes, they were spilled
  * around the interpreter, and each block's reload from scratch waited (vmcnt) for the
  * previous block's output stores too. */
@@ -410,42 +334,6 @@ __device__ __forceinline__ void tg_cache_store (const TgCache& c, TgLds& sm, con
 		}
 	}
 }
-#else
-__device__ __forceinline__ void tg_cache_load (TgCache& c, const tbf_launch& P, const TgLds& sm, const tbf_seg_ctl& G,
-                                               const tbf_tpl_desc* T)
-{
-	const int             lane = threadIdx.x & (NL - 1);
-	const tbf_prog_entry* prog = P.prog + G.prog_off + 1;
-	c.np                       = (int)P.prog[G.prog_off].pad;
-	c.on                       = c.np <= 2 * NL;
-	int env                    = 0;
-#pragma unroll
-	for (int k = 0; k < 2; k++) {
-		const int e = lane + k * NL;
-		c.w[k] = c.len[k] = c.off[k] = c.pos[k] = 0;
-		if (c.on && e < c.np) {
-			const uint32_t w = prog[e].wheel;
-			c.w[k]           = w;
-			c.len[k]         = T->len[w];
-			c.off[k]         = T->off[w];
-			c.pos[k]         = sm.st.pos[w];
-			env |= prog[e].env != 0;
-		}
-	}
-	c.anyEnv = __any (env);
-}
-
-__device__ __forceinline__ void tg_cache_store (const TgCache& c, TgLds& sm)
-{
-	const int lane = threadIdx.x & (NL - 1);
-	if (!c.on)
-		return;
-#pragma unroll
-	for (int k = 0; k < 2; k++)
-		if (lane + k * NL < c.np)
-			sm.st.pos[c.w[k]] = c.pos[k];
-}
-#endif
 
 /* oscGenerateFragment core interpreter + vibratoProc + mixdown, src/tonegen.cpp:3607-3777 */
 __device__ __forceinline__ void stage_tonegen (const tbf_launch& P, TgLds& sm, const tbf_seg_ctl& G, const tbf_tpl_desc* T,
@@ -465,25 +353,20 @@ __device__ __forceinline__ void stage_tonegen (const tbf_launch& P, TgLds& sm, c
 	/* A delta chunk (P.ctlIdx) plays a program k_tgctl has just written, a new one on every
 	 * block under dense events: its entries are read once, lane-parallel, into LDS here, for
 	 * the main loop's broadcast reads (the main loop's scalar loads of them missed the
-	 * scalar cache four entries at a time).  A chunk without deltas replays one program,
-	 * whose entries stay in the scalar cache. */
-	const bool lp      = (P.ctlIdx != nullptr || TG_LDS_ALL) && np <= TG_PCAP;
+	 * scalar cache four entries at a time).  A chunk without deltas replays one program and
+	 * stages it the same way: its per-block scalar loads cost more (k_tonegen 3.79 -> 4.96 ms
+	 * per 512 blocks, profiles/r06/s23_tg_lds_all). */
+	const bool lp      = np <= TG_PCAP;
 	bool       anyEnv;
 	if (tc && tc->on) {
-		/* the launch's program, entries held in the lanes (TgCache) */
+		/* the launch's program, its entries' bank positions cached in LDS (TgCache) */
 #pragma unroll
 		for (int k = 0; k < 2; k++) {
 			const int e = lane + k * NL;
 			if (e < np) {
-#if TG_LCACHE
 				const uint32_t b = sm.cbase[e], nb = b + TBF_BLK; /* off + pos, off + pos + TBF_BLK */
 				sm.u.ent.base[e] = b;
 				sm.cbase[e]      = (sm.cend[e] < nb) ? nb - sm.clen[e] : nb; /* (len < pos + TBF_BLK) as below */
-#else
-				const uint32_t pos = tc->pos[k], len = tc->len[k];
-				sm.u.ent.base[e] = tc->off[k] + pos;
-				tc->pos[k]       = (len < pos + TBF_BLK) ? pos + TBF_BLK - len : pos + TBF_BLK;
-#endif
 				if (lp) { /* the gains through LDS too (the scanner's rows overwrite them each block) */
 					const uint4 a = ((const uint4*)(prog + e))[0], b = ((const uint4*)(prog + e))[1];
 					sm.u.ent.g[e] = make_float4 (__uint_as_float (a.y), __uint_as_float (a.z), __uint_as_float (a.w), __uint_as_float (b.x));
@@ -528,14 +411,9 @@ __device__ __forceinline__ void stage_tonegen (const tbf_launch& P, TgLds& sm, c
 				 * is then a scalar branch, so a steady entry skips the envelope arithmetic */
 				const float4 a = sm.u.ent.g[e];
 				const float2 b = sm.u.ent.h[e];
-#if TG_GRFL
-				auto rfl = [] (float v) { return __int_as_float (__builtin_amdgcn_readfirstlane (__float_as_int (v))); };
-				g[0] = rfl (a.x); g[1] = rfl (a.y); g[2] = rfl (a.z); g[3] = rfl (a.w); g[4] = rfl (b.x); g[5] = rfl (b.y);
-#else
 				/* the gains stay in the lanes (every lane read the same LDS word): only the
 				 * envelope word needs to be scalar, for the branch */
 				g[0] = a.x; g[1] = a.y; g[2] = a.z; g[3] = a.w; g[4] = b.x; g[5] = b.y;
-#endif
 				er = (uint32_t)__builtin_amdgcn_readfirstlane ((int)sm.u.ent.er[e]);
 			} else {
 				const tbf_prog_entry& E = prog[e];
@@ -556,11 +434,7 @@ __device__ __forceinline__ void stage_tonegen (const tbf_launch& P, TgLds& sm, c
 			constexpr bool EN = decltype (EC)::value; /* the block has envelope entries */
 #pragma unroll
 			for (int k = 0; k < K; k++) {
-#if TG_ABL == 1 /* timing experiment only (wrong output): every entry reads the bank's first row */
-				const float* __restrict__ bp = P.bank + (sm.u.ent.base[e + k] & 63u);
-#else
 				const float* __restrict__ bp = P.bank + sm.u.ent.base[e + k];
-#endif
 				G.xs[k]                      = f2v {bp[lane], bp[lane + NL]};
 				if constexpr (EN) { /* (a steady entry loads row 0 of the attack table: an L1 hit) */
 					float    gg[6];
@@ -649,11 +523,7 @@ __device__ __forceinline__ void stage_tonegen (const tbf_launch& P, TgLds& sm, c
 
 	const uint32_t routing = G.routing;
 	/* vibrato scanner, src/vibrato.cpp:365-411 */
-#if TG_ABL == 2 /* timing experiment only (wrong output): no scanner */
-	if (false) {
-#else
 	if (routing & 0x03) {
-#endif
 		const uint32_t* otab  = P.vibTab + 2048u * G.vibTable;
 		const uint32_t  out0  = st.outPos;
 		const uint32_t  stat0 = st.stator;
@@ -832,7 +702,7 @@ k_tonegen (const tbf_launch P, const tbf_seg_ctl* __restrict__ ctl, const tbf_tp
 	/* a chunk without deltas plays the instance's current program on every block */
 	TgCache tc;
 	tc.on = false;
-	if (!P.ctlIdx && TG_CACHE)
+	if (!P.ctlIdx)
 		tg_cache_load (tc, P, sm, ctl_of (P, ctl, 0, inst), T);
 	if (part > 0)
 		stage_tonegen (P, sm, ctl_of (P, ctl, 0, inst), T, nullptr, nullptr, nullptr, 0.f, 0.f, &tc);
@@ -845,11 +715,7 @@ k_tonegen (const tbf_launch P, const tbf_seg_ctl* __restrict__ ctl, const tbf_tp
 			stage_tonegen (P, sm, ctl_of (P, ctl, blk, inst), T, o + (size_t)blk * TBF_BLK, nullptr, nullptr, 0.f, 0.f, &tc);
 	}
 	if (part == ns - 1) {
-#if TG_LCACHE
 		tg_cache_store (tc, sm, P, ctl_of (P, ctl, 0, inst), T);
-#else
-		tg_cache_store (tc, sm);
-#endif
 		wave_sync ();
 		const uint32_t* src = (const uint32_t*)&sm.st;
 		uint32_t*       dst = (uint32_t*)S;
@@ -869,9 +735,8 @@ k_tonegen (const tbf_launch P, const tbf_seg_ctl* __restrict__ ctl, const tbf_tp
  *              alternate samples, so each covers half a tile).  One FP64 instruction stream
  *              advances 64 chains; a wave per instance served 2.
  *   wave 1     the preamp's xorshift dither stream (fpd), lane j = instance j
- *   waves 2..  lane-parallel work, one instance per task and wave (MP_WIDE: 64-sample tiles;
- *              else two instances per task, a half-wave each, 32-sample tiles): the gain
- *              products, the denormal guard, the waveshaper, blend and dither, the stores
+ *   waves 2..  lane-parallel work, one instance per task and wave (64-sample tiles): the
+ *              gain products, the denormal guard, the waveshaper, blend and dither, the stores
  * Iteration it: the chases of tile it, the products of tile it - 1, the high-pass of tile
  * it - 2, the waveshaper of tile it - 3; one barrier per iteration.  Every chain runs the
  * reference's operations in its order.  Tonegen-only chains (configs[1]) stop after the
@@ -885,20 +750,6 @@ k_tonegen (const tbf_launch P, const tbf_seg_ctl* __restrict__ ctl, const tbf_tp
 #ifndef MP_PROF
 #define MP_PROF 0 /* profiling variant: s_memtime per role and section (tools/mp_prof.py) */
 #endif
-#ifndef MP_ABL
-#define MP_ABL 0 /* timing experiments (wrong output): 1 no waveshaper, 2 no serial chains, 3 no dither */
-#endif
-#ifndef MP_SIN_PAIRS
-#define MP_SIN_PAIRS 0 /* the density sines in pairs (tbf_sin2) instead of one vote for all tasks */
-#endif
-#ifndef MP_PRIO
-#define MP_PRIO 2 /* the helpers raise their priority at the waveshaper's start and drop it after density
-                   * step MP_PRIO - 1, so the two helpers of a SIMD progress together instead of in age order */
-#endif
-#ifndef MP_WIDE
-#define MP_WIDE 1 /* tiles of 64 samples, a helper task = one instance (0: 32, an instance pair) */
-#endif
-#if MP_WIDE
 /* a tile is a whole wave of samples: each iteration gives a CU 2048 samples of waveshaper
  * work (four density sines each, chains of dependent FP64 operations), eight chains per
  * SIMD instead of four, which the 32-sample tiles left latency-bound (tools/mp_prof.py) */
@@ -906,12 +757,6 @@ k_tonegen (const tbf_launch P, const tbf_seg_ctl* __restrict__ ctl, const tbf_tp
 #define MP_NTK (MP_CB / MP_H)     /* helper tasks (instances) per tile */
 #define MP_XR 3                   /* preamp-input rows by tile mod 3 (tiles it-1 .. it-3 alive) */
 #define MP_CR 4                   /* control slots by block mod 4 (two tiles per block) */
-#else
-#define MP_T 32                   /* samples per tile: one per lane of a half-wave */
-#define MP_NTK (MP_CB / 2 / MP_H) /* helper tasks (instance pairs) per tile */
-#define MP_XR 4
-#define MP_CR 2
-#endif
 #define MP_S (MP_T + 1)           /* row stride of the per-sample rows (odd: conflict-free columns) */
 #define MP_HS (MP_T / 2 + 1)      /* row stride of the high-pass rows (a chain's MP_T / 2 samples) */
 #ifndef MP_H
@@ -919,8 +764,7 @@ k_tonegen (const tbf_launch P, const tbf_seg_ctl* __restrict__ ctl, const tbf_tp
 #endif
 #define MP_THREADS (NL * (2 + MP_H))
 #define MP_TPB (TBF_BLK / MP_T)   /* tiles per block */
-static_assert (2 * MP_CB <= NL && (MP_WIDE ? MP_T == NL && MP_CB % MP_H == 0 : 2 * MP_T == NL && MP_CB % (2 * MP_H) == 0),
-               "k_mixpre geometry");
+static_assert (2 * MP_CB <= NL && MP_T == NL && MP_CB % MP_H == 0, "k_mixpre geometry");
 #define MP_ROWS (2 * MP_CB + (2 * MP_CB < NL)) /* chain rows, + one that idle chain lanes write */
 
 /* one block's control of an instance as k_mixpre uses it, staged in LDS by the dither wave
@@ -1011,14 +855,12 @@ __device__ __forceinline__ void preamp_shape_n (const double (&x0)[NT], const do
 		dpos = dpos && (C[t]->flags & MPF_DPOS);
 	}
 	const int itw = wave_max (itm);
-#if MP_PRIO
+	/* the helper raises its priority here and drops it after the second density step, so the
+	 * two helpers of a SIMD progress together instead of in age order */
 	__builtin_amdgcn_s_setprio (1);
-#endif
 	for (int c = 0; c < itw; c++) {
-#if MP_PRIO
-		if (c == MP_PRIO)
+		if (c == 2)
 			__builtin_amdgcn_s_setprio (0);
-#endif
 		double br[NT];
 #pragma unroll
 		for (int t = 0; t < NT; t++) {
@@ -1026,21 +868,13 @@ __device__ __forceinline__ void preamp_shape_n (const double (&x0)[NT], const do
 			if (br[t] > 1.57079633)
 				br[t] = 1.57079633;
 		}
-#if MP_SIN_PAIRS
-#pragma unroll
-		for (int t = 0; t < NT; t += 2)
-			tbf_sin2 (br[t], br[t + 1], br[t], br[t + 1]);
-#else
 		tbf_sin_n<NT> (br);
-#endif
 #pragma unroll
 		for (int t = 0; t < NT; t++)
 			if (c < C[t]->iter)
 				x[t] = (x[t] > 0.0) ? br[t] : -br[t];
 	}
-#if MP_PRIO
 	__builtin_amdgcn_s_setprio (0);
-#endif
 	double br[NT];
 #pragma unroll
 	for (int t = 0; t < NT; t++) {
@@ -1117,12 +951,8 @@ k_mixpre (const tbf_launch P, const tbf_seg_ctl* __restrict__ ctl)
 					rsv = C.reset;
 				}
 				float* row = sm.g[it & 1][cl];
-#if MP_ABL == 2 /* timing experiment only (wrong output): no serial chase or high-pass */
-				if (true) {
-#else
 				if (__all ((v * m) + a == v)) { /* a fixed point on every lane (no percussion, the key
 				                                  * compression settled): the whole tile is v */
-#endif
 #pragma unroll 8
 					for (int k = 0; k < MP_T; k++)
 						row[k] = v;
@@ -1151,11 +981,7 @@ k_mixpre (const tbf_launch P, const tbf_seg_ctl* __restrict__ ctl)
 					hp             = !(C.flags & MPF_CLEAN);
 					ia             = C.iir;
 				}
-#if MP_ABL == 2
-				if (false) {
-#else
 				if (hp) {
-#endif
 					const double* xr = sm.x[th % MP_XR][cl];
 					double*       hr = sm.h[th & 1][cl];
 					const double  om = 1.0 - ia;
@@ -1228,11 +1054,7 @@ k_mixpre (const tbf_launch P, const tbf_seg_ctl* __restrict__ ctl)
 			const unsigned long long _d0 = __builtin_amdgcn_s_memtime ();
 #endif
 			if (lane < MP_CB) {
-#if MP_ABL == 3 /* timing experiment only (wrong output): no dither stream */
-				if (false) {
-#else
 				if (pre && it < nT) {
-#endif
 					if (it % MP_TPB == 0)
 						adv =!(sm.c[(it / MP_TPB) % MP_CR][lane].flags & MPF_CLEAN);
 					uint32_t* f = sm.f[it & 3][lane];
@@ -1269,11 +1091,10 @@ k_mixpre (const tbf_launch P, const tbf_seg_ctl* __restrict__ ctl)
 			M->odFpd = fs;
 		return;
 	}
-	/* helpers: task t = instance h + MP_H t, lane n = sample n of the tile (MP_WIDE; else
-	 * instances 2 (h + MP_H t) + {0, 1}, half-wave hj each, lane n of the half-wave = sample n).
+	/* helpers: task t = instance h + MP_H t, lane n = sample n of the tile.
 	 * The (s, p) input is read two iterations before its use, into two register sets
 	 * alternating by iteration parity (the loop is unrolled by two, so the sets stay static) */
-	const int     h = w - 2, hj = MP_WIDE ? 0 : lane >> 5, n = lane & (MP_T - 1);
+	const int     h = w - 2, n = lane & (MP_T - 1);
 	const float2* in[MP_NTK];
 	float*        o1[MP_NTK];
 	float*        oL[MP_NTK];
@@ -1283,7 +1104,7 @@ k_mixpre (const tbf_launch P, const tbf_seg_ctl* __restrict__ ctl)
 	float2        pS[2][MP_NTK];
 #pragma unroll
 	for (int t = 0; t < MP_NTK; t++) {
-		const int j       = MP_WIDE ? h + MP_H * t : 2 * (h + MP_H * t) + hj;
+		const int j       = h + MP_H * t;
 		okT[t]            = j < nj;
 		jT[t]             = okT[t] ? j : nj - 1;
 		const uint32_t is = inst0 + jT[t];
@@ -1330,11 +1151,7 @@ k_mixpre (const tbf_launch P, const tbf_seg_ctl* __restrict__ ctl)
 					xd[t] = sm.x[kw % MP_XR][rT[t]][n >> 1];
 					xh[t] = sm.h[kw & 1][rT[t]][n >> 1];
 					f1[t] = sm.f[kw & 3][jT[t]][n + 1];
-#if MP_ABL == 1 /* timing experiment only (wrong output): helpers without the waveshaper */
-					cl[t] = true;
-#else
 					cl[t] = (Cp[t]->flags & MPF_CLEAN) != 0;
-#endif
 					allCl = allCl && cl[t];
 				}
 				if (!__all (allCl))
@@ -1448,19 +1265,12 @@ k_mixpre (const tbf_launch P, const tbf_seg_ctl* __restrict__ ctl)
 /* sin (v0 + (n+1) D) by angle addition from the start phase's S = sin v0, C = cos v0 and the
  * step rows sd = sin ((n+1) D), cm = 2 sin^2 ((n+1) D / 2): S + (C sd - S cm).  Not libm's
  * bits either way (FP64 sines only need a few ulps; the float outputs
- * are bit-identical); RVL_SINFMA forms C sd - S cm with one fma (3 FP64 instructions for 4:
+ * are bit-identical); C sd - S cm is formed with one fma (3 FP64 instructions for 4:
  * k_rv_core_lds 9.48 -> 9.42 ms alone per 512 blocks, profiles/r06/s2).  Every network
  * kernel and path uses this one expression, so they agree however a render is split. */
-#ifndef RVL_SINFMA
-#define RVL_SINFMA 1
-#endif
 __device__ __forceinline__ double rv_sin_add (double S, double C, double sd, double cm)
 {
-#if RVL_SINFMA
 	return S + __builtin_fma (C, sd, -(S * cm));
-#else
-	return S + ((C * sd) - (S * cm));
-#endif
 }
 
 struct RvCoreLds {
@@ -1792,33 +1602,8 @@ struct RvLds {
 };
 static_assert (sizeof (RvLds) <= 160 * 1024, "k_rv_core_lds: a channel's rings fill gfx950's 160 KB of LDS");
 
-/* a ring write at slot i of a line of delay d, and at its mirror when i < RVL_MIR */
-__device__ __forceinline__ void rvl_write (double* rg, int i, int d, double v)
-{
-	rg[i] = v;
-	if (i < RVL_MIR)
-		rg[i + d + 1] = v;
-}
-
-#ifndef RVL_FAST2
-#define RVL_FAST2 1 /* tap index without the FP64 sum (a vote on the rare carry), allpass products as fmas (exact) */
-#endif
-#ifndef RVL_PRIO
-#define RVL_PRIO 1 /* workers raise their priority at a phase start and drop it part-way, so the three workers
-                    * of a SIMD progress together instead of in age order (1: drop after the tap reads, 2: after
-                    * the Householder mix) */
-#endif
-#ifndef RVL_EXPECT
-#define RVL_EXPECT 1 /* the ring wrap / mirror branches marked unlikely, so the common case falls through */
-#endif
-#if RVL_EXPECT
+/* the ring wrap / mirror branches are marked unlikely, so the common case falls through */
 #define RVL_RARE(x) __builtin_expect (!!(x), 0)
-#else
-#define RVL_RARE(x) (x)
-#endif
-#ifndef RVL_SCAL
-#define RVL_SCAL 1 /* the workers' line counters in scalar registers, wraps as scalar branches (below) */
-#endif
 /* lane n's slot c + n of a line of delay D, wrapped past D (wrap_slot), for a wave-uniform c
  * in [0, D + 1]: a sub-block wraps a line in about one of D / 64 groups, so the test is a
  * scalar branch around the lanes' correction and the common case is one add */
@@ -1850,8 +1635,9 @@ __device__ __forceinline__ int rvl_slot_l (int l, const int (&cs)[12], int n)
 	}
 }
 
-/* rvl_write at slot rvl_slot<D> (c, n): the mirror (slots below RVL_MIR) is possible only when
- * c < RVL_MIR or the sub-block wraps, again a scalar test.  The rare block only adjusts the
+/* a ring write at slot rvl_slot<D> (c, n) of a line of delay D, and at its mirror (slot +
+ * D + 1) when the slot is below RVL_MIR: the mirror is possible only when c < RVL_MIR or
+ * the sub-block wraps, again a scalar test.  The rare block only adjusts the
  * slot and writes the mirror, and the one ring write follows the join: the common case is a
  * scalar compare, a branch not taken and the write.  With a ring write on either side of
  * the test, the rare block lay inline behind the common write, which then took a second
@@ -2039,16 +1825,11 @@ __device__ __forceinline__ void rvl_pair (const tbf_launch& P, const tbf_inst_co
 	/* the workers and the planner run separate loops with the same two barriers per group, so
 	 * the registers of one role are not held live across the other's code */
 	if (w < RVL_G) {
-#if RVL_SCAL
 		/* this worker's first slot of each line in the group, wave-uniform (SGPRs) */
 		int cs[12];
 #pragma unroll
 		for (int l = 0; l < 12; l++)
 			cs[l] = rl (cw, l);
-#define RVL_C(l) cs[l]
-#else
-#define RVL_C(l) rl (cw, l)
-#endif
 #pragma unroll 1
 		for (uint32_t g = 0; g < nGrp; g++) {
 			const int  nb  = (int)min ((uint32_t)RVL_G, nSub - g * RVL_G);
@@ -2067,9 +1848,9 @@ __device__ __forceinline__ void rvl_pair (const tbf_launch& P, const tbf_inst_co
 			if (pst)
 				rv_st (&bout[po], pmix);
 			if (act) {
-#if RVL_PRIO
+				/* the priority raised at a phase start and dropped part-way (here after the tap
+				 * reads), so the three workers of a SIMD progress together instead of in age order */
 				__builtin_amdgcn_s_setprio (1);
-#endif
 				/* the lines' vibrato sines: closed form on every line (wave-uniform, the rule), or
 				 * per line the closed form or the literal recurrence and sin */
 				const uint32_t om = __builtin_amdgcn_readfirstlane (sm.okm[par][w]);
@@ -2107,20 +1888,16 @@ __device__ __forceinline__ void rvl_pair (const tbf_launch& P, const tbf_inst_co
 				 * next line's address was formed) */
 				double I[8], fr[8], r0[8], r1[8];
 				int    wk[8];
-#if RVL_SCAL && RVL_FAST2
 				double offv[8];
 				int    cnv[8];
 				bool   slow = false;
-#endif
 #pragma unroll
 				for (int l = 0; l < 8; l++) {
 					const double off = (sn[l] + 1.0) * K.vibDepth;
-#if RVL_SCAL
 					const int cn = rvl_slot_l (l, cs, n);
 					/* off >= 0, so off - floor (off) is exact (or off < 0 tiny, |off| >= 2.7 2^-53: one
 					 * rounding of off + 1, below 1): v_fract_f64's value */
 					fr[l] = __builtin_amdgcn_fract (off);
-#if RVL_FAST2
 					/* (int)(cn + off) == cn + (int)off unless the sum's rounding (ulp <= 2^-42, the
 					 * sum < 2048) carries the fraction to the next integer, or off < 0: both need
 					 * fr >= 1 - 2^-21, i.e. fr's high word >= 0x3FEFFFFF (one integer compare);
@@ -2129,31 +1906,19 @@ __device__ __forceinline__ void rvl_pair (const tbf_launch& P, const tbf_inst_co
 					cnv[l]  = cn;
 					wk[l]   = cn + (int)off;
 					slow    = slow || (uint32_t)(__double_as_longlong (fr[l]) >> 32) >= 0x3FEFFFFFu;
-#else
-					wk[l] = (int)(cn + off); /* <= d + 5: the mirror covers wk + 1 */
-#endif
-#else
-					const int    cn  = wrap_slot (rl (cw, l) + n + 1, RVL_DLY[l]);
-					wk[l]            = (int)(cn + off); /* <= d + 5: the mirror covers wk + 1 */
-					fr[l]            = off - floor (off);
-#endif
 				}
-#if RVL_SCAL && RVL_FAST2
 				if (__builtin_expect (__any (slow), 0)) {
 #pragma unroll
 					for (int l = 0; l < 8; l++)
 						wk[l] = (int)(cnv[l] + offv[l]);
 				}
-#endif
 #pragma unroll
 				for (int l = 0; l < 8; l++) {
 					const double* rg = sm.ring + RVL_LOFS[l];
 					r0[l]            = rg[wk[l]];
 					r1[l]            = rg[wk[l] + 1];
 				}
-#if RVL_PRIO == 1
 				__builtin_amdgcn_s_setprio (0);
-#endif
 #pragma unroll
 				for (int l = 0; l < 8; l++) {
 					double x = (r0[l] * (1 - fr[l]));
@@ -2171,13 +1936,9 @@ __device__ __forceinline__ void rvl_pair (const tbf_launch& P, const tbf_inst_co
 				fb[6] = (I[6] - (I[4] + I[5] + I[7])) * K.regen;
 				fb[7] = (I[7] - (I[4] + I[5] + I[6])) * K.regen;
 				mix = (I[0] + I[1] + I[2] + I[3] + I[4] + I[5] + I[6] + I[7]) / 8.0;
-#if RVL_PRIO == 2
-				__builtin_amdgcn_s_setprio (0);
-#endif
 #pragma unroll
 				for (int l = 8; l < 12; l++) {
-					const double old = sm.ring[RVL_LOFS[l] + RVL_C (l) + n + 1]; /* <= d + 64: mirror */
-#if RVL_FAST2
+					const double old = sm.ring[RVL_LOFS[l] + cs[l] + n + 1]; /* <= d + 64: mirror */
 					/* a0 - old 0.5 then (.) 0.5 + old: both products by 0.5 are exact unless an
 					 * operand is subnormal (< 2.2e-308), so one fma each gives the reference's
 					 * values.  The input's denormal guard (src/reverb.cpp:343-346) keeps the input
@@ -2188,14 +1949,6 @@ __device__ __forceinline__ void rvl_pair (const tbf_launch& P, const tbf_inst_co
 					const double a = __builtin_fma (old, -0.5, a0);
 					apw[l - 8]     = a;
 					ap[l - 8]      = __builtin_fma (a, 0.5, old);
-#else
-					double       a   = a0;
-					a -= old * 0.5;
-					apw[l - 8] = a;
-					a *= 0.5;
-					a += old;
-					ap[l - 8] = a;
-#endif
 				}
 				if (n == NL - 1) {
 #pragma unroll
@@ -2206,16 +1959,13 @@ __device__ __forceinline__ void rvl_pair (const tbf_launch& P, const tbf_inst_co
 			__syncthreads ();
 			/* ---- write phase ---- */
 			if (act) {
-#if RVL_PRIO
 				__builtin_amdgcn_s_setprio (1);
-#endif
 				/* the previous sub-block's last feedback, all 8 lines read before any ring write */
 				const double* cp = w == 0 ? sm.carry[par ^ 1][RVL_G - 1] : sm.carry[par][w - 1];
 				double        cprv[8];
 #pragma unroll
 				for (int l = 0; l < 8; l++)
 					cprv[l] = cp[l];
-#if RVL_SCAL
 				rvl_write_s<RVL_DLY[8]> (sm.ring + RVL_LOFS[8], cs[8], n, apw[0]);
 				rvl_write_s<RVL_DLY[9]> (sm.ring + RVL_LOFS[9], cs[9], n, apw[1]);
 				rvl_write_s<RVL_DLY[10]> (sm.ring + RVL_LOFS[10], cs[10], n, apw[2]);
@@ -2223,27 +1973,13 @@ __device__ __forceinline__ void rvl_pair (const tbf_launch& P, const tbf_inst_co
 				/* feedback (n - 1): lane 0 takes the previous sub-block's last, the DPP move's old value */
 				rvl_write_s<RVL_DLY[0]> (sm.ring + RVL_LOFS[0], cs[0], n, ap[3] + lane_shr1_or (fb[0], cprv[0]));
 				rvl_write_s<RVL_DLY[1]> (sm.ring + RVL_LOFS[1], cs[1], n, ap[2] + lane_shr1_or (fb[1], cprv[1]));
-#if RVL_PRIO
 				__builtin_amdgcn_s_setprio (0);
-#endif
 				rvl_write_s<RVL_DLY[2]> (sm.ring + RVL_LOFS[2], cs[2], n, ap[1] + lane_shr1_or (fb[2], cprv[2]));
 				rvl_write_s<RVL_DLY[3]> (sm.ring + RVL_LOFS[3], cs[3], n, ap[0] + lane_shr1_or (fb[3], cprv[3]));
 				rvl_write_s<RVL_DLY[4]> (sm.ring + RVL_LOFS[4], cs[4], n, ap[0] + lane_shr1_or (fb[4], cprv[4]));
 				rvl_write_s<RVL_DLY[5]> (sm.ring + RVL_LOFS[5], cs[5], n, ap[1] + lane_shr1_or (fb[5], cprv[5]));
 				rvl_write_s<RVL_DLY[6]> (sm.ring + RVL_LOFS[6], cs[6], n, ap[2] + lane_shr1_or (fb[6], cprv[6]));
 				rvl_write_s<RVL_DLY[7]> (sm.ring + RVL_LOFS[7], cs[7], n, ap[3] + lane_shr1_or (fb[7], cprv[7]));
-#else
-#pragma unroll
-				for (int l = 8; l < 12; l++)
-					rvl_write (sm.ring + RVL_LOFS[l], wrap_slot (rl (cw, l) + n, RVL_DLY[l]), RVL_DLY[l], apw[l - 8]);
-				const int srcAp[8] = {3, 2, 1, 0, 0, 1, 2, 3};
-#pragma unroll
-				for (int l = 0; l < 8; l++) {
-					const double up   = lane_shr1 (fb[l]);
-					const double prev = n == 0 ? cprv[l] : up;
-					rvl_write (sm.ring + RVL_LOFS[l], wrap_slot (rl (cw, l) + n, RVL_DLY[l]), RVL_DLY[l], ap[srcAp[l]] + prev);
-				}
-#endif
 				/* the tap mix, stored at the start of the next group (see above) */
 				pmix = mix;
 				po   = o;
@@ -2252,14 +1988,11 @@ __device__ __forceinline__ void rvl_pair (const tbf_launch& P, const tbf_inst_co
 			a0  = a0n;
 			a0n = nxt;
 			cw = wrap_slot (cw + TBF_SUB * RVL_G, dlyv);
-#if RVL_SCAL
 #pragma unroll
 			for (int l = 0; l < 12; l++)
 				cs[l] = wrap_slot (cs[l] + TBF_SUB * RVL_G, RVL_DLY[l]);
-#endif
 			__syncthreads ();
 		}
-#undef RVL_C
 	} else {
 #pragma unroll 1
 		for (uint32_t g = 0; g < nGrp; g++) {
@@ -2389,13 +2122,6 @@ __device__ __forceinline__ void rvc_dither_row (uint32_t* f, uint32_t& s)
 		s    = xs_step (s);
 	}
 	f[RVC_T] = s;
-}
-
-/* the predelay slot k samples after counter c in [0, d] (k <= d + 1): cnt_adv's steady state */
-__device__ __forceinline__ int rvc_slot (int c, int d, int k)
-{
-	const int v = c + k;
-	return v > d ? v - d - 1 : v;
 }
 
 /* a launch's per-block values sit one per lane: lane b = block b.  A launch of more than 64
@@ -2924,15 +2650,9 @@ k_rv_post (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf
 }
 
 /* ================================================================== k_whirl */
-#ifndef WH_EXPECT
-#define WH_EXPECT 1 /* rare paths (bypass, horn A catching up, a wrapped drum window, the rotor-angle and
-                     * motion replays, a new parameter set) marked unlikely: the common case falls through */
-#endif
-#if WH_EXPECT
+/* rare paths (bypass, horn A catching up, a wrapped drum window, the rotor-angle and motion
+ * replays, a new parameter set) are marked unlikely: the common case falls through */
 #define WH_RARE(x) __builtin_expect (!!(x), 0)
-#else
-#define WH_RARE(x) (x)
-#endif
 __device__ void whirl_speed (tbf_wh_state& st, const tbf_inst_const& K, int revOpt, int& brake)
 {
 	/* the rotor state in registers: its LDS reads issued together, not one per branch */
@@ -3067,7 +2787,6 @@ __device__ __forceinline__ void motion_pass (float (*ring)[W + WH_PAD], const in
 		v[gi]  = ring[gi][i0[gi]];
 		w[gi]  = ring[gi][i1[gi]];
 	}
-#if WH_PIN_READS
 	/* the loaded values are pinned here, all reads issued: left to itself the compiler
 	 * sinks the adds and one of the reads into the owners' store branches below, and each
 	 * pass then waits out two or more LDS latencies (a read and a full lgkmcnt(0) drain
@@ -3075,7 +2794,6 @@ __device__ __forceinline__ void motion_pass (float (*ring)[W + WH_PAD], const in
 #pragma unroll
 	for (int gi = 0; gi < RG; gi++)
 		asm volatile ("" : "+v"(v[gi]), "+v"(w[gi]));
-#endif
 #pragma unroll
 	for (int gi = 0; gi < RG; gi++) {
 		const uint64_t eq = eqm[gi][q], s1 = s1m[gi][q];
@@ -3100,140 +2818,12 @@ __device__ __forceinline__ void motion_pass (float (*ring)[W + WH_PAD], const in
 	}
 }
 
-/* one DF2 state recurrence (EQ_IIR, src/whirl.cpp:1479-1485) over a sub-block in one lane:
- * temp[i] = (x[i] - a1 temp[i-1]) - a2 temp[i-2], written over x[i].  Element i of the row
- * is r[i], or with WRAP r[(base + i) & m] (a ring window that wraps); read in groups of
- * eight before their temps are written.  The outputs y = (temp b0 + b1 temp[-1]) + b2
- * temp[-2] are lane-parallel afterwards (wh_outputs).  scrub applies the block-end NaN
- * scrub (src/whirl.cpp:1622-1630) to the incoming state first. */
-template <bool WRAP>
-__device__ __forceinline__ void wh_serial (float* r, uint32_t base, uint32_t m, float& z0, float& z1, float a1, float a2, bool scrub)
-{
-	if (scrub) {
-		if (isnan (z0))
-			z0 = 0.f;
-		if (isnan (z1))
-			z1 = 0.f;
-	}
-#if WH_SERIAL_PIPE
-	/* two register sets of eight: the next group's reads are in flight while this group's
-	 * recurrence runs (the groups' elements are distinct, so no read passes a write of its
-	 * own element) */
-	auto ld = [&] (float (&v)[8], int i0) {
-#pragma unroll
-		for (int k = 0; k < 8; k++)
-			v[k] = WRAP ? r[(base + (uint32_t)(i0 + k)) & m] : r[i0 + k];
-	};
-	auto run = [&] (float (&v)[8], int i0) {
-#pragma unroll
-		for (int k = 0; k < 8; k++) {
-			const float t = v[k] - (a1 * z0) - (a2 * z1);
-			z1            = z0;
-			z0            = t;
-			v[k]          = t;
-		}
-#pragma unroll
-		for (int k = 0; k < 8; k++) {
-			if (WRAP)
-				r[(base + (uint32_t)(i0 + k)) & m] = v[k];
-			else
-				r[i0 + k] = v[k];
-		}
-	};
-	float xa[8], xb[8];
-	ld (xa, 0);
-#pragma unroll
-	for (int i0 = 0; i0 < TBF_SUB; i0 += 16) {
-		ld (xb, i0 + 8);
-		run (xa, i0);
-		if (i0 + 16 < TBF_SUB)
-			ld (xa, i0 + 16);
-		run (xb, i0 + 8);
-	}
-#else
-	for (int i0 = 0; i0 < TBF_SUB; i0 += 8) {
-		float xv[8];
-#pragma unroll
-		for (int k = 0; k < 8; k++)
-			xv[k] = WRAP ? r[(base + (uint32_t)(i0 + k)) & m] : r[i0 + k];
-#pragma unroll
-		for (int k = 0; k < 8; k++) {
-			const float t = xv[k] - (a1 * z0) - (a2 * z1);
-			z1            = z0;
-			z0            = t;
-			xv[k]         = t;
-		}
-#pragma unroll
-		for (int k = 0; k < 8; k++) {
-			if (WRAP)
-				r[(base + (uint32_t)(i0 + k)) & m] = xv[k];
-			else
-				r[i0 + k] = xv[k];
-		}
-	}
-#endif
-}
-/* the same with the state in memory */
-template <bool WRAP>
-__device__ __forceinline__ void wh_serial (float* r, uint32_t base, uint32_t m, float* fz, float a1, float a2, bool scrub)
-{
-	float z0 = fz[0], z1 = fz[1];
-	wh_serial<WRAP> (r, base, m, z0, z1, a1, a2, scrub);
-	fz[0] = z0;
-	fz[1] = z1;
-}
-
-/* wh_serial<false> on a 16-B aligned row, 4 samples per LDS read / write (ds_read_b128 /
- * ds_write_b128: 32 LDS instructions per pass instead of 128); the same operations in the
- * same order, the next group of 8 read while this one's recurrence runs */
-__device__ __forceinline__ void wh_serial_v (float* r, float& z0, float& z1, float a1, float a2, bool scrub)
-{
-	if (scrub) {
-		if (isnan (z0))
-			z0 = 0.f;
-		if (isnan (z1))
-			z1 = 0.f;
-	}
-	PRIO_UP ();
-	float4* r4  = (float4*)r;
-	auto    run = [&] (float4 (&v)[2], int g) {
-		float x[8] = {v[0].x, v[0].y, v[0].z, v[0].w, v[1].x, v[1].y, v[1].z, v[1].w};
-#pragma unroll
-		for (int k = 0; k < 8; k++) {
-			const float t = x[k] - (a1 * z0) - (a2 * z1);
-			z1            = z0;
-			z0            = t;
-			x[k]          = t;
-		}
-		r4[2 * g]     = make_float4 (x[0], x[1], x[2], x[3]);
-		r4[2 * g + 1] = make_float4 (x[4], x[5], x[6], x[7]);
-	};
-	float4 xa[2], xb[2];
-	xa[0] = r4[0];
-	xa[1] = r4[1];
-#pragma unroll
-	for (int g = 0; g < TBF_SUB / 8; g += 2) {
-		xb[0] = r4[2 * g + 2];
-		xb[1] = r4[2 * g + 3];
-		run (xa, g);
-		if (g + 2 < TBF_SUB / 8) {
-			xa[0] = r4[2 * g + 4];
-			xa[1] = r4[2 * g + 5];
-		}
-		run (xb, g + 1);
-	}
-	PRIO_DOWN ();
-}
-__device__ __forceinline__ void wh_serial_v (float* r, float* fz, float a1, float a2, bool scrub)
-{
-	float z0 = fz[0], z1 = fz[1];
-	wh_serial_v (r, z0, z1, a1, a2, scrub);
-	fz[0] = z0;
-	fz[1] = z1;
-}
-
-#if WH_SERIAL_REGS
-/* The serial pass fed from registers, one chain per DPP row: chain f runs in lane 16 f and
+/* The serial passes: one DF2 state recurrence (EQ_IIR, src/whirl.cpp:1479-1485) over a
+ * sub-block per chain, temp[i] = (x[i] - a1 temp[i-1]) - a2 temp[i-2], written over x[i].
+ * Element i of a chain's row is row[i], or with WRAP row[(base + i) & m] (a ring window that
+ * wraps).  The outputs y = (temp b0 + b1 temp[-1]) + b2 temp[-2] are lane-parallel
+ * afterwards (wh_output).
+ * The pass is fed from registers, one chain per DPP row: chain f runs in lane 16 f and
  * lane 16 f + j holds samples j, 16 + j, 32 + j, 48 + j of the chain's row (wh_chain_load:
  * four ds_read_b32 for all chains together, one LDS round trip).  Step k takes x[k] from
  * lane 16 f + (k & 15) of register k / 16 through the DPP operand of its subtract
@@ -3304,12 +2894,13 @@ __device__ __forceinline__ f2v wh_pk_mul (f2v a, f2v bp)
 	return p;
 }
 
-/* wh_serial over the chains of mask (bit 16 f: chain f is active), x from wh_chain_load:
- * the same multiplies and subtracts in the same order, temp[n] = (x[n] - a1 temp[n-1]) -
- * a2 temp[n-2].  a2 temp[n-1] is formed beside a1 temp[n-1] by one packed multiply (two
- * IEEE multiplies) and used one step later, so a step is three VALU instructions.  z0, z1,
- * a1, a2, scrub: per lane, read in lanes 16 f.  An inactive chain neither stores nor
- * advances its state. */
+/* the recurrence over the chains of mask (bit 16 f: chain f is active), x from
+ * wh_chain_load: the reference's multiplies and subtracts in its order, temp[n] = (x[n] -
+ * a1 temp[n-1]) - a2 temp[n-2].  a2 temp[n-1] is formed beside a1 temp[n-1] by one packed
+ * multiply (two IEEE multiplies) and used one step later, so a step is three VALU
+ * instructions.  z0, z1, a1, a2, scrub: per lane, read in lanes 16 f; scrub applies the
+ * block-end NaN scrub (src/whirl.cpp:1622-1630) to the incoming state first.  An inactive
+ * chain neither stores nor advances its state. */
 template <bool WRAP>
 __device__ __forceinline__ void wh_serial_regs (float* row, uint32_t base, uint32_t m, const float (&x)[4], const uint64_t mask_,
                                                 float& z0, float& z1, float a1, float a2, bool scrub)
@@ -3328,10 +2919,8 @@ __device__ __forceinline__ void wh_serial_regs (float* row, uint32_t base, uint3
 	float xv[4] = {x[0], x[1], x[2], x[3]};
 	asm volatile ("" : "+v"(xv[0]), "+v"(xv[1]), "+v"(xv[2]), "+v"(xv[3]));
 	PRIO_UP ();
-#if WH_SERIAL_PK
 	const f2v A = {a1, a2};
 	float     q = a2 * s1; /* a2 temp[n-2] */
-#endif
 	/* the group's four temps in the registers its write takes them from; temp[n-1] is read
 	 * where it lies, as the low or the high half of a register pair (wh_pk_mul) */
 	f4v T;
@@ -3342,13 +2931,9 @@ __device__ __forceinline__ void wh_serial_regs (float* row, uint32_t base, uint3
 #pragma unroll
 		for (int k = 0; k < 4; k++) {
 			const float xk = row_shl (xv[g >> 2], 4 * g + k);
-#if WH_SERIAL_PK
 			const f2v p = k == 0 ? wh_pk_mul<true> (A, T.zw) : (k == 1 ? wh_pk_mul<false> (A, N.xy) : (k == 2 ? wh_pk_mul<true> (A, N.xy) : wh_pk_mul<false> (A, N.zw)));
 			N[k]        = (xk - p.x) - q;
 			q           = p.y;
-#else
-			N[k] = xk - (a1 * s0) - (a2 * s1);
-#endif
 			s1 = s0;
 			s0 = N[k];
 		}
@@ -3389,9 +2974,6 @@ __device__ __forceinline__ void whs_serial_regs (float* row, uint32_t base, uint
 		fz[f][1] = z1;
 	}
 }
-#else
-#define WH_FZL(f) (f)
-#endif
 
 /* the filter outputs, lane n = sample n: t = temp[n], z0 / z1 = the state the pass started
  * from (temp[-1], temp[-2]); the neighbours' temps by DPP lane shifts */
@@ -3479,17 +3061,11 @@ __device__ __forceinline__ void wh_reg_load (WhLds<W>& sm, WhReg& R)
 	for (int i = 0; i < 4; i++)
 		R.z[i] = uni (st.z[i]);
 	R.fz0 = R.fz1 = 0.f;
-#if WH_SERIAL_REGS
 	if ((lane & 15) == 0) {
 		R.fz0 = st.fz[lane >> 4][0];
 		R.fz1 = st.fz[lane >> 4][1];
 	}
-#endif
 	if (lane < 4) {
-#if !WH_SERIAL_REGS
-		R.fz0       = st.fz[lane][0];
-		R.fz1       = st.fz[lane][1];
-#endif
 		sm.xf[lane] = st.adx[0][(st.adi[0] + 3 - lane) & 7];
 		sm.x1[lane] = st.adx[1][(st.adi[1] + 3 - lane) & 7];
 		sm.x2[lane] = st.adx[2][(st.adi[2] + 3 - lane) & 7];
@@ -3514,17 +3090,10 @@ __device__ __forceinline__ void wh_reg_store (WhLds<W>& sm, const WhReg& R)
 		for (int i = 0; i < 4; i++)
 			st.z[i] = R.z[i];
 	}
-#if WH_SERIAL_REGS
 	if ((lane & 15) == 0) {
 		st.fz[lane >> 4][0] = R.fz0;
 		st.fz[lane >> 4][1] = R.fz1;
 	}
-#else
-	if (lane < 4) {
-		st.fz[lane][0] = R.fz0;
-		st.fz[lane][1] = R.fz1;
-	}
-#endif
 	if (R.ran && lane < 24) { /* history k = lane / 8, entry j = lane % 8, one lane each */
 		const int    k = lane >> 3, j = lane & 7;
 		const float* h = k == 0 ? sm.xf : (k == 1 ? sm.x1 : sm.x2);
@@ -3591,23 +3160,17 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 	}
 	const double   hornIncr = R.hornIncr, drumIncr = R.drumIncr;
 	const uint32_t WM       = (uint32_t)W - 1u;
-	/* the horn filters' coefficients of this block (the runtime set in the state); serial
-	 * filter coefficients: lane 0 horn A, lane 1 horn B, lanes 2-3 drum shelf */
+	/* the horn filters' coefficients of this block (the runtime set in the state) */
 	float ha[5], hb[5];
 #pragma unroll
 	for (int j = 0; j < 5; j++) {
 		ha[j] = st.prm.hafw[j];
 		hb[j] = st.prm.hbfw[j];
 	}
-	/* a1, a2 of the serial lanes' recurrences: lane 0 horn A, lane 1 horn B, lanes 2-3 drum shelves */
-#if WH_SERIAL_REGS
-	/* chain f in lane 16 f: the coefficients by DPP row */
+	/* a1, a2 of the serial chains' recurrences, by DPP row (chain f in lane 16 f): chain 0
+	 * horn A, chain 1 horn B, chains 2-3 the drum shelves */
 	const float fa0 = lane < 16 ? ha[0] : (lane < 32 ? hb[0] : K.drf[0]);
 	const float fa1 = lane < 16 ? ha[1] : (lane < 32 ? hb[1] : K.drf[1]);
-#else
-	const float fa0 = lane == 0 ? ha[0] : (lane == 1 ? hb[0] : K.drf[0]);
-	const float fa1 = lane == 0 ? ha[1] : (lane == 1 ? hb[1] : K.drf[1]);
-#endif
 
 	for (int sb = 0; sb < TBF_BLK / TBF_SUB; sb++) {
 		const int      n      = lane;
@@ -3624,11 +3187,11 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 		/* DF2 biquads: horn B runs on horn A's output, so A runs one sub-block ahead and
 		 * one serial pass advances A over the next sub-block (chain 0), B over this one into
 		 * xf (chain 1) and the drum shelves over this one's ring outputs, in place (chains 2,
-		 * 3); chain f runs in lane WH_FZL (f).  A's own pass over this sub-block runs only when it is not ahead (launch
-		 * start, after a bypassed block or a new coefficient set). */
+		 * 3); chain f runs in lane WH_FZL (f).  A's own pass over this sub-block runs only
+		 * when it is not ahead (launch start, after a bypassed block or a new coefficient
+		 * set). */
 		const int  ap    = R.ap;
 		const bool aNext = sb + 1 < TBF_BLK / TBF_SUB || hasNext;
-#ifndef WH_ABL_HORN
 		if (WH_RARE (!R.aReady))
 			sm.ab[ap ^ 1][n] = xin;
 		if (aNext)
@@ -3636,23 +3199,15 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 		wave_sync ();
 		if (WH_RARE (!R.aReady)) {
 			const float z0 = rlf (R.fz0, 0), z1 = rlf (R.fz1, 0);
-#ifndef WH_NO_SERIAL
-#if WH_SERIAL_REGS
 			{ /* horn A alone, over this sub-block: every row of lanes loads its row, chain 0 is the active one */
 				float xc[4];
 				wh_chain_load<false> (sm.ab[ap ^ 1], 0u, ~0u, xc);
 				wh_serial_regs<false> (sm.ab[ap ^ 1], 0u, ~0u, xc, 1ull, R.fz0, R.fz1, ha[0], ha[1], false);
 			}
-#else
-			if (lane == 0)
-				wh_serial_v (sm.ab[ap ^ 1], R.fz0, R.fz1, ha[0], ha[1], false);
-#endif
-#endif
 			wave_sync ();
 			sm.ab[ap ^ 1][n] = wh_output (sm.ab[ap ^ 1][n], z0, z1, ha);
 			wave_sync ();
 		}
-#endif
 		/* the states the pass starts from (horn A's scrubbed when it crosses into the next block) */
 		const bool scrubA = sb + 1 == TBF_BLK / TBF_SUB;
 		float      zs[4][2];
@@ -3667,15 +3222,10 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 		}
 		const uint32_t wb   = R.outpos & WM; /* the drum rings' window: wave-uniform */
 		const bool     wrap = wb + TBF_SUB > (uint32_t)W;
-#if WH_SERIAL_REGS && !defined(WH_NO_SERIAL)
 		{
 			/* chain f's row in the lanes of DPP row f; horn A's chain is inactive when there
 			 * is no next sub-block */
-#ifdef WH_ABL_HORN /* timing experiment only (wrong output): horn filters A, B not run in k_whirl */
-			const uint64_t chains = 0x0001000100000000ull;
-#else
 			const uint64_t chains = 0x0001000100010000ull | (aNext ? 1ull : 0ull);
-#endif
 			float* row = lane < 16 ? sm.ab[ap] : (lane < 32 ? sm.ab[ap ^ 1] : sm.wring[lane >> 4]);
 			float  xc[4];
 			if (WH_RARE (wrap)) {
@@ -3689,31 +3239,12 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 				wh_serial_regs<false> (row, 0u, ~0u, xc, chains, R.fz0, R.fz1, fa0, fa1, lane == 0 && scrubA);
 			}
 		}
-#else
-#ifdef WH_NO_SERIAL /* timing experiment only (wrong output): k_whirl without its serial filter passes */
-		if (false) {
-#elif defined(WH_ABL_HORN) /* timing experiment only (wrong output): horn filters A, B not run in k_whirl */
-		if (lane >= 2 && lane < 4) {
-#else
-		if (lane < 4 && (lane > 0 || aNext)) {
-#endif
-			float* row = lane == 0 ? sm.ab[ap] : (lane == 1 ? sm.ab[ap ^ 1] : sm.wring[lane]);
-			if (WH_RARE (wrap))
-				wh_serial<true> (row, lane < 2 ? 0u : wb, lane < 2 ? ~0u : WM, R.fz0, R.fz1, fa0, fa1, lane == 0 && scrubA);
-			else
-				wh_serial_v (row + (lane < 2 ? 0u : wb), R.fz0, R.fz1, fa0, fa1, lane == 0 && scrubA);
-		}
-#endif
 		wave_sync ();
 		/* the filter outputs: horn B -> xf, horn A of the next sub-block in place, the drum
 		 * shelves' (then the ring slots are cleared) */
-#ifdef WH_ABL_HORN
-		sm.xf[4 + n] = xin;
-#else
 		sm.xf[4 + n] = wh_output (sm.ab[ap ^ 1][n], zs[1][0], zs[1][1], hb);
 		if (aNext)
 			sm.ab[ap][n] = wh_output (sm.ab[ap][n], zs[0][0], zs[0][1], ha);
-#endif
 		const float dL = wh_output (sm.wring[2][o], zs[2][0], zs[2][1], K.drf);
 		const float dR = wh_output (sm.wring[3][o], zs[3][0], zs[3][1], K.drf);
 		sm.wring[2][o] = 0.f;
@@ -3772,7 +3303,7 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 		 * table loads in flight together), then each ring's ordered adds ---- */
 		/* a ring group's table positions and table loads need the rotor angles alone, and their
 		 * registers are free once the group's motions are formed: the next group's loads go out
-		 * then, ahead of this group's ring passes, and fly under them (WH_NEXT_TABLES) */
+		 * then, ahead of this group's ring passes, and fly under them */
 		float h1v[WH_RG][3];
 		f2u   dpv[WH_RG][3];
 		f4u   b4v[2][3];
@@ -3814,7 +3345,7 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 		for (int r0 = 0; r0 < 4; r0 += WH_RG) {
 			int   mu[WH_RG][3];
 			float ma[WH_RG][3], mb[WH_RG][3];
-			if (!(WH_NEXT_TABLES && r0 > 0))
+			if (r0 == 0)
 				tables (r0);
 			/* behind the table loads: the next block's input (used from the second
 			 * sub-block on; the second sub-block loads it again, so that every sub-block
@@ -3857,7 +3388,7 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 					mb[gi][q]      = qq;
 				}
 			}
-			if (WH_NEXT_TABLES && r0 + WH_RG < 4)
+			if (r0 + WH_RG < 4)
 				tables (r0 + WH_RG);
 			/* fast path preconditions (wave votes), per ring: each motion's slot
 			 * non-decreasing in n with groups of <= 2 equal slots, and the ring's motions
@@ -4309,7 +3840,7 @@ __device__ void whirl_horn (const tbf_launch& P, WhLds<W>& sm, const bool bypass
 		ha[j] = sgpr_f (st.prm.hafw[j]);
 		hb[j] = sgpr_f (st.prm.hbfw[j]);
 	}
-	/* serial lanes: 0 horn A (over the next sub-block), 1 horn B (over this one) */
+	/* serial chains: 0 (lane 0) horn A (over the next sub-block), 1 (lane 16) horn B (over this one) */
 	const float fa0 = lane == 0 ? ha[0] : hb[0];
 	const float fa1 = lane == 0 ? ha[1] : hb[1];
 	for (int sb = 0; sb < TBF_BLK / TBF_SUB; sb++) {
@@ -4336,12 +3867,7 @@ __device__ void whirl_horn (const tbf_launch& P, WhLds<W>& sm, const bool bypass
 		wave_sync ();
 		if (WH_RARE (!sm.aReady)) {
 			const float z0 = st.fz[0][0], z1 = st.fz[0][1];
-#if WH_SERIAL_REGS
 			whs_serial_regs<false> (sm.ab[ap ^ 1], 0u, ~0u, 1ull, st.fz, ha[0], ha[1], false);
-#else
-			if (lane == 0)
-				wh_serial_v (sm.ab[ap ^ 1], st.fz[0], ha[0], ha[1], false);
-#endif
 			wave_sync ();
 			sm.ab[ap ^ 1][n] = wh_output (sm.ab[ap ^ 1][n], z0, z1, ha);
 			wave_sync ();
@@ -4357,13 +3883,8 @@ __device__ void whirl_horn (const tbf_launch& P, WhLds<W>& sm, const bool bypass
 			zs[0][0] = isnan (zs[0][0]) ? 0.f : zs[0][0];
 			zs[0][1] = isnan (zs[0][1]) ? 0.f : zs[0][1];
 		}
-#if WH_SERIAL_REGS
 		whs_serial_regs<false> (lane < 16 ? sm.ab[ap] : sm.ab[ap ^ 1], 0u, ~0u, 0x10000ull | (aNext ? 1ull : 0ull), st.fz, fa0, fa1,
 		                        lane == 0 && scrubA);
-#else
-		if (lane < 2 && (lane > 0 || aNext))
-			wh_serial_v (lane == 0 ? sm.ab[ap] : sm.ab[ap ^ 1], st.fz[lane], fa0, fa1, lane == 0 && scrubA);
-#endif
 		wave_sync ();
 		sm.xf[4 + n] = wh_output (sm.ab[ap ^ 1][n], zs[1][0], zs[1][1], hb);
 		if (aNext)
@@ -4454,11 +3975,10 @@ __device__ void whirl_drum (const tbf_launch& P, WhLds<W>& sm, const bool bypass
 		const int32_t  unwrap = (int32_t)(opos + (uint32_t)n - outpos);
 		const float    xin    = (float)((double)(sb == 0 ? in0 : in1) + 1e-14);
 		const uint32_t o      = outpos & WM;
-		/* the shelves over this sub-block's ring outputs, in place (lanes 0, 1: DL, DR) */
+		/* the shelves over this sub-block's ring outputs, in place */
 		const float z20 = st.fz[2][0], z21 = st.fz[2][1], z30 = st.fz[3][0], z31 = st.fz[3][1];
 		const uint32_t wb   = opos & WM; /* wave-uniform */
 		const bool     wrap = wb + TBF_SUB > (uint32_t)W;
-#if WH_SERIAL_REGS
 		{ /* chains 0, 1 (lanes 0, 16): DL, DR */
 			float* row = sm.wring[lane < 16 ? 2 : 3];
 			if (WH_RARE (wrap)) /* (outpos advances by whole sub-blocks from 0, so no state reaches this) */
@@ -4466,15 +3986,6 @@ __device__ void whirl_drum (const tbf_launch& P, WhLds<W>& sm, const bool bypass
 			else
 				whs_serial_regs<false> (row + wb, 0u, ~0u, 0x10001ull, &st.fz[2], K.drf[0], K.drf[1], false);
 		}
-#else
-		if (lane < 2) {
-			float* row = sm.wring[2 + lane];
-			if (WH_RARE (wrap))
-				wh_serial<true> (row, wb, WM, st.fz[2 + lane], K.drf[0], K.drf[1], false);
-			else
-				wh_serial_v (row + wb, st.fz[2 + lane], K.drf[0], K.drf[1], false);
-		}
-#endif
 		wave_sync ();
 		const float dL = wh_output (sm.wring[2][o], z20, z21, K.drf);
 		const float dR = wh_output (sm.wring[3][o], z30, z31, K.drf);
@@ -4578,16 +4089,10 @@ k_whirl_split (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const
 		const bool  byp     = rl (byv, blk_lane ((int)blk)) != 0;
 		const int   rev     = rl (rvv, blk_lane ((int)blk));
 		const float* inNext = inBase + (size_t)(more ? blk + 1 : blk) * TBF_BLK;
-#ifndef WHS_ONLY
 		if (horn)
 			whirl_horn<W> (P, sm, byp, rev, K, c0, c1, inNext, n0, n1, hasNext, oL, oR, pend, opos);
 		else
 			whirl_drum<W> (P, sm, byp, rev, K, c0, c1, inNext, n0, n1, opos, clr);
-#elif WHS_ONLY == 1
-		whirl_horn<W> (P, sm, byp, rev, K, c0, c1, inNext, n0, n1, hasNext, oL, oR, pend, opos);
-#else
-		whirl_drum<W> (P, sm, byp, rev, K, c0, c1, inNext, n0, n1, opos, clr);
-#endif
 		c0 = n0;
 		c1 = n1;
 	}

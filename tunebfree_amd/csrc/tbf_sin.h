@@ -101,17 +101,10 @@ __device__ __forceinline__ double tbf_sin_small (double x, double a, double n)
 	return __builtin_bit_cast (double, r ^ f);
 }
 
-#ifndef SIN_EXPECT
-#define SIN_EXPECT 1 /* the first fast path (every lane's quadrant 0) likely, the library call for huge
-                      * arguments unlikely: the compiler lays the common path out as the fall-through */
-#endif
-#if SIN_EXPECT
+/* the first fast path (every lane's quadrant 0) likely, the library call for huge arguments
+ * unlikely: the compiler lays the common path out as the fall-through */
 #define TBF_LIKELY(x) __builtin_expect (!!(x), 1)
 #define TBF_UNLIKELY(x) __builtin_expect (!!(x), 0)
-#else
-#define TBF_LIKELY(x) (x)
-#define TBF_UNLIKELY(x) (x)
-#endif
 #define TBF_N(a) __builtin_rint ((a) * TBF_D (0x3FE45F306DC9C883))
 #define TBF_SMALL(a) ((a) < TBF_D (0x41D0000000000000)) /* 2^30; false for NaN (OCML's test) */
 
