@@ -291,7 +291,44 @@ struct TgCache {
 	bool     on;
 	int      np;
 	bool     anyEnv;
+	uint32_t live; /* the program's live-bus mask (tg_bus_mask) */
 };
+
+/* The live-bus mask of a program: bit 0 the swell bus, bit 1 percussion, bit 2 vibrato.  A
+ * bus is live if some entry feeds it -- a gain (sg / pg / vg; of an envelope entry also nsg /
+ * npg / nvg) that is not zero by its bit pattern: -0.f counts as zero, a NaN as live -- and
+ * the block's routing reads its sum (vb only under routing & 0x03, pc and st.pz only under
+ * routing & 0x0C).  The interpreter leaves a dead bus out (stage_tonegen).
+ * tg_entry_bits: one entry's bits, a = {wheel | env << 16 | row << 24, sg, pg, vg}, b = {nsg,
+ * npg, nvg, pad}; bit 3: a zero gain of the entry is -0.f. */
+#define TG_BUS_SW 1u
+#define TG_BUS_PC 2u
+#define TG_BUS_VB 4u
+#define TG_BUS_ALL 7u
+__device__ __forceinline__ uint32_t tg_entry_bits (const uint4 a, const uint4 b)
+{
+	const uint32_t em = ((a.x >> 16) & 0xffu) ? 0xffffffffu : 0u; /* the next gains count on an envelope entry */
+	const uint32_t s = a.y | (b.x & em), p = a.z | (b.y & em), v = a.w | (b.z & em);
+	const bool     ls = (s << 1) != 0, lp = (p << 1) != 0, lv = (v << 1) != 0;
+	return (ls ? TG_BUS_SW : 0u) | (lp ? TG_BUS_PC : 0u) | (lv ? TG_BUS_VB : 0u) |
+	       (((!ls && s) || (!lp && p) || (!lv && v)) ? 8u : 0u);
+}
+
+/* the lanes' entry bits reduced over the wave, under the block's routing: wave-uniform.  A
+ * dead bus is given the sign its sum would have had with every gain +0.f (stage_tonegen); a
+ * program with a -0.f gain, which no control path writes, takes the full loop instead. */
+__device__ __forceinline__ uint32_t tg_bus_mask (uint32_t bits, uint32_t routing)
+{
+	uint32_t m = (__any (bits & TG_BUS_SW) ? TG_BUS_SW : 0u) | (__any (bits & TG_BUS_PC) ? TG_BUS_PC : 0u) |
+	             (__any (bits & TG_BUS_VB) ? TG_BUS_VB : 0u);
+	if (!(routing & 0x0C))
+		m &= ~TG_BUS_PC;
+	if (!(routing & 0x03))
+		m &= ~TG_BUS_VB;
+	if (__any (bits & 8u))
+		m = TG_BUS_ALL;
+	return (uint32_t)__builtin_amdgcn_readfirstlane ((int)m);
+}
 
 /* The positions live in LDS (sm.cbase / cend / clen): held in the lanes, they were spilled
  * around the interpreter, and each block's reload from scratch waited (vmcnt) for the
@@ -303,7 +340,8 @@ __device__ __forceinline__ void tg_cache_load (TgCache& c, const tbf_launch& P, 
 	const tbf_prog_entry* prog = P.prog + G.prog_off + 1;
 	c.np                       = (int)P.prog[G.prog_off].pad;
 	c.on                       = c.np <= 2 * NL;
-	int env                    = 0;
+	int      env               = 0;
+	uint32_t bits              = 0;
 #pragma unroll
 	for (int k = 0; k < 2; k++) {
 		const int e = lane + k * NL;
@@ -313,9 +351,13 @@ __device__ __forceinline__ void tg_cache_load (TgCache& c, const tbf_launch& P, 
 			sm.cend[e]       = off + len;
 			sm.clen[e]       = len;
 			env |= prog[e].env != 0;
+			bits |= tg_entry_bits (((const uint4*)(prog + e))[0], ((const uint4*)(prog + e))[1]);
 		}
 	}
 	c.anyEnv = __any (env);
+	/* (a program too long for the cache is also too long for the LDS-staged loop, the one
+	 * with bus variants) */
+	c.live = c.on ? tg_bus_mask (bits, G.routing) : TG_BUS_ALL;
 }
 
 __device__ __forceinline__ void tg_cache_store (const TgCache& c, TgLds& sm, const tbf_launch& P, const tbf_seg_ctl& G,
@@ -358,6 +400,7 @@ __device__ __forceinline__ void stage_tonegen (const tbf_launch& P, TgLds& sm, c
 	 * per 512 blocks, profiles/r06/s23_tg_lds_all). */
 	const bool lp      = np <= TG_PCAP;
 	bool       anyEnv;
+	uint32_t   live; /* the buses the block computes (tg_bus_mask); wave-uniform */
 	if (tc && tc->on) {
 		/* the launch's program, its entries' bank positions cached in LDS (TgCache) */
 #pragma unroll
@@ -376,8 +419,10 @@ __device__ __forceinline__ void stage_tonegen (const tbf_launch& P, TgLds& sm, c
 			}
 		}
 		anyEnv = tc->anyEnv;
+		live   = tc->live;
 	} else {
-		int envHere = 0;
+		int      envHere = 0;
+		uint32_t bits    = 0;
 		for (int e = lane; e < np; e += NL) {
 			const uint32_t w   = prog[e].wheel;
 			const uint32_t pos = st.pos[w];
@@ -390,9 +435,11 @@ __device__ __forceinline__ void stage_tonegen (const tbf_launch& P, TgLds& sm, c
 				sm.u.ent.g[e] = make_float4 (__uint_as_float (a.y), __uint_as_float (a.z), __uint_as_float (a.w), __uint_as_float (b.x));
 				sm.u.ent.h[e] = make_float2 (__uint_as_float (b.y), __uint_as_float (b.z));
 				sm.u.ent.er[e] = a.x >> 16; /* env | row << 8 */
+				bits |= tg_entry_bits (a, b);
 			}
 		}
 		anyEnv = __any (envHere);
+		live   = lp ? tg_bus_mask (bits, G.routing) : TG_BUS_ALL; /* this block's program and routing */
 	}
 	wave_sync ();
 	/* main loop in program order (the adds keep the reference's order); a lane holds
@@ -401,9 +448,46 @@ __device__ __forceinline__ void stage_tonegen (const tbf_launch& P, TgLds& sm, c
 	 * loops have no data-dependent branch, so the unrolled entries' loads are in flight
 	 * together.  The sums start at -0.f: -0 + a == a for every a, so the first entry's add
 	 * equals the reference's copy (CR_CPY). */
+	/* A variant M of the loops leaves out the buses outside M (tg_bus_mask): their multiplies
+	 * and adds, and the gain words only they read.  The sum it skips is -0 + sum of x_e (+0),
+	 * every term a zero with x_e's sign (also under an envelope: +0 + ev (+0 - +0) is +0 for
+	 * the tables' finite ev; the bank's samples are finite): -0.f where every entry's sample
+	 * is negative or -0.f, +0.f otherwise.  That sign reaches s = x + vout, p and sm.vin, so
+	 * the variant keeps it: sgn is the signed-integer maximum of the samples' words, starting
+	 * at -0.f's, whose sign bit is the AND of theirs (one v_max3_i32 per sample and two
+	 * entries), and the dead buses take sgn's sign bit as their value. */
 	f2v  sw = {-0.f, -0.f}, vb = {-0.f, -0.f}, pc = {-0.f, -0.f};
-	auto loops = [&] (auto LP) {
-		constexpr bool L = decltype (LP)::value;
+	int  sgn0 = (int)0x80000000, sgn1 = (int)0x80000000;
+	auto loops = [&] (auto LP, auto MC) {
+		constexpr bool     L = decltype (LP)::value;
+		constexpr uint32_t M = decltype (MC)::value;
+		constexpr bool     SW = (M & TG_BUS_SW) != 0, PC = (M & TG_BUS_PC) != 0, VB = (M & TG_BUS_VB) != 0;
+		/* entry x of gains g: a plain entry's terms, an envelope entry's */
+		auto plain = [&] (const f2v x, const float (&g)[6]) {
+			if constexpr (SW)
+				sw = sw + x * g[0];
+			if constexpr (VB)
+				vb = vb + x * g[2];
+			if constexpr (PC)
+				pc = pc + x * g[1];
+			if constexpr (M != TG_BUS_ALL) {
+				sgn0 = max (sgn0, __float_as_int (x.x));
+				sgn1 = max (sgn1, __float_as_int (x.y));
+			}
+		};
+		auto envel = [&] (const f2v x, const f2v ev, const float (&g)[6]) {
+			/* envelope entry x * (g + e (ng - g)) (src/tonegen.cpp:3640-3662) */
+			if constexpr (SW)
+				sw = sw + x * (g[0] + (ev * (g[3] - g[0])));
+			if constexpr (VB)
+				vb = vb + x * (g[2] + (ev * (g[5] - g[2])));
+			if constexpr (PC)
+				pc = pc + x * (g[1] + (ev * (g[4] - g[1])));
+			if constexpr (M != TG_BUS_ALL) {
+				sgn0 = max (sgn0, __float_as_int (x.x));
+				sgn1 = max (sgn1, __float_as_int (x.y));
+			}
+		};
 		/* entry e's gains {sg, pg, vg, nsg, npg, nvg} and env | row << 8 */
 		auto ent = [&] (int e, float (&g)[6], uint32_t& er) {
 			if constexpr (L) {
@@ -453,16 +537,10 @@ __device__ __forceinline__ void stage_tonegen (const tbf_launch& P, TgLds& sm, c
 				float    g[6];
 				uint32_t er;
 				ent (e + k, g, er);
-				if (EN && (er & 0xffu)) {
-					/* envelope entry x * (g + e (ng - g)) (src/tonegen.cpp:3640-3662) */
-					sw = sw + G.xs[k] * (g[0] + (G.evs[k] * (g[3] - g[0])));
-					vb = vb + G.xs[k] * (g[2] + (G.evs[k] * (g[5] - g[2])));
-					pc = pc + G.xs[k] * (g[1] + (G.evs[k] * (g[4] - g[1])));
-				} else { /* x * g (3667-3685) */
-					sw = sw + G.xs[k] * g[0];
-					vb = vb + G.xs[k] * g[2];
-					pc = pc + G.xs[k] * g[1];
-				}
+				if (EN && (er & 0xffu))
+					envel (G.xs[k], G.evs[k], g);
+				else /* x * g (3667-3685) */
+					plain (G.xs[k], g);
 			}
 		};
 		/* one entry: the remainder */
@@ -476,15 +554,9 @@ __device__ __forceinline__ void stage_tonegen (const tbf_launch& P, TgLds& sm, c
 			if (EN && (er & 0xffu)) {
 				const uint32_t env = er & 0xffu, row = (er >> 8) & 7u;
 				const float*   ep  = (env == 2 ? T->releaseEnv[row] : T->attackEnv[row]);
-				const f2v      ev  = f2v {ep[lane], ep[lane + NL]};
-				sw                 = sw + x * (g[0] + (ev * (g[3] - g[0])));
-				vb                 = vb + x * (g[2] + (ev * (g[5] - g[2])));
-				pc                 = pc + x * (g[1] + (ev * (g[4] - g[1])));
-			} else {
-				sw = sw + x * g[0];
-				vb = vb + x * g[2];
-				pc = pc + x * g[1];
-			}
+				envel (x, f2v {ep[lane], ep[lane + NL]}, g);
+			} else
+				plain (x, g);
 		};
 		auto run = [&] (auto EC) {
 			const int nG = np / K;
@@ -508,11 +580,30 @@ __device__ __forceinline__ void stage_tonegen (const tbf_launch& P, TgLds& sm, c
 			run (BoolC<true> {});
 		else
 			run (BoolC<false> {});
+		if constexpr (M != TG_BUS_ALL) {
+			const f2v z = {__int_as_float (sgn0 & (int)0x80000000), __int_as_float (sgn1 & (int)0x80000000)};
+			if constexpr (!SW)
+				sw = z;
+			if constexpr (!VB)
+				vb = z;
+			if constexpr (!PC)
+				pc = z;
+		}
 	};
-	if (lp)
-		loops (BoolC<true> {});
+	/* The LDS-staged loop has a variant for each mask with one dead bus (swell: the Jazz 1
+	 * registration with the upper manual on the vibrato; vibrato; percussion); a mask with
+	 * two or three dead buses takes one that computes a superset of its buses, a program
+	 * longer than TG_PCAP the full loop. */
+	if (!lp)
+		loops (BoolC<false> {}, IntC<TG_BUS_ALL> {});
+	else if (live == TG_BUS_ALL)
+		loops (BoolC<true> {}, IntC<TG_BUS_ALL> {});
+	else if (!(live & TG_BUS_SW))
+		loops (BoolC<true> {}, IntC<TG_BUS_PC | TG_BUS_VB> {});
+	else if (!(live & TG_BUS_VB))
+		loops (BoolC<true> {}, IntC<TG_BUS_SW | TG_BUS_PC> {});
 	else
-		loops (BoolC<false> {});
+		loops (BoolC<true> {}, IntC<TG_BUS_SW | TG_BUS_VB> {});
 	if (np == 0) /* no program: the buses stay cleared (+0) */
 		sw = vb = pc = f2v{0.f, 0.f};
 	wave_sync (); /* the entry table is overwritten below */
