@@ -61,6 +61,11 @@ extern "C" {
 #define TBF_CHAIN_TONEGEN 1  /* oscGenerateFragment only, L = R = tonegen output */
 #define TBF_CHAIN_TAP_PREAMP 2 /* parity tap: L = R = preamp output */
 #define TBF_CHAIN_TAP_REVERB 3 /* parity tap: L = R = reverb output */
+/* effects-only chains: the caller's audio instead of the tone generator's, through the
+ * tbf_process* calls below (the tbf_render* calls and tbf_synth_sound return -22 on them) */
+#define TBF_CHAIN_FX 4            /* caller audio -> overdrive -> reverb -> whirl */
+#define TBF_CHAIN_FX_TAP_PREAMP 5 /* parity tap: L = R = preamp output of the caller's audio */
+#define TBF_CHAIN_FX_TAP_REVERB 6 /* parity tap: L = R = reverb output */
 
 typedef struct tbf_engine tbf_engine;
 
@@ -223,6 +228,32 @@ int tbf_midi_control_id (const char* fn);
 int tbf_render_events (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, float* d_outL,
                        float* d_outR, uint64_t stride, void* stream);
 
+/* ---- effects-only chains (TBF_CHAIN_FX*): the caller's audio through the effects ----
+ * preamp -> b_reverb::reverb -> whirlProc3 of the reference on caller-supplied mono audio,
+ * one row per instance, with the instance's own effect state (the same srand (seed) ->
+ * allocReverb -> allocPreamp as a full-chain instance of that seed) and control surface:
+ * tbf_set_param, tbf_midi_control, cfg keys and events act as on the full chain, and what
+ * faces the tone generator (notes, drawbars, vibrato, percussion, programmes, retune) is
+ * accepted and inaudible.  The tone generator never runs and has no stage buffer.
+ * Instance i reads in[i * in_stride + 0 .. nblocks*128); in_stride >= nblocks*128, odd
+ * strides and any 4-byte-aligned pointer are valid, and nothing outside [0, nblocks*128) of a
+ * row is read.  Inputs are finite floats; subnormals and -0.f pass as through the
+ * reference.  The input range must not overlap either output range (-22).  Events apply at
+ * block boundaries, as in tbf_render_events (no frame-granular FIFO: tbf_synth_sound has no
+ * counterpart here).  On an engine of another chain mode these calls return -22, on a
+ * host-only engine of an effects-only chain -19. */
+/* host buffers, synchronous */
+int tbf_process (tbf_engine* e, uint32_t nblocks, const float* in, uint64_t in_stride, float* outL, float* outR,
+                 uint64_t stride);
+/* device memory on `stream`, as tbf_render_device, and the same ordering extended to the
+ * input: d_in must be complete when `stream` reaches this call (the first stage of every
+ * call waits for `stream`), and may be overwritten once `stream` has passed it */
+int tbf_process_device (tbf_engine* e, uint32_t nblocks, const float* d_in, uint64_t in_stride, float* d_outL,
+                        float* d_outR, uint64_t stride, void* stream);
+/* the same with events, as tbf_render_events */
+int tbf_process_events (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, const float* d_in,
+                        uint64_t in_stride, float* d_outL, float* d_outR, uint64_t stride, void* stream);
+
 int tbf_synchronize (tbf_engine* e);
 /* Which exact-but-slow paths the kernels took since the engine's first render (cumulative,
  * informational; the results are bit-identical either way).  Waits for the engine's
@@ -264,7 +295,8 @@ int tbf_debug_front_chunks (const tbf_engine* e, uint64_t* device_chunks, uint64
 /* test hook: launches of each kernel variant since the engine was created, counted on the
  * host where the engine launches a stage, from the fields the launch switches on.  Writes
  * min (cap, TBF_LAUNCH_KINDS) counts in the order below and returns TBF_LAUNCH_KINDS; a
- * host engine (device -1) launches nothing and reports zeros. */
+ * host engine (device -1) launches nothing and reports zeros; an effects-only engine
+ * (TBF_CHAIN_FX*) reports zero for both k_tonegen kinds. */
 enum {
 	TBF_LAUNCH_TONEGEN        = 0, /* k_tonegen, one block range per instance */
 	TBF_LAUNCH_TONEGEN_RANGES = 1, /* k_tonegen, an instance's blocks split over several waves */

@@ -33,6 +33,13 @@
 
 extern "C" int tbf_launch_stage (const tbf_launch* P, int k, hipStream_t stream);
 extern "C" int tbf_chain_stages (uint32_t chain);
+extern "C" int tbf_chain_first_stage (uint32_t chain);
+extern "C" uint32_t tbf_chain_kernels (uint32_t chain);
+
+/* an effects-only chain (TBF_CHAIN_FX*): the caller's audio in place of the tone generator's */
+static bool chainFx (uint32_t chain) { return tbf_chain_first_stage (chain) > 0; }
+/* whether the chain runs the reverb stages (and so holds their stage buffers) */
+static bool chainReverb (uint32_t chain) { return tbf_chain_stages (chain) > 2; }
 extern "C" int tbf_launch_tgctl (const tbf_launch* P, hipStream_t stream);
 extern "C" int tbf_launch_front (const tbf_launch* P, hipStream_t stream);
 extern "C" int tbf_launch_calibrate (int op, void* buf, uint64_t n, hipStream_t s);
@@ -546,6 +553,7 @@ int tbf_engine_destroy (tbf_engine* e)
 	e->err.release ();
 	e->outL.release ();
 	e->outR.release ();
+	e->extBuf.release ();
 	e->mid0.release ();
 	e->mid1.release ();
 	e->mid2.release ();
@@ -2058,9 +2066,9 @@ static size_t stageFootprint (const tbf_engine* e, size_t n, uint32_t blocks)
 {
 	static const int prod[5] = {0, 1, 2, 3, 4}, rd[5][2] = {{1, -1}, {2, 4}, {3, -1}, {4, -1}, {5, -1}};
 	static const size_t per[5] = {8, 4, 16, 16, 4};
-	const bool rv = e->cfg.chain_mode != TBF_CHAIN_TONEGEN && e->cfg.chain_mode != TBF_CHAIN_TAP_PREAMP;
+	const bool rv = chainReverb (e->cfg.chain_mode), fx = chainFx (e->cfg.chain_mode);
 	size_t sum = 0;
-	for (int b = 0; b < 5; b++) {
+	for (int b = fx ? 1 : 0; b < 5; b++) { /* an effects-only chain has no mid0 */
 		if (b > 0 && !rv)
 			break;
 		bool dbl = false;
@@ -2077,7 +2085,8 @@ static int stageBuffers (tbf_engine* e, uint32_t n, uint32_t nblocks, hipStream_
 	while (want < nblocks && want < e->steadyChunk)
 		want *= 2;
 	want = std::min (want, std::max (e->steadyChunk, (uint32_t)TBF_CHUNK));
-	if (e->stageN == n && e->stageBlocks >= want && e->mid0.p)
+	const bool fx = chainFx (e->cfg.chain_mode); /* no mid0: stage 1 reads the caller's rows */
+	if (e->stageN == n && e->stageBlocks >= want && (fx || e->mid0.p))
 		return 0;
 	/* every launch that may read the old buffers: pipelined stages and the caller's stream
 	 * (the engine's own streams and s; no device-wide synchronization, which would also
@@ -2093,12 +2102,12 @@ static int stageBuffers (tbf_engine* e, uint32_t n, uint32_t nblocks, hipStream_
 			dbl = dbl || (r >= 0 && e->grp[r] != e->grp[prod[b]]);
 		e->stageDbl[b] = dbl;
 	}
-	const bool rv = e->cfg.chain_mode != TBF_CHAIN_TONEGEN && e->cfg.chain_mode != TBF_CHAIN_TAP_PREAMP;
+	const bool rv = chainReverb (e->cfg.chain_mode);
 	auto       k  = [&] (int b) { return (size_t)(e->stageDbl[b] ? 2 : 1); };
 	for (uint32_t blocks = want;;) {
 		e->mid0.release (), e->mid1.release (), e->mid2.release (), e->rvA.release (), e->rvB.release ();
 		const size_t need = (size_t)n * blocks * TBF_BLK;
-		const bool   ok   = !e->mid0.ensure (k (0) * 2 * need) &&
+		const bool   ok   = (fx || !e->mid0.ensure (k (0) * 2 * need)) &&
 		                (!rv || (!e->mid1.ensure (k (1) * need) && !e->mid2.ensure (k (4) * need) &&
 		                         !e->rvA.ensure (k (2) * 2 * need) && !e->rvB.ensure (k (3) * 2 * need)));
 		if (ok) {
@@ -2185,6 +2194,7 @@ static int renderImpl (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, ui
 {
 	e->callS   = s;
 	e->outWait = false;
+	e->inWait  = false;
 	const int rc = renderBody (e, nblocks, dL, dR, stride, s, ev, nev);
 	if (e->defPending) { /* an error return between two chunks */
 		(void)issueDeferred (e);
@@ -2202,6 +2212,8 @@ static int renderBody (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, ui
 	const uint32_t n = (uint32_t)e->inst.size ();
 	if (n == 0 || nblocks == 0)
 		return 0;
+	if (chainFx (e->cfg.chain_mode) && !e->extIn)
+		return fail (-5, "internal: an effects-only render without an input");
 	if (!e->retuned.empty ()) {
 		/* retuned instances (tbf_instance_retune): fresh tone-generator state and the new
 		 * template id, after every launch so far, before this call's first block */
@@ -2252,7 +2264,9 @@ static int renderBody (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, ui
 	P.nInst     = n;
 	P.wringLen  = e->wringLen;
 	P.statorInc = e->statorInc;
-	P.chain     = e->cfg.chain_mode;
+	P.chain     = tbf_chain_kernels (e->cfg.chain_mode);
+	P.ext       = e->extIn;
+	P.extStride = e->extStride;
 	P.slabLen   = e->slabLen;
 	P.errFlags  = e->err.p;
 	P.dbg       = e->cfg.debug_flags;
@@ -2278,7 +2292,9 @@ static int renderBody (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, ui
 	 * caller's stream after joining.  With tbf_debug_kernel_times on, each launch is
 	 * bracketed by events on its own stream (durations then include the overlap with the
 	 * other streams' kernels). */
-	const bool   pipe  = e->pipeline && e->cfg.chain_mode == TBF_CHAIN_FULL && !e->timeSerial;
+	const bool   pipe  = e->pipeline && P.chain == TBF_CHAIN_FULL && !e->timeSerial;
+	/* an effects-only chain starts at stage 1, which reads the caller's rows */
+	const int    st0   = tbf_chain_first_stage (e->cfg.chain_mode);
 	/* k_rv_pre ahead (tbf_engine.preAhead): with the default stage groups only */
 	static const int defGrp[TBF_NSTAGES] = {0, 0, 1, 1, 1, 2};
 	const bool       aheadOn = e->preAhead && pipe && std::equal (defGrp, defGrp + TBF_NSTAGES, e->grp);
@@ -2556,7 +2572,7 @@ static int renderBody (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, ui
 			return fail (-5, "internal: a chunk with control deltas longer than 64 blocks");
 		const bool     piped   = pipe && (!delta || dpipe);
 		auto at = [&] (int b) { return e->stageDbl[b] ? (size_t)bset * need : (size_t)0; };
-		P.mid0 = e->mid0.p + 2 * at (0);
+		P.mid0 = e->mid0.p ? e->mid0.p + 2 * at (0) : nullptr;
 		P.mid1 = e->mid1.p ? e->mid1.p + at (1) : nullptr;
 		P.mid2 = e->mid2.p ? e->mid2.p + at (4) : nullptr;
 		P.rvA  = e->rvA.p ? e->rvA.p + 2 * at (2) : nullptr;
@@ -2603,6 +2619,7 @@ static int renderBody (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, ui
 		                            : std::max (1u, std::min ({8u, 2048u / std::max (n, 1u), len / 4}));
 		P.tgSplit = std::min (P.tgSplit, std::max (len, 1u));
 		P.outOffset = (uint64_t)b0 * TBF_BLK;
+		P.extOffset = (uint64_t)b0 * TBF_BLK;
 		P.nCtlInst  = 0;
 		if (e->devCtl && (dfront ? delta : !e->hDInst.empty ())) {
 			/* k_tgctl: the stepped blocks' programs, ahead of k_tonegen on this stream */
@@ -2717,7 +2734,7 @@ static int renderBody (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, ui
 			 * k_rv_core, rvB by k_rv_post, mid2 by k_whirl) when they run on another stream. */
 			static const int readers[TBF_NSTAGES][2] = {{1, -1}, {2, 4}, {3, -1}, {4, -1}, {5, -1}, {-1, -1}};
 			auto strm = [&] (int k) { return e->gs[e->grp[k == 2 && ahead ? TBF_NSTAGES - 1 : k]]; };
-			for (int k = 0; k < nst; k++) {
+			for (int k = st0; k < nst; k++) {
 				hipStream_t sk = strm (k);
 				if (k == nst - 1 && plain && b0 + len < nblocks) { /* held back for the next chunk's k_rv_pre */
 					e->defP       = P;
@@ -2725,9 +2742,14 @@ static int renderBody (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, ui
 					e->defPending = true;
 					break;
 				}
-				if (k == 0 && !e->stagesBusy) { /* after the caller's stream (uploads, earlier chunks) */
+				/* after the caller's stream (uploads, earlier chunks).  A generator needs that only
+				 * when the stage streams are idle; a stage that reads the caller's input needs it on
+				 * every call: the input is complete only where the caller's stream reaches the call
+				 * (later chunks of the call follow the first on the stage's stream) */
+				if (k == st0 && (!e->stagesBusy || (st0 > 0 && !e->inWait))) {
 					HIPCHK (hipEventRecord (e->sjoin, s));
 					HIPCHK (hipStreamWaitEvent (sk, e->sjoin, 0));
+					e->inWait = true;
 				}
 				if (k == nst - 1 && !e->outWait) { /* the output stage writes the caller's buffers */
 					HIPCHK (hipEventRecord (e->sjoin, s));
@@ -2761,7 +2783,7 @@ static int renderBody (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, ui
 			b0 += len;
 			continue;
 		}
-		for (int k = 0; k < nst; k++) {
+		for (int k = st0; k < nst; k++) {
 			hipEvent_t e0 = nullptr, e1 = nullptr;
 			if (e->timeOn) {
 				HIPCHK (hipEventCreate (&e0));
@@ -2795,12 +2817,124 @@ static int renderBody (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, ui
 	return 0;
 }
 
+/* the tbf_render* calls and tbf_synth_sound on an effects-only engine */
+static int noRenderOnFx (const tbf_engine* e)
+{
+	if (chainFx (e->cfg.chain_mode))
+		return fail (-22, "effects-only engine (TBF_CHAIN_FX*) has no tone generator to render: "
+		                  "use tbf_process / tbf_process_device / tbf_process_events");
+	return 0;
+}
+
+/* the checks of the tbf_process* calls (the overlap check compares pointers on the host only) */
+static int processArgs (tbf_engine* e, uint32_t nblocks, const float* in, uint64_t inStride, const float* outL,
+                        const float* outR, uint64_t stride)
+{
+	if (!e || !in || !outL || !outR)
+		return fail (-22, "null argument");
+	if (!chainFx (e->cfg.chain_mode))
+		return fail (-22, "tbf_process* needs an effects-only engine (TBF_CHAIN_FX*)");
+	if (e->cfg.device < 0)
+		return fail (-19, "host-only engine (device -1) cannot render");
+	const uint64_t per = (uint64_t)nblocks * TBF_BLK;
+	if (inStride < per)
+		return fail (-22, "in_stride smaller than nblocks*128");
+	if (stride < per)
+		return fail (-22, "stride smaller than nblocks*128");
+	const uint64_t n = e->inst.size ();
+	if (n && per) { /* [first float, one past the last float) of each range */
+		const uintptr_t i0 = (uintptr_t)in, i1 = (uintptr_t)(in + (n - 1) * inStride + per);
+		for (const float* o : {outL, outR}) {
+			const uintptr_t o0 = (uintptr_t)o, o1 = (uintptr_t)(o + (n - 1) * stride + per);
+			if (i0 < o1 && o0 < i1)
+				return fail (-22, "input and output ranges overlap");
+		}
+	}
+	return 0;
+}
+
+/* renderImpl with the call's input rows (tbf_engine.extIn: set for this call only) */
+static int processImpl (tbf_engine* e, uint32_t nblocks, const float* dIn, uint64_t inStride, float* dL, float* dR,
+                        uint64_t stride, hipStream_t s, const tbf_event* ev = nullptr, uint32_t nev = 0)
+{
+	e->extIn     = dIn;
+	e->extStride = inStride;
+	const int rc = renderImpl (e, nblocks, dL, dR, stride, s, ev, nev);
+	e->extIn     = nullptr;
+	return rc;
+}
+
+/* events sorted by block (in parallel: large event lists) */
+static int eventsSorted (const tbf_event* ev, uint32_t nev)
+{
+	const unsigned    T  = std::max (1u, std::min (hostThreads (), (nev + 32767) / 32768));
+	const uint32_t    sg = (nev + T - 1) / T;
+	std::vector<char> bad (T, 0);
+	parallelFor (T, [&] (uint32_t t) {
+		const uint32_t k0 = std::max (1u, std::min (nev, t * sg)), k1 = std::min (nev, (t + 1) * sg);
+		for (uint32_t k = k0; k < k1; k++)
+			if (ev[k].block < ev[k - 1].block) {
+				bad[t] = 1;
+				return;
+			}
+	});
+	for (char b : bad)
+		if (b)
+			return fail (-22, "events must be sorted by block");
+	return 0;
+}
+
 extern "C" {
+
+int tbf_process_device (tbf_engine* e, uint32_t nblocks, const float* dIn, uint64_t inStride, float* dL, float* dR,
+                        uint64_t stride, void* stream)
+{
+	if (int rc = processArgs (e, nblocks, dIn, inStride, dL, dR, stride))
+		return rc;
+	HIPCHK (hipSetDevice (e->cfg.device));
+	return processImpl (e, nblocks, dIn, inStride, dL, dR, stride, stream ? (hipStream_t)stream : e->stream);
+}
+
+int tbf_process_events (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, const float* dIn,
+                        uint64_t inStride, float* dL, float* dR, uint64_t stride, void* stream)
+{
+	if (nev && !ev)
+		return fail (-22, "null argument");
+	if (int rc = processArgs (e, nblocks, dIn, inStride, dL, dR, stride))
+		return rc;
+	if (int rc = eventsSorted (ev, nev))
+		return rc;
+	HIPCHK (hipSetDevice (e->cfg.device));
+	return processImpl (e, nblocks, dIn, inStride, dL, dR, stride, stream ? (hipStream_t)stream : e->stream, ev, nev);
+}
+
+int tbf_process (tbf_engine* e, uint32_t nblocks, const float* in, uint64_t inStride, float* outL, float* outR,
+                 uint64_t stride)
+{
+	if (int rc = processArgs (e, nblocks, in, inStride, outL, outR, stride))
+		return rc;
+	HIPCHK (hipSetDevice (e->cfg.device));
+	const uint32_t n   = (uint32_t)e->inst.size ();
+	const size_t   per = (size_t)nblocks * TBF_BLK;
+	if (n == 0 || per == 0)
+		return 0;
+	if (e->extBuf.ensure ((size_t)n * per) || e->outL.ensure ((size_t)n * per) || e->outR.ensure ((size_t)n * per))
+		return fail (-12, "out of device memory (input and outputs)");
+	HIPCHK (hipMemcpy2DAsync (e->extBuf.p, per * 4, in, inStride * 4, per * 4, n, hipMemcpyHostToDevice, e->stream));
+	if (int rc = processImpl (e, nblocks, e->extBuf.p, per, e->outL.p, e->outR.p, per, e->stream))
+		return rc;
+	HIPCHK (hipMemcpy2DAsync (outL, stride * 4, e->outL.p, per * 4, per * 4, n, hipMemcpyDeviceToHost, e->stream));
+	HIPCHK (hipMemcpy2DAsync (outR, stride * 4, e->outR.p, per * 4, per * 4, n, hipMemcpyDeviceToHost, e->stream));
+	HIPCHK (hipStreamSynchronize (e->stream));
+	return 0;
+}
 
 int tbf_render_device (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, uint64_t stride, void* stream)
 {
 	if (!e || !dL || !dR)
 		return fail (-22, "null argument");
+	if (int rc = noRenderOnFx (e))
+		return rc;
 	if (e->cfg.device < 0)
 		return fail (-19, "host-only engine (device -1) cannot render");
 	HIPCHK (hipSetDevice (e->cfg.device));
@@ -2812,24 +2946,12 @@ int tbf_render_events (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uin
 {
 	if (!e || !dL || !dR || (nev && !ev))
 		return fail (-22, "null argument");
+	if (int rc = noRenderOnFx (e))
+		return rc;
 	if (e->cfg.device < 0)
 		return fail (-19, "host-only engine (device -1) cannot render");
-	{ /* sorted by block (in parallel: large event lists) */
-		const unsigned    T  = std::max (1u, std::min (hostThreads (), (nev + 32767) / 32768));
-		const uint32_t    sg = (nev + T - 1) / T;
-		std::vector<char> bad (T, 0);
-		parallelFor (T, [&] (uint32_t t) {
-			const uint32_t k0 = std::max (1u, std::min (nev, t * sg)), k1 = std::min (nev, (t + 1) * sg);
-			for (uint32_t k = k0; k < k1; k++)
-				if (ev[k].block < ev[k - 1].block) {
-					bad[t] = 1;
-					return;
-				}
-		});
-		for (char b : bad)
-			if (b)
-				return fail (-22, "events must be sorted by block");
-	}
+	if (int rc = eventsSorted (ev, nev))
+		return rc;
 	HIPCHK (hipSetDevice (e->cfg.device));
 	return renderImpl (e, nblocks, dL, dR, stride, stream ? (hipStream_t)stream : e->stream, ev, nev);
 }
@@ -2838,6 +2960,8 @@ int tbf_render (tbf_engine* e, uint32_t nblocks, float* outL, float* outR, uint6
 {
 	if (!e || !outL || !outR)
 		return fail (-22, "null argument");
+	if (int rc = noRenderOnFx (e))
+		return rc;
 	if (e->cfg.device < 0)
 		return fail (-19, "host-only engine (device -1) cannot render");
 	HIPCHK (hipSetDevice (e->cfg.device));
@@ -2860,6 +2984,8 @@ int tbf_synth_sound (tbf_engine* e, uint32_t nframes, float* outL, float* outR, 
 {
 	if (!e || !outL || !outR)
 		return fail (-22, "null argument");
+	if (int rc = noRenderOnFx (e))
+		return rc;
 	if (stride < nframes)
 		return fail (-22, "stride smaller than nframes");
 	const uint32_t n = (uint32_t)e->inst.size ();

@@ -324,6 +324,7 @@ struct tbf_engine {
 	bool                                    timeSerial = false; /* time with pipelining off */
 	std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> tev;
 	DevBuf<float>                           outL, outR;
+	DevBuf<float>                           extBuf; /* tbf_process: the host input on the device */
 	DevBuf<float>                           mid0, mid1, mid2; /* inter-stage blocks of one launch chunk */
 	DevBuf<double>                          rvA, rvB;   /* reverb inter-kernel streams (FP64) */
 	std::vector<tbf_seg_ctl>                hCtl;  /* current control per instance (pool entries 0..n-1) */
@@ -373,6 +374,13 @@ struct tbf_engine {
 	uint64_t                                defCix     = 0;
 	hipStream_t                             callS      = nullptr; /* the caller's stream of the current renderImpl ... */
 	bool                                    outWait    = false;   /* ... which the output stage has waited for */
+	/* effects-only chains (TBF_CHAIN_FX*): the current call's input rows (tbf_process*; NULL in a
+	 * tbf_render* call), and whether the call's first stage has waited for the caller's stream
+	 * yet: a generator's first stage waits only when the stage streams are idle, a stage that
+	 * reads the caller's buffer waits on every call (the input-side analogue of outWait) */
+	const float*                            extIn      = nullptr;
+	uint64_t                                extStride  = 0;
+	bool                                    inWait     = false;
 	uint64_t                                aheadCount = 0;       /* k_rv_pre launches that ran ahead (tbf_debug_pre_ahead) */
 	bool                                    rvLdsOn  = true;  /* k_rv_core_lds when the rings fit (TBF_RV_LDS=0: k_rv_core) */
 	bool                                    rvLdsFit = false; /* the instances' rings fit k_rv_core_lds */

@@ -318,7 +318,8 @@ typedef struct tbf_launch {
 	uint32_t              nBlocks;
 	uint32_t              wringLen;
 	uint32_t              statorInc;
-	uint32_t              chain;     /* TBF_CHAIN_*: 0 full, 1 tonegen, 2 preamp tap, 3 reverb tap */
+	uint32_t              chain;     /* TBF_CHAIN_*: 0 full, 1 tonegen, 2 preamp tap, 3 reverb tap (an effects-only
+	                                  * chain as the chain of the same end: tbf_chain_kernels) */
 	uint32_t              instBase;
 	uint32_t              slabLen;
 	uint32_t              dbg;       /* TBF_DEBUG_* bits of tbf_engine_config.debug_flags */
@@ -348,6 +349,11 @@ typedef struct tbf_launch {
 	const float*          fevVal;    /* ... and the values of its TBF_FEV_EFFECT events */
 	const float*          keyComp;   /* [tpl][128] keyCompTable */
 	uint32_t              progBase;  /* program slot of delta d (pool index nInst + d): progBase + d * TBF_PROG_SLOT */
+	/* effects-only chains (TBF_CHAIN_FX*): the caller's input rows, which stage 1 (k_mixpre_ext)
+	 * reads in place of mid0; NULL on every other chain */
+	const float*          ext;
+	uint64_t              extStride; /* floats between instances */
+	uint64_t              extOffset; /* first sample index of this chunk */
 } tbf_launch;
 
 #endif

@@ -62,7 +62,15 @@ SIGNATURES = {
     "tbf_set_steady_chunk": (C.c_int, [C.c_void_p, C.c_uint32]),
     "tbf_render_events": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                     C.c_uint64, C.c_void_p]),
+    "tbf_process": (C.c_int, [C.c_void_p, C.c_uint32, _fp, C.c_uint64, _fp, _fp, C.c_uint64]),
+    "tbf_process_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                     C.c_uint64, C.c_void_p]),
+    "tbf_process_events": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
+                                     C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
 }
+
+# tbf_engine_config.chain_mode of the effects-only chains (include/tbf.h TBF_CHAIN_FX*)
+CHAIN_FX, CHAIN_FX_TAP_PREAMP, CHAIN_FX_TAP_REVERB = 4, 5, 6
 
 # tbf_event kinds (include/tbf.h)
 EV_NOTE, EV_PARAM, EV_CONTROL, EV_PROGRAM = 0, 1, 2, 3
@@ -286,6 +294,35 @@ class Engine:
         _check(self._lib.tbf_render_events(self._h, int(nblocks), ev.ctypes.data if len(ev) else None, len(ev),
                                            C.c_void_p(int(outL_ptr)), C.c_void_p(int(outR_ptr)), int(stride),
                                            None if stream is None else C.c_void_p(int(stream))))
+
+    def process(self, x):
+        """Effects-only engines (chain=CHAIN_FX*): x [n_instances, nblocks*128] float32 through
+        overdrive -> reverb -> whirl; synchronous, returns (L, R) of the same shape."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n = self.n_instances
+        if x.ndim != 2 or x.shape[0] != n or x.shape[1] % 128:
+            raise ValueError(f"input shape {x.shape}: want ({n}, nblocks*128)")
+        L = np.zeros_like(x)
+        R = np.zeros_like(x)
+        _check(self._lib.tbf_process(self._h, x.shape[1] // 128, x.ctypes.data_as(_fp), x.shape[1],
+                                     L.ctypes.data_as(_fp), R.ctypes.data_as(_fp), x.shape[1]))
+        return L, R
+
+    def process_device(self, nblocks, in_ptr, in_stride, outL_ptr, outR_ptr, stride, stream=None):
+        """tbf_process_device: enqueue nblocks of device-resident input rows (e.g. a torch
+        tensor's data_ptr()) through the effects into device memory.  The input must be
+        complete where `stream` reaches the call and may be overwritten behind it."""
+        _check(self._lib.tbf_process_device(self._h, int(nblocks), C.c_void_p(int(in_ptr)), int(in_stride),
+                                            C.c_void_p(int(outL_ptr)), C.c_void_p(int(outR_ptr)), int(stride),
+                                            None if stream is None else C.c_void_p(int(stream))))
+
+    def process_events_device(self, nblocks, events, in_ptr, in_stride, outL_ptr, outR_ptr, stride, stream=None):
+        """tbf_process_events: process_device with scheduled events (Engine.events)."""
+        ev = np.ascontiguousarray(events, dtype=EVENT_DTYPE)
+        _check(self._lib.tbf_process_events(self._h, int(nblocks), ev.ctypes.data if len(ev) else None, len(ev),
+                                            C.c_void_p(int(in_ptr)), int(in_stride), C.c_void_p(int(outL_ptr)),
+                                            C.c_void_p(int(outR_ptr)), int(stride),
+                                            None if stream is None else C.c_void_p(int(stream))))
 
     def synchronize(self):
         _check(self._lib.tbf_synchronize(self._h))

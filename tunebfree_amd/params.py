@@ -9,3 +9,6 @@ BUS_DRAWBAR_BASE = 100
 VIBRATO_LOWER, SWELL, WHIRL_BYPASS = 130, 131, 132
 
 CHAIN_FULL, CHAIN_TONEGEN = 0, 1
+CHAIN_TAP_PREAMP, CHAIN_TAP_REVERB = 2, 3
+# effects-only chains: the caller's audio through overdrive -> reverb -> whirl (Engine.process*)
+CHAIN_FX, CHAIN_FX_TAP_PREAMP, CHAIN_FX_TAP_REVERB = 4, 5, 6
