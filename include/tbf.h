@@ -156,6 +156,44 @@ uint32_t tbf_instance_count (const tbf_engine* e);
  * scanner.* cfg keys in force now apply to the new tone generator. */
 int tbf_instance_retune (tbf_engine* e, uint32_t inst, uint32_t tpl_id);
 
+/* ---- instance state: fork, save, restore ----
+ * An instance's complete state -- the device DSP state (reverb rings and predelay history,
+ * whirl rings, scanner ring, wheel positions, IIR states, dither streams, rotor angles and
+ * ramps, the per-wheel control tables, the current core program) and the host control
+ * state -- copied, never re-derived.  The three calls are synchronous and wait for the
+ * engine's own stream and the pipelined stage streams; a caller rendering on its own
+ * stream must synchronize that stream first (as for tbf_error_flags).
+ *
+ * tbf_instances_clone appends n instances; new instance *first + k is an exact copy of
+ * instance src[k] as it stands now, i.e. as of the next block boundary: the device state,
+ * the whole host control state including what is pending and not yet rendered (queued key
+ * messages, dirty drawbars / routing, a pending rotary option, whirl parameter set or
+ * retune, the control rand() stream) and the source's row of the tbf_synth_sound FIFO.
+ * From then on the clone is an ordinary instance: with the same later events it renders
+ * the source's samples bit for bit, with other events what the reference renders for an
+ * organ of the source's seed with the source's history and then those events.  src may
+ * repeat; every src[k] must exist before the call (-22, nothing added); on -12 nothing is
+ * added and the existing instances are untouched.  Works on every chain mode, on a
+ * host-only engine (device -1: the control plane alone) and before the first render. */
+int tbf_instances_clone (tbf_engine* e, uint32_t n, const uint32_t* src, uint32_t* first);
+/* The n instances' state into one opaque blob of *size bytes (blob NULL: only the count;
+ * otherwise cap must cover it, -22).  A blob is valid for this build of the library only:
+ * it is no versioned or portable format, it dumps the engine's structs as they are, and its
+ * header (struct sizes, sample rate, chain mode, device / host-only, control path, ring
+ * window and slab length, fingerprints of the engine-wide tables and of each instance's
+ * template) exists to refuse any other use.  Block granularity: -16 while the
+ * tbf_synth_sound FIFO holds unserved frames. */
+int tbf_instances_save (tbf_engine* e, uint32_t n, const uint32_t* inst, void* blob, uint64_t cap, uint64_t* size);
+/* Overwrites the existing, distinct instances inst[k] with the blob's k-th record (inst need
+ * not be the indices saved from): on the same engine (rewind) or on another engine created
+ * with the same configuration and holding an equal template at the same id (migrate).  n
+ * must equal the blob's count and every header field and fingerprint must match, else -22
+ * with tbf_last_error () naming the first mismatch; every length in the blob is checked
+ * against size (a truncated or corrupted blob is a -22, never an out-of-range read), and
+ * everything is validated before anything is touched: a failed load changes nothing.
+ * -16 while the tbf_synth_sound FIFO holds unserved frames. */
+int tbf_instances_load (tbf_engine* e, uint32_t n, const uint32_t* inst, const void* blob, uint64_t size);
+
 int tbf_note (tbf_engine* e, uint32_t inst, int32_t key, int32_t on);
 int tbf_set_param (tbf_engine* e, uint32_t inst, int32_t param, double value);
 

@@ -64,12 +64,7 @@ int tbf::fail (int code, const std::string& msg)
 	} while (0)
 
 
-/* program slots (tbf_types.h TBF_PROG_SLOT: header + entries).  The device program pool
- * holds two persistent slots per instance (2 i, 2 i + 1; the host-controlled path uses
- * the first), then the chunk's delta programs */
-#define SLOT ((size_t)TBF_PROG_SLOT)
-#define PSLOTS ((size_t)TBF_PROG_PSLOTS)
-#define PERSIST(n) ((size_t)(n) * PSLOTS * SLOT)
+/* program slots: SLOT, PSLOTS, PERSIST (n) of tbf_engine_impl.h */
 /* blocks per kernel launch chunk: bounds the inter-stage buffers to
  * n_inst x TBF_CHUNK x 128 floats each (134 MB at 4096 instances) */
 #ifndef TBF_CHUNK
@@ -251,6 +246,7 @@ static int buildShared (tbf_engine* e)
 {
 	const double sr = e->cfg.sample_rate;
 	e->wt.build (sr, e->conf);
+	e->engFp = 0;
 	/* compact whirl ring: live window < maxAhead + 2 + one sub-block */
 	uint32_t W = 512;
 	while ((float)W < e->wt.maxAhead + 2.0f + TBF_SUB + 2.0f)
@@ -554,6 +550,8 @@ int tbf_engine_destroy (tbf_engine* e)
 	e->outL.release ();
 	e->outR.release ();
 	e->extBuf.release ();
+	e->stStage.release ();
+	e->stPairs.release ();
 	e->mid0.release ();
 	e->mid1.release ();
 	e->mid2.release ();
@@ -1290,6 +1288,17 @@ static int ensureDevice (tbf_engine* e)
 	}
 	e->deviceReady = true;
 	return 0;
+}
+
+int tbf::engineDevice (tbf_engine* e) { return ensureDevice (e); }
+
+int tbf::engineDrain (tbf_engine* e)
+{
+	if (e->cfg.device < 0)
+		return 0;
+	HIPCHK (hipSetDevice (e->cfg.device));
+	HIPCHK (hipStreamSynchronize (e->stream));
+	return drainStages (e);
 }
 
 int tbf::controlById (Instance& in, int id, int value);

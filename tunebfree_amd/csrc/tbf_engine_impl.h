@@ -46,6 +46,8 @@ void setCharacter (struct Instance& in, float v);
 
 namespace tbf {
 
+/* (tbf_instances_clone / _save / _load copy an instance field by field: a new member goes
+ * into ioInstance, csrc/tbf_fork.cpp, too; TgControl's into ioTg) */
 struct Instance {
 	uint32_t       tpl = 0;
 	TgControl      tg;
@@ -203,6 +205,13 @@ struct DevBuf {
 
 using namespace tbf; /* private header: the engine's own translation units only */
 
+/* program slots (tbf_types.h TBF_PROG_SLOT: header + entries).  The device program pool
+ * holds TBF_PROG_PSLOTS persistent slots per instance (the host-controlled path uses the
+ * first), then the chunk's delta programs */
+#define SLOT ((size_t)TBF_PROG_SLOT)
+#define PSLOTS ((size_t)TBF_PROG_PSLOTS)
+#define PERSIST(n) ((size_t)(n) * PSLOTS * SLOT)
+
 #define TBF_NSTAGES 6 /* k_tonegen, k_mixpre, k_rv_pre, k_rv_core, k_rv_post, k_whirl */
 
 struct tbf_engine {
@@ -214,6 +223,10 @@ struct tbf_engine {
 	uint32_t                                statorInc = 0;
 	uint32_t                                wringLen  = 512;
 	std::vector<std::unique_ptr<TgTemplate>> tpls;
+	/* fingerprints for tbf_instances_save / _load (csrc/tbf_fork.cpp), 0: not computed yet:
+	 * per template (computed once), and of the engine-wide tables (buildShared resets it) */
+	std::vector<uint64_t>                   tplFp;
+	uint64_t                                engFp = 0;
 	std::vector<Instance>                   inst;
 	std::vector<uint32_t>                   retuned; /* tbf_instance_retune: device state to reset */
 	uint64_t                                hostCtlNs = 0, hostCtlBlocks = 0; /* tbf_debug_host_time */
@@ -325,6 +338,9 @@ struct tbf_engine {
 	std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> tev;
 	DevBuf<float>                           outL, outR;
 	DevBuf<float>                           extBuf; /* tbf_process: the host input on the device */
+	/* k_state_move (csrc/tbf_fork.cpp): the packed records of a save / load, and the pair lists */
+	DevBuf<unsigned char>                   stStage;
+	DevBuf<uint32_t>                        stPairs;
 	DevBuf<float>                           mid0, mid1, mid2; /* inter-stage blocks of one launch chunk */
 	DevBuf<double>                          rvA, rvB;   /* reverb inter-kernel streams (FP64) */
 	std::vector<tbf_seg_ctl>                hCtl;  /* current control per instance (pool entries 0..n-1) */
@@ -415,6 +431,10 @@ namespace tbf {
 /* the calling thread's active list while renderImpl steps an instance range on a host
  * worker thread (nullptr: the engine's own list) */
 extern thread_local std::vector<uint32_t>* tlAct;
+/* for csrc/tbf_fork.cpp: the device arrays sized and filled for every instance
+ * (ensureDevice), and the wait for the engine's stream and the pipelined stage streams */
+int engineDevice (tbf_engine* e);
+int engineDrain (tbf_engine* e);
 inline void markActive (tbf_engine* e, uint32_t i)
 {
 	if (i < e->inAct.size () && !e->inAct[i]) {

@@ -44,6 +44,9 @@ SIGNATURES = {
     "tbf_instances_add": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u32p, _u32p]),
     "tbf_instance_count": (C.c_uint32, [C.c_void_p]),
     "tbf_instance_retune": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "tbf_instances_clone": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u32p]),
+    "tbf_instances_save": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "tbf_instances_load": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.c_void_p, C.c_uint64]),
     "tbf_note": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int32, C.c_int32]),
     "tbf_set_param": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int32, C.c_double]),
     "tbf_render": (C.c_int, [C.c_void_p, C.c_uint32, _fp, _fp, C.c_uint64]),
@@ -228,6 +231,33 @@ class Engine:
         _check(self._lib.tbf_instances_add(self._h, len(t), t.ctypes.data_as(_u32p), s.ctypes.data_as(_u32p),
                                            C.byref(first)))
         return first.value
+
+    def clone(self, src):
+        """tbf_instances_clone: append exact copies of the instances src (an index or a list,
+        repeats allowed), device and host state, pending events included; returns the first
+        new index."""
+        a = np.ascontiguousarray(np.atleast_1d(src), dtype=np.uint32)
+        first = C.c_uint32()
+        _check(self._lib.tbf_instances_clone(self._h, len(a), a.ctypes.data_as(_u32p), C.byref(first)))
+        return first.value
+
+    def save(self, inst):
+        """tbf_instances_save: the instances' full state as an opaque uint8 blob (valid for
+        this build of the library only)."""
+        a = np.ascontiguousarray(np.atleast_1d(inst), dtype=np.uint32)
+        size = C.c_uint64()
+        _check(self._lib.tbf_instances_save(self._h, len(a), a.ctypes.data_as(_u32p), None, 0, C.byref(size)))
+        blob = np.zeros(size.value, np.uint8)
+        _check(self._lib.tbf_instances_save(self._h, len(a), a.ctypes.data_as(_u32p), blob.ctypes.data, blob.nbytes,
+                                            C.byref(size)))
+        assert size.value == blob.nbytes
+        return blob
+
+    def load(self, inst, blob):
+        """tbf_instances_load: overwrite the instances inst with the blob's records, in order."""
+        a = np.ascontiguousarray(np.atleast_1d(inst), dtype=np.uint32)
+        b = np.ascontiguousarray(blob, dtype=np.uint8)
+        _check(self._lib.tbf_instances_load(self._h, len(a), a.ctypes.data_as(_u32p), b.ctypes.data, b.nbytes))
 
     @property
     def n_instances(self):
