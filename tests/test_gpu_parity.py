@@ -957,11 +957,14 @@ def test_gpu_engine_switches_bitexact(oracle):
     """The scheduling switches change where and when work runs, never the output: with
     1100 instances, events on every block (keys, drawbars, control functions) and a
     programme change in the second chunk (that chunk's host control falls back to the
-    serial loop), rendered in two calls, every switch renders bit-identically to the
-    default engine: the serial host loop, the opt-in control stream (three persistent
-    program slots), a third stage-buffer set, the chunk-parity streams, no pipelining,
-    the streaming reverb network kernel (k_rv_core instead of k_rv_core_lds), the LDS
-    kernel run alone or beside k_whirl only, and four stage-group streams.
+    serial loop), rendered in two calls, every switch the engine reads renders
+    bit-identically to the default engine: the serial host loop (TBF_HOST_SERIAL=1), no
+    pipelining (TBF_PIPELINE=0), the streaming reverb network kernel (TBF_RV_LDS=0:
+    k_rv_core instead of k_rv_core_lds), the host front end for every chunk
+    (TBF_DEVICE_FRONT=0), the per-wheel control on the host (TBF_HOST_CONTROL=1), k_rv_pre
+    ahead (TBF_PRE_AHEAD=1), the stage-group layouts 0,0,1,1,2,2 (three streams, other
+    buffers by parity) and 0,0,1,2,2,3 (four streams), and k_tonegen without block ranges
+    (TBF_TG_SPLIT=1).
     Instances without a programme change are also checked against the oracle."""
     import os
     import torch
@@ -988,9 +991,9 @@ def test_gpu_engine_switches_bitexact(oracle):
                 rows.append((b, i, 1, S.P_DRAWBAR + 6, float((i + b) % 9)))
                 oscen[i].append((b, "param", S.P_DRAWBAR + 6, (i + b) % 9))
     prog_inst = {5, 700}
-    switches = [{}, {"TBF_HOST_SERIAL": "1"}, {"TBF_CTL_STREAM": "1"}, {"TBF_STAGE_BUFS": "3"},
-                {"TBF_PIPE_MODE": "0"}, {"TBF_PIPELINE": "0"}, {"TBF_RV_LDS": "0"}, {"TBF_RV_EXCL": "1"},
-                {"TBF_RV_EXCL": "2"}, {"TBF_PIPE_GROUPS": "0,1,2,3,3"}]
+    switches = [{}, {"TBF_HOST_SERIAL": "1"}, {"TBF_PIPELINE": "0"}, {"TBF_RV_LDS": "0"},
+                {"TBF_DEVICE_FRONT": "0"}, {"TBF_HOST_CONTROL": "1"}, {"TBF_PRE_AHEAD": "1"},
+                {"TBF_PIPE_GROUPS": "0,0,1,1,2,2"}, {"TBF_PIPE_GROUPS": "0,0,1,2,2,3"}, {"TBF_TG_SPLIT": "1"}]
     outs, cid = [], None
     for env in switches:
         os.environ.update(env)
@@ -1016,8 +1019,11 @@ def test_gpu_engine_switches_bitexact(oracle):
                                  nb * 128)
         eng.synchronize()
         outs.append((L.cpu().numpy(), R.cpu().numpy()))
-        c = eng.launches()  # calls of 40 and 32 blocks: the LDS network kernel unless switched off
-        streaming = env.get("TBF_RV_LDS") == "0"
+        # calls of 40 and 32 blocks: the LDS network kernel unless switched off.  Host control ends a
+        # chunk when its delta programs fill the pool: with a stepped delta per instance and block
+        # that is every few blocks, fewer than the LDS kernel takes (RVL_MIN_BLOCKS)
+        c = eng.launches()
+        streaming = env.get("TBF_RV_LDS") == "0" or env.get("TBF_HOST_CONTROL") == "1"
         assert (c["k_rv_core"] > 0, c["k_rv_core_lds"] > 0) == (streaming, not streaming), (env, c)
         assert c["k_whirl"] > 0 and c["k_whirl_split"] == 0, c  # 1100 instances: a full batch's whirl kernel
         eng.close()

@@ -472,8 +472,8 @@ int tbf_engine_create (const tbf_engine_config* cfg, tbf_engine** out)
 		e->rvGrid      = rp ? (uint32_t)std::max (atoi (rp), 0) : (uint32_t)std::max (ncu, 1);
 		if (e->rvWork.ensure (1))
 			return fail (-12, "out of device memory");
-		HIPCHK (hipEventCreateWithFlags (&e->upEv, hipEventDisableTiming));
-		HIPCHK (hipEventCreateWithFlags (&e->upEvB, hipEventDisableTiming));
+		for (ChunkStaging& cs : e->stg)
+			HIPCHK (hipEventCreateWithFlags (&cs.upEv, hipEventDisableTiming));
 		const char* pl = getenv ("TBF_PIPELINE");
 		e->pipeline    = !(pl && pl[0] == '0');
 		if (const char* pa = getenv ("TBF_PRE_AHEAD")) /* 0 / 1: the next chunk's k_rv_pre beside k_rv_post (A/B) */
@@ -484,6 +484,7 @@ int tbf_engine_create (const tbf_engine_config* cfg, tbf_engine** out)
 		e->devCtl      = !(hc && hc[0] == '1');
 		const char* hs = getenv ("TBF_HOST_SERIAL"); /* the serial loop (A/B); TBF_HOST_THREADS: workers */
 		e->parCtl      = !(hs && hs[0] == '1');
+		e->dbgPhases   = getenv ("TBF_DEBUG_HOST_PHASES") != nullptr;
 		const char* df = getenv ("TBF_DEVICE_FRONT"); /* 0: note-only chunks step on the host too (A/B) */
 		e->frontOn     = !(df && df[0] == '0');
 		if (const char* sp = getenv ("TBF_WHIRL_SPLIT")) /* 0 / 1: k_whirl / k_whirl_split always */
@@ -509,56 +510,6 @@ int tbf_engine_destroy (tbf_engine* e)
 	for (hipStream_t q : e->gs)
 		if (q)
 			(void)hipStreamSynchronize (q);
-	e->bank.release ();
-	e->tplDesc.release ();
-	e->cst.release ();
-	e->st.release ();
-	e->wring.release ();
-	e->rslab.release ();
-	e->ctl.release ();
-	e->prog.release ();
-	e->tgc.release ();
-	e->drec.release ();
-	e->dmsg.release ();
-	e->dctlInst.release ();
-	e->drecB.release ();
-	e->dmsgB.release ();
-	e->dgain.release ();
-	e->dgainB.release ();
-	e->dwh.release ();
-	e->dwhB.release ();
-	e->dctlInstB.release ();
-	e->dfull.release ();
-	e->dfullB.release ();
-	e->dfront.release ();
-	e->dfrontB.release ();
-	e->dfev.release ();
-	e->dfevB.release ();
-	e->dfval.release ();
-	e->dfvalB.release ();
-	e->dfoff.release ();
-	e->dfoffB.release ();
-	e->dkeyComp.release ();
-	e->dident.release ();
-	e->coff.release ();
-	e->contrib.release ();
-	e->vib.release ();
-	e->xsj.release ();
-	e->whTab.release ();
-	e->whBw.release ();
-	e->err.release ();
-	e->outL.release ();
-	e->outR.release ();
-	e->extBuf.release ();
-	e->stStage.release ();
-	e->stPairs.release ();
-	e->mid0.release ();
-	e->mid1.release ();
-	e->mid2.release ();
-	e->rvA.release ();
-	e->rvB.release ();
-	e->rvWork.release ();
-	e->mixFixed.release ();
 	if (e->stream)
 		(void)hipStreamDestroy (e->stream);
 	for (hipStream_t q : e->gs)
@@ -573,10 +524,10 @@ int tbf_engine_destroy (tbf_engine* e)
 	}
 	if (e->sjoin)
 		(void)hipEventDestroy (e->sjoin);
-	for (hipEvent_t ev : {e->upEv, e->upEvB})
-		if (ev)
-			(void)hipEventDestroy (ev);
-	delete e;
+	for (ChunkStaging& cs : e->stg)
+		if (cs.upEv)
+			(void)hipEventDestroy (cs.upEv);
+	delete e; /* the device buffers go with it (DevBuf) */
 	return 0;
 }
 
@@ -1324,7 +1275,7 @@ static int applyEvent (tbf_engine* e, const tbf_event& ev)
  * part of oscGenerateFragment and the effect setters' per-block constants).  Updates
  * the instance's current control e->hCtl[i] / program e->hProg; returns true when the
  * control the next block renders with changed. */
-static bool stepControl (tbf_engine* e, uint32_t i, bool& progChanged, tbf_tgc_rec* rec = nullptr,
+static bool stepControl (tbf_engine* e, ChunkStaging& cs, uint32_t i, bool& progChanged, tbf_tgc_rec* rec = nullptr,
                          std::vector<uint16_t>* msgOut = nullptr, std::vector<float>* gainOut = nullptr,
                          std::vector<tbf_wh_params>* whOut = nullptr)
 {
@@ -1344,10 +1295,10 @@ static bool stepControl (tbf_engine* e, uint32_t i, bool& progChanged, tbf_tgc_r
 			gainOut->resize (ag + kg);
 			in.tg.stepFront (msgOut->data () + at, at, gainOut->data () + ag, ag, *rec, c);
 		} else {
-			const uint32_t at = (uint32_t)e->hMsg.size (), ag = (uint32_t)e->hGain.size ();
-			e->hMsg.resize (at + k);
-			e->hGain.resize (ag + kg);
-			in.tg.stepFront (e->hMsg.data () + at, at, e->hGain.data () + ag, ag, *rec, c);
+			const uint32_t at = (uint32_t)cs.hMsg.size (), ag = (uint32_t)cs.hGain.size ();
+			cs.hMsg.resize (at + k);
+			cs.hGain.resize (ag + kg);
+			in.tg.stepFront (cs.hMsg.data () + at, at, cs.hGain.data () + ag, ag, *rec, c);
 		}
 		in.progDirty = false;
 		in.ctlDirty  = true;
@@ -1393,14 +1344,29 @@ static bool stepControl (tbf_engine* e, uint32_t i, bool& progChanged, tbf_tgc_r
 			whOut->push_back (p);
 			c.whSet = (uint32_t)whOut->size ();
 		} else {
-			e->hWh.push_back (p);
-			c.whSet = (uint32_t)e->hWh.size ();
+			cs.hWh.push_back (p);
+			c.whSet = (uint32_t)cs.hWh.size ();
 		}
 		in.whDirty = false;
 	}
 	in.ctlDirty = (c.whRevOption >= 0) || c.whSet;
 	return true;
 }
+
+/* What renderBody decides for one chunk, handed to the phases of the render path beside
+ * the chunk's staged arrays, e->stg[rp] (ChunkStaging). */
+struct Chunk {
+	uint64_t    cix;          /* the chunk's sequence number (tbf_engine.chunkSeq) */
+	int         rp;           /* control region and staging set: cix & 1 under device control, else 0 */
+	uint32_t    bset;         /* stage-buffer set: cix & 1 */
+	uint32_t    b0, want;     /* first block in the call, blocks planned (chunkLength) ... */
+	uint32_t    len;          /* ... and stepped: fewer when the host control ends the chunk early */
+	uint32_t    evBeg, evEnd; /* its events (block < b0 + want); evBeg moves past those the host control applied */
+	bool        delta, dfront; /* it has control deltas; the device front end (k_front) stepped it */
+	bool        dpipe, piped; /* device control and pipelining: uploads on us = gs[0]; stages on the group streams */
+	hipStream_t us;           /* the stream of the chunk's uploads and control kernels ... */
+	bool        usWaited;     /* ... which has waited for the previous user of this region (usWait) */
+};
 
 /* Device control: one chunk's host control (events + front-end steps) on host worker
  * threads, one contiguous instance range each.  Instances are independent and each keeps
@@ -1412,25 +1378,18 @@ static bool stepControl (tbf_engine* e, uint32_t i, bool& progChanged, tbf_tgc_r
  * changes excluded by the caller: randomizeDrawbars writes the shared programme table).
  * Fills what the serial loop fills: dCtl, hRec, hMsg, hCtlInst, stepped, hIdx (every row),
  * curIdx, chg, actList. */
-static int stepChunkParallel (tbf_engine* e, uint32_t n, uint32_t want, uint32_t b0, const tbf_event* ev,
-                              uint32_t evBeg, uint32_t evEnd, int rp, bool& delta)
+static int stepChunkParallel (tbf_engine* e, ChunkStaging& cs, Chunk& ck, uint32_t n, const tbf_event* ev)
 {
+	const uint32_t want = ck.want, b0 = ck.b0, evBeg = ck.evBeg, evEnd = ck.evEnd;
 	const unsigned T   = std::max (1u, std::min<unsigned> (hostThreads (), (n + 255) / 256));
 	const uint32_t per = (n + T - 1) / T;
 	auto&          out = e->parStep;
 	out.resize (T);
 	for (auto& o : out) {
-		o.msgs.clear ();
-		o.gains.clear ();
-		o.whs.clear ();
-		o.act.clear ();
-		o.ctlInst.clear ();
-		o.evs.clear ();
-		o.dInst.clear ();
-		o.fulls.clear ();
+		o.msgs.clear (), o.gains.clear (), o.whs.clear (), o.act.clear (), o.ctlInst.clear (), o.evs.clear ();
+		o.dInst.clear (), o.fulls.clear (), o.err.clear ();
 		o.nd = 0;
 		o.rc = 0;
-		o.err.clear ();
 	}
 	for (uint32_t a : e->actList) /* the active list by range, in order */
 		out[a / per].act.push_back (a);
@@ -1462,11 +1421,10 @@ static int stepChunkParallel (tbf_engine* e, uint32_t n, uint32_t want, uint32_t
 			}
 		});
 	}
-	e->hRec.resize ((size_t)n * want);
+	cs.hRec.resize ((size_t)n * want);
 	e->lastEmit.resize (n);
 	e->lastProg.resize (n);
 	e->dseen.assign (n, 0);
-	std::vector<uint32_t>& cur = e->curIdx;
 	const auto             ph0 = std::chrono::steady_clock::now ();
 	std::vector<uint64_t>  thNs (T);
 	parallelFor (T, [&] (uint32_t t) {
@@ -1474,7 +1432,8 @@ static int stepChunkParallel (tbf_engine* e, uint32_t n, uint32_t want, uint32_t
 		tbf_engine::ParStep& o    = out[t];
 		const uint32_t       i0   = t * per, i1 = std::min (n, i0 + per);
 		const uint32_t       base = i0 * want;
-		tbf_tgc_rec*         Rr   = e->hRec.data () + base; /* the worker's part of the staging */
+		tbf_tgc_rec*         Rr   = cs.hRec.data () + base; /* the worker's part of the staging */
+		uint32_t* const      idx  = cs.hIdx.data ();
 		tlAct                     = &o.act; /* (markActive's pushes; o.act is rebuilt below) */
 		/* instance-major: an instance's blocks one after another, so its host state stays in
 		 * the core's L1 over the chunk (block-major passes over the range missed it on every
@@ -1514,11 +1473,11 @@ static int stepChunkParallel (tbf_engine* e, uint32_t n, uint32_t want, uint32_t
 						e->dseen[i]    = 1;
 						e->lastEmit[i] = e->hCtl[i];
 					}
-					if (stepControl (e, i, pc, &rec, &o.msgs, &o.gains, &o.whs)) {
+					if (stepControl (e, cs, i, pc, &rec, &o.msgs, &o.gains, &o.whs)) {
 						const uint32_t d = base + o.nd++;
 						tbf_seg_ctl    c = e->hCtl[i];
 						if (pc) {
-							c.prog_off = (uint32_t)(PERSIST (n) + ((size_t)rp * n * TBF_CHUNK + d) * SLOT);
+							c.prog_off = (uint32_t)(PERSIST (n) + ((size_t)ck.rp * n * TBF_CHUNK + d) * SLOT);
 							if (!e->stepped[i]) {
 								e->stepped[i] = 1;
 								o.ctlInst.push_back (i);
@@ -1554,9 +1513,9 @@ static int stepChunkParallel (tbf_engine* e, uint32_t n, uint32_t want, uint32_t
 					} else
 						e->inAct[i] = 0;
 				}
-				e->hIdx[(size_t)len * n + i] = ci;
+				idx[(size_t)len * n + i] = ci;
 			}
-			cur[i] = ci;
+			e->curIdx[i] = ci;
 		}
 		o.act.clear (); /* the range's instances still active, in order */
 		for (uint32_t i = i0; i < i1; i++)
@@ -1582,21 +1541,21 @@ static int stepChunkParallel (tbf_engine* e, uint32_t n, uint32_t want, uint32_t
 		nf += out[t].fulls.size ();
 		if (out[t].nd) {
 			e->dSeg.push_back ({t * per * want, out[t].nd});
-			delta = true;
+			ck.delta = true;
 		}
 	}
 	if (e->dSeg.empty ())
 		e->dSeg.push_back ({0, 0});
-	e->hMsg.resize (nm);
-	e->hGain.resize (ng);
-	e->hWh.resize (nw);
-	e->hFull.resize (nf);
+	cs.hMsg.resize (nm);
+	cs.hGain.resize (ng);
+	cs.hWh.resize (nw);
+	cs.hFull.resize (nf);
 	if (nm || ng || nw || nf)
 		parallelFor (T, [&] (uint32_t t) { /* message, gain, full entry and whirl set offsets: worker-local -> chunk */
 			tbf_engine::ParStep& o    = out[t];
 			const size_t         base = (size_t)t * per * want;
 			for (size_t d = base; d < base + o.nd; d++) {
-				tbf_tgc_rec& r = e->hRec[d];
+				tbf_tgc_rec& r = cs.hRec[d];
 				if (r.flags & 0x80)
 					r.msgOff += (uint32_t)mb[t];
 				if (r.flags & 4)
@@ -1608,23 +1567,23 @@ static int stepChunkParallel (tbf_engine* e, uint32_t n, uint32_t want, uint32_t
 				if (f.whSet)
 					f.whSet += (uint32_t)wb[t];
 			if (!o.fulls.empty ())
-				memcpy ((void*)(e->hFull.data () + fb[t]), o.fulls.data (), o.fulls.size () * sizeof (tbf_seg_ctl));
+				memcpy ((void*)(cs.hFull.data () + fb[t]), o.fulls.data (), o.fulls.size () * sizeof (tbf_seg_ctl));
 			if (!o.whs.empty ())
-				memcpy ((void*)(e->hWh.data () + wb[t]), o.whs.data (), o.whs.size () * sizeof (tbf_wh_params));
+				memcpy ((void*)(cs.hWh.data () + wb[t]), o.whs.data (), o.whs.size () * sizeof (tbf_wh_params));
 			if (!o.msgs.empty ())
-				memcpy (e->hMsg.data () + mb[t], o.msgs.data (), o.msgs.size () * sizeof (uint16_t));
+				memcpy (cs.hMsg.data () + mb[t], o.msgs.data (), o.msgs.size () * sizeof (uint16_t));
 			if (!o.gains.empty ())
-				memcpy (e->hGain.data () + gb[t], o.gains.data (), o.gains.size () * sizeof (float));
+				memcpy (cs.hGain.data () + gb[t], o.gains.data (), o.gains.size () * sizeof (float));
 		});
 	e->actList.clear ();
 	for (unsigned t = 0; t < T; t++) {
 		e->actList.insert (e->actList.end (), out[t].act.begin (), out[t].act.end ());
 		for (uint32_t i : out[t].ctlInst)
-			e->hCtlInst.push_back (i);
+			cs.hCtlInst.push_back (i);
 		for (uint32_t i : out[t].dInst)
-			e->hDInst.push_back (i);
+			cs.hDInst.push_back (i);
 	}
-	if (getenv ("TBF_DEBUG_HOST_PHASES")) {
+	if (e->dbgPhases) {
 		const auto ph2 = std::chrono::steady_clock::now ();
 		auto       ms  = [] (auto a, auto b) { return std::chrono::duration<double, std::milli> (b - a).count (); };
 		uint64_t   mx = 0, sum = 0;
@@ -1635,6 +1594,8 @@ static int stepChunkParallel (tbf_engine* e, uint32_t n, uint32_t want, uint32_t
 		fprintf (stderr, "stepChunkParallel T=%u: step %.3f ms (thread max %.3f, mean %.3f) merge %.3f ms\n", T,
 		         ms (ph0, ph1), mx / 1e6, sum / 1e6 / T, ms (ph1, ph2));
 	}
+	ck.evBeg = evEnd;
+	ck.len   = want;
 	return 0;
 }
 
@@ -1784,11 +1745,11 @@ static void scanChunk (uint32_t n, uint32_t b0, const tbf_event* ev, uint32_t ev
 	}
 }
 
-static int stepChunkFront (tbf_engine* e, uint32_t n, uint32_t want, uint32_t b0, const tbf_event* ev, uint32_t evBeg,
-                           uint32_t evEnd, ChunkScan& cs, bool& delta)
+static int stepChunkFront (tbf_engine* e, ChunkStaging& cs, Chunk& ck, uint32_t n)
 {
-	const unsigned T   = cs.T;
-	const uint32_t per = cs.per;
+	const ChunkScan& sc = e->scan; /* the chunk's events, bucketed by scanChunk */
+	const unsigned T   = sc.T;
+	const uint32_t per = sc.per;
 	auto&          out = e->parStep;
 	const auto     f0  = std::chrono::steady_clock::now ();
 	out.resize (T);
@@ -1802,18 +1763,18 @@ static int stepChunkFront (tbf_engine* e, uint32_t n, uint32_t want, uint32_t b0
 	/* the events by instance range come from scanChunk's buckets, in event order */
 	const auto            f1 = std::chrono::steady_clock::now ();
 	std::vector<uint32_t> wbase (T + 1, 0);
-	auto seg = [&] (unsigned sgm, unsigned t) { return cs.boff.data () + (size_t)sgm * (T + 1) + t; };
+	auto seg = [&] (unsigned sgm, unsigned t) { return sc.boff.data () + (size_t)sgm * (T + 1) + t; };
 	for (unsigned t = 0; t < T; t++) {
 		size_t c = 0;
-		for (unsigned sgm = 0; sgm < cs.Te; sgm++)
+		for (unsigned sgm = 0; sgm < sc.Te; sgm++)
 			c += seg (sgm, t)[1] - seg (sgm, t)[0];
 		wbase[t + 1] = wbase[t] + (uint32_t)c;
 	}
-	e->hFevOff.resize (n + 1);
-	e->hFev.resize (std::max<uint32_t> (wbase[T], 1));
-	e->hFevVal.resize (std::max<uint32_t> (wbase[T], 1));
-	e->hFront.resize (n);
-	const bool          dbgPh = getenv ("TBF_DEBUG_HOST_PHASES") != nullptr;
+	cs.hFevOff.resize (n + 1);
+	cs.hFev.resize (std::max<uint32_t> (wbase[T], 1));
+	cs.hFevVal.resize (std::max<uint32_t> (wbase[T], 1));
+	cs.hFront.resize (n);
+	const bool          dbgPh = e->dbgPhases;
 	std::vector<double> thMs (dbgPh ? 3 * T : 0);
 	parallelFor (T, [&] (uint32_t t) {
 		const auto             g0 = std::chrono::steady_clock::now ();
@@ -1822,9 +1783,9 @@ static int stepChunkFront (tbf_engine* e, uint32_t n, uint32_t want, uint32_t b0
 		std::vector<uint32_t>& eo = o.eoff;
 		auto&                  es = o.erec;
 		eo.assign ((size_t)(i1 > i0 ? i1 - i0 : 0) + 1, 0);
-		for (unsigned sgm = 0; sgm < cs.Te; sgm++)
+		for (unsigned sgm = 0; sgm < sc.Te; sgm++)
 			for (uint32_t k = seg (sgm, t)[0]; k < seg (sgm, t)[1]; k++)
-				eo[cs.rec[k].inst - i0 + 1]++;
+				eo[sc.rec[k].inst - i0 + 1]++;
 		for (uint32_t i = i0; i < i1; i++)
 			eo[i - i0 + 1] += eo[i - i0];
 		es.resize (wbase[t + 1] - wbase[t]);
@@ -1832,9 +1793,9 @@ static int stepChunkFront (tbf_engine* e, uint32_t n, uint32_t want, uint32_t b0
 		   * order, so the per-instance pass below reads them sequentially) */
 			std::vector<uint32_t>& fill = o.efill;
 			fill.assign (eo.begin (), eo.end () - 1);
-			for (unsigned sgm = 0; sgm < cs.Te; sgm++)
+			for (unsigned sgm = 0; sgm < sc.Te; sgm++)
 				for (uint32_t k = seg (sgm, t)[0]; k < seg (sgm, t)[1]; k++) {
-					const ChunkScan::Rec& r = cs.rec[k];
+					const ChunkScan::Rec& r = sc.rec[k];
 					es[fill[r.inst - i0]++] = {r.bf >> 2, r.id, r.v, r.bf & 3u};
 				}
 		}
@@ -1842,7 +1803,7 @@ static int stepChunkFront (tbf_engine* e, uint32_t n, uint32_t want, uint32_t b0
 		for (uint32_t i = i0; i < i1; i++) {
 			Instance&        in = e->inst[i];
 			TgControl&       tg = in.tg;
-			tbf_front_state& F  = e->hFront[i];
+			tbf_front_state& F  = cs.hFront[i];
 			memset (&F, 0, sizeof (F));
 			static_assert (sizeof (F.keys) == sizeof (tg.keyBits), "384 key bits");
 			memcpy (F.keys, tg.keyBits, sizeof (F.keys));
@@ -1868,7 +1829,7 @@ static int stepChunkFront (tbf_engine* e, uint32_t n, uint32_t want, uint32_t b0
 			F.percSoft        = tg.percIsSoft != 0;
 			F.percFast        = tg.percIsFast != 0;
 			F.swell           = tg.swellPedalGain;
-			e->hFevOff[i]     = wbase[t] + eo[i - i0];
+			cs.hFevOff[i]     = wbase[t] + eo[i - i0];
 			/* the host's front state takes the events too (it stays the truth for any later
 			 * host-stepped chunk): the same setters, block by block, and the same steps as
 			 * the device -- a block with inputs steps, and so does the one after it */
@@ -1898,7 +1859,7 @@ static int stepChunkFront (tbf_engine* e, uint32_t n, uint32_t want, uint32_t b0
 				if (E.flag & 1u) {
 					const float    v = E.v;
 					const uint32_t w = frontParam (E.id, v);
-					e->hFev[wbase[t] + j] = w | (blk << 16);
+					cs.hFev[wbase[t] + j] = w | (blk << 16);
 					if (E.id >= 0 && E.id < 64)
 						in.params[E.id] = v;
 					const uint32_t op = (w >> 12) & 7u;
@@ -1950,7 +1911,7 @@ static int stepChunkFront (tbf_engine* e, uint32_t n, uint32_t want, uint32_t b0
 								break;
 							}
 						}
-						e->hFevVal[wbase[t] + j] = x;
+						cs.hFevVal[wbase[t] + j] = x;
 						fxd                      = true;
 						continue;
 					}
@@ -1968,12 +1929,12 @@ static int stepChunkFront (tbf_engine* e, uint32_t n, uint32_t want, uint32_t b0
 				}
 				const bool on = (E.flag & 2u) != 0;
 				const bool ok = E.id >= 0 && E.id < 384; /* oscKeyOn/Off ignore keys >= MAX_KEYS */
-				e->hFev[wbase[t] + j] = (ok ? (uint32_t)E.id : 0x0fffu) | (on ? 1u << 12 : 0u) | (blk << 16);
+				cs.hFev[wbase[t] + j] = (ok ? (uint32_t)E.id : 0x0fffu) | (on ? 1u << 12 : 0u) | (blk << 16);
 				msgsB += ok ? (uint32_t)tg.noteCount (E.id, on) : 0u;
 			}
 			if (curB >= 0) {
 				closeBlock ();
-				if ((uint32_t)curB + 1 < want)
+				if ((uint32_t)curB + 1 < ck.want)
 					pend = false;
 			} else
 				pend = false; /* no events: block 0 takes the pending step */
@@ -2021,7 +1982,7 @@ static int stepChunkFront (tbf_engine* e, uint32_t n, uint32_t want, uint32_t b0
 			thMs[3 * t + 2] = std::chrono::duration<double, std::milli> (g2 - g1).count (); /* mirror */
 		}
 	});
-	e->hFevOff[n] = wbase[T];
+	cs.hFevOff[n] = wbase[T];
 	{ /* the gain-pair slots: each range's base */
 		std::vector<uint32_t> gb (T + 1, 0);
 		for (unsigned t = 0; t < T; t++)
@@ -2029,19 +1990,19 @@ static int stepChunkFront (tbf_engine* e, uint32_t n, uint32_t want, uint32_t b0
 		e->frontGain = gb[T];
 		parallelFor (T, [&] (uint32_t t) {
 			for (uint32_t i = t * per; i < std::min (n, (t + 1) * per); i++)
-				e->hFront[i].gainOff += gb[t];
+				cs.hFront[i].gainOff += gb[t];
 		});
 	}
 	e->actList.clear ();
 	for (unsigned t = 0; t < T; t++) {
 		e->actList.insert (e->actList.end (), out[t].act.begin (), out[t].act.end ());
 		for (uint32_t i : out[t].ctlInst)
-			e->hCtlInst.push_back (i);
+			cs.hCtlInst.push_back (i);
 	}
-	delta = !e->hCtlInst.empty ();
+	ck.delta = !cs.hCtlInst.empty ();
 	for (unsigned t = 0; t < T; t++)
-		delta = delta || out[t].fx;
-	if (getenv ("TBF_DEBUG_HOST_PHASES")) {
+		ck.delta = ck.delta || out[t].fx;
+	if (dbgPh) {
 		auto ms = [] (auto a, auto b) { return std::chrono::duration<double, std::milli> (b - a).count (); };
 		fprintf (stderr, "stepChunkFront T=%u: partition %.3f ms, instances %.3f ms\n", T, ms (f0, f1),
 		         ms (f1, std::chrono::steady_clock::now ()));
@@ -2054,6 +2015,8 @@ static int stepChunkFront (tbf_engine* e, uint32_t n, uint32_t want, uint32_t b0
 		fprintf (stderr, "  threads (mean / max ms): start %.3f / %.3f, sort %.3f / %.3f, mirror %.3f / %.3f\n", sm[0], mx[0],
 		         sm[1], mx[1], sm[2], mx[2]);
 	}
+	ck.evBeg = ck.evEnd;
+	ck.len   = ck.want;
 	return 0;
 }
 
@@ -2062,28 +2025,40 @@ static int stepChunkFront (tbf_engine* e, uint32_t n, uint32_t want, uint32_t b0
  * enough for the longest chunk this call can make, so a caller that renders 64 blocks at a
  * time never pays for longer chunks (n x blocks x 128 x 56 B at the default stage
  * groups: 15 GB at 4096 instances and the default 512-block chunks, 60 GB at 2048, 1.9 GB
- * at 64).  They only grow (a
- * different stride under chunks still in flight would be wrong), after every launch that
- * may read them has finished.  When the device cannot hold them, the chunk halves down to
+ * at 64).  They only grow (a different stride under chunks still in flight would be
+ * wrong), after every launch that may read them has finished.  When the device cannot hold them, the chunk halves down to
  * TBF_CHUNK before the call fails, and steadyChunk stays at what fitted.  A buffer whose
  * producer and every reader run on one stage-group stream is single: the next chunk's
  * producer is ordered behind this chunk's readers by the stream (default groups {0,0,1,1,1,2}:
  * mid0, rvA and rvB single; mid1, mid2 by chunk parity). */
-/* bytes of the stage buffers at n instances and chunks of `blocks` blocks (mid0 8 B, mid1 /
- * mid2 4 B, rvA / rvB 16 B per sample, each doubled when it alternates by chunk parity) */
+/* the stage buffers: the stage that writes each, the
+ * stages that read it (-1: none; mid0 is read by k_mixpre, mid1 by k_rv_pre and k_rv_post,
+ * rvA by k_rv_core, rvB by k_rv_post, mid2 by k_whirl) and its bytes per sample */
+enum { SB_MID0, SB_MID1, SB_RVA, SB_RVB, SB_MID2, SB_COUNT };
+static const struct StageBuf {
+	int    prod, rd[2];
+	size_t bytes;
+} stageBuf[SB_COUNT] = {{0, {1, -1}, 8}, {1, {2, 4}, 4}, {2, {3, -1}, 16}, {3, {4, -1}, 16}, {4, {5, -1}, 4}};
+
+/* whether buffer b alternates by chunk parity: a reader on another stream than its producer */
+static bool stageBufAlternates (const tbf_engine* e, int b)
+{
+	for (int r : stageBuf[b].rd)
+		if (r >= 0 && e->grp[r] != e->grp[stageBuf[b].prod])
+			return true;
+	return false;
+}
+
+/* bytes of the stage buffers at n instances and chunks of `blocks` blocks (each buffer
+ * doubled when it alternates by chunk parity) */
 static size_t stageFootprint (const tbf_engine* e, size_t n, uint32_t blocks)
 {
-	static const int prod[5] = {0, 1, 2, 3, 4}, rd[5][2] = {{1, -1}, {2, 4}, {3, -1}, {4, -1}, {5, -1}};
-	static const size_t per[5] = {8, 4, 16, 16, 4};
 	const bool rv = chainReverb (e->cfg.chain_mode), fx = chainFx (e->cfg.chain_mode);
 	size_t sum = 0;
-	for (int b = fx ? 1 : 0; b < 5; b++) { /* an effects-only chain has no mid0 */
-		if (b > 0 && !rv)
+	for (int b = fx ? SB_MID1 : SB_MID0; b < SB_COUNT; b++) { /* an effects-only chain has no mid0 */
+		if (b > SB_MID0 && !rv)
 			break;
-		bool dbl = false;
-		for (int r : rd[b])
-			dbl = dbl || (r >= 0 && e->grp[r] != e->grp[prod[b]]);
-		sum += (dbl ? 2 : 1) * per[b];
+		sum += (stageBufAlternates (e, b) ? 2 : 1) * stageBuf[b].bytes;
 	}
 	return sum * n * blocks * TBF_BLK;
 }
@@ -2103,22 +2078,17 @@ static int stageBuffers (tbf_engine* e, uint32_t n, uint32_t nblocks, hipStream_
 	if (int rc = drainStages (e))
 		return rc;
 	HIPCHK (hipStreamSynchronize (s));
-	/* producer stage -> reader stages of mid0, mid1, rvA, rvB, mid2 */
-	static const int prod[5] = {0, 1, 2, 3, 4}, rd[5][2] = {{1, -1}, {2, 4}, {3, -1}, {4, -1}, {5, -1}};
-	for (int b = 0; b < 5; b++) {
-		bool dbl = false;
-		for (int r : rd[b])
-			dbl = dbl || (r >= 0 && e->grp[r] != e->grp[prod[b]]);
-		e->stageDbl[b] = dbl;
-	}
 	const bool rv = chainReverb (e->cfg.chain_mode);
-	auto       k  = [&] (int b) { return (size_t)(e->stageDbl[b] ? 2 : 1); };
+	/* buffer b's elements of `elem` bytes per sample */
+	auto       k  = [&] (int b, size_t elem) { return (size_t)(stageBufAlternates (e, b) ? 2 : 1) * (stageBuf[b].bytes / elem); };
 	for (uint32_t blocks = want;;) {
 		e->mid0.release (), e->mid1.release (), e->mid2.release (), e->rvA.release (), e->rvB.release ();
 		const size_t need = (size_t)n * blocks * TBF_BLK;
-		const bool   ok   = (fx || !e->mid0.ensure (k (0) * 2 * need)) &&
-		                (!rv || (!e->mid1.ensure (k (1) * need) && !e->mid2.ensure (k (4) * need) &&
-		                         !e->rvA.ensure (k (2) * 2 * need) && !e->rvB.ensure (k (3) * 2 * need)));
+		const bool   ok   = (fx || !e->mid0.ensure (k (SB_MID0, sizeof (float)) * need)) &&
+		                (!rv || (!e->mid1.ensure (k (SB_MID1, sizeof (float)) * need) &&
+		                         !e->mid2.ensure (k (SB_MID2, sizeof (float)) * need) &&
+		                         !e->rvA.ensure (k (SB_RVA, sizeof (double)) * need) &&
+		                         !e->rvB.ensure (k (SB_RVB, sizeof (double)) * need)));
 		if (ok) {
 			e->stageBlocks = blocks;
 			e->stageN      = n;
@@ -2152,9 +2122,8 @@ static int launchStage (tbf_engine* e, const tbf_launch& P, int k, hipStream_t s
 	return rc;
 }
 
-/* one pipelined stage launch on its stream: the optional timing events around it, then the
- * events that later stages and chunks wait for */
-static int issueStage (tbf_engine* e, const tbf_launch& P, int k, hipStream_t sk, uint64_t cix)
+/* one stage launch on stream sk, between the optional timing events (tbf_debug_kernel_times) */
+static int timedLaunch (tbf_engine* e, const tbf_launch& P, int k, hipStream_t sk)
 {
 	hipEvent_t e0 = nullptr, e1 = nullptr;
 	if (e->timeOn) {
@@ -2169,6 +2138,15 @@ static int issueStage (tbf_engine* e, const tbf_launch& P, int k, hipStream_t sk
 		HIPCHK (hipEventRecord (e1, sk));
 		e->tev.push_back ({k, {e0, e1}});
 	}
+	return 0;
+}
+
+/* one pipelined stage launch on its stream, then the events that later stages and chunks
+ * wait for */
+static int issueStage (tbf_engine* e, const tbf_launch& P, int k, hipStream_t sk, uint64_t cix)
+{
+	if (int rc = timedLaunch (e, P, k, sk))
+		return rc;
 	HIPCHK (hipEventRecord (e->sdone[k], sk));
 	HIPCHK (hipEventRecord (e->pev[cix & 3][k], sk));
 	return 0;
@@ -2194,67 +2172,36 @@ static int issueDeferred (tbf_engine* e)
 	return issueStage (e, e->defP, TBF_NSTAGES - 1, sk, e->defCix);
 }
 
-static int renderBody (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, uint64_t stride, hipStream_t s,
-                       const tbf_event* ev, uint32_t nev);
-
-/* renderBody, and on every way out of it the held-back k_whirl: it never outlives the call */
-static int renderImpl (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, uint64_t stride, hipStream_t s,
-                       const tbf_event* ev = nullptr, uint32_t nev = 0)
+/* The phases of renderBody, in its order (n: the instances; s: the caller's stream; P: the
+ * call's launch parameters, whose per-chunk fields the phases fill). */
+/* retuned instances (tbf_instance_retune): fresh tone-generator state and the new
+ * template id, after every launch so far, before this call's first block */
+static int resetRetuned (tbf_engine* e, hipStream_t s)
 {
-	e->callS   = s;
-	e->outWait = false;
-	e->inWait  = false;
-	const int rc = renderBody (e, nblocks, dL, dR, stride, s, ev, nev);
-	if (e->defPending) { /* an error return between two chunks */
-		(void)issueDeferred (e);
-		(void)hipStreamWaitEvent (s, e->sdone[TBF_NSTAGES - 1], 0);
+	if (int rc = joinStages (e, s))
+		return rc;
+	for (uint32_t i : e->retuned) {
+		HIPCHK (hipMemcpyAsync (&e->st.p[i].mo, &e->inst[i].s0.mo, offsetof (tbf_mo_state, iirA),
+		                        hipMemcpyHostToDevice, s));
+		HIPCHK (hipMemcpyAsync (&e->st.p[i].tg, &e->inst[i].s0.tg, sizeof (tbf_tg_state),
+		                        hipMemcpyHostToDevice, s));
+		HIPCHK (hipMemcpyAsync (&e->cst.p[i].tpl, &e->inst[i].k.tpl, sizeof (uint32_t), hipMemcpyHostToDevice, s));
+		if (e->devCtl) { /* a fresh per-wheel control state and an empty program */
+			HIPCHK (hipMemsetAsync (e->tgc.p + i, 0, sizeof (tbf_tgc_state), s));
+			HIPCHK (hipMemsetAsync (e->prog.p + PSLOTS * i * SLOT, 0, PSLOTS * SLOT * sizeof (tbf_prog_entry), s));
+			e->pslot[i]         = 0;
+			e->hCtl[i].prog_off = (uint32_t)(PSLOTS * i * SLOT);
+			e->persistStale     = true;
+		}
 	}
-	return rc;
+	HIPCHK (hipStreamSynchronize (s));
+	e->retuned.clear ();
+	return 0;
 }
 
-static int renderBody (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, uint64_t stride, hipStream_t s,
-                       const tbf_event* ev, uint32_t nev)
+/* the launch fields that hold for the whole call */
+static int fillLaunch (tbf_engine* e, tbf_launch& P, uint32_t n, float* dL, float* dR, uint64_t stride)
 {
-	int rc = ensureDevice (e);
-	if (rc)
-		return rc;
-	const uint32_t n = (uint32_t)e->inst.size ();
-	if (n == 0 || nblocks == 0)
-		return 0;
-	if (chainFx (e->cfg.chain_mode) && !e->extIn)
-		return fail (-5, "internal: an effects-only render without an input");
-	if (!e->retuned.empty ()) {
-		/* retuned instances (tbf_instance_retune): fresh tone-generator state and the new
-		 * template id, after every launch so far, before this call's first block */
-		if ((rc = joinStages (e, s)))
-			return rc;
-		for (uint32_t i : e->retuned) {
-			HIPCHK (hipMemcpyAsync (&e->st.p[i].mo, &e->inst[i].s0.mo, offsetof (tbf_mo_state, iirA),
-			                        hipMemcpyHostToDevice, s));
-			HIPCHK (hipMemcpyAsync (&e->st.p[i].tg, &e->inst[i].s0.tg, sizeof (tbf_tg_state),
-			                        hipMemcpyHostToDevice, s));
-			HIPCHK (hipMemcpyAsync (&e->cst.p[i].tpl, &e->inst[i].k.tpl, sizeof (uint32_t), hipMemcpyHostToDevice, s));
-			if (e->devCtl) { /* a fresh per-wheel control state and an empty program */
-				HIPCHK (hipMemsetAsync (e->tgc.p + i, 0, sizeof (tbf_tgc_state), s));
-				HIPCHK (hipMemsetAsync (e->prog.p + PSLOTS * i * SLOT, 0, PSLOTS * SLOT * sizeof (tbf_prog_entry), s));
-				e->pslot[i]         = 0;
-				e->hCtl[i].prog_off = (uint32_t)(PSLOTS * i * SLOT);
-				e->persistStale     = true;
-			}
-		}
-		HIPCHK (hipStreamSynchronize (s));
-		e->retuned.clear ();
-	}
-	if (stride < (uint64_t)nblocks * TBF_BLK)
-		return fail (-22, "stride smaller than nblocks*128");
-	if (e->actAll || e->inAct.size () != n) { /* new instances: step every one */
-		e->inAct.assign (n, 1);
-		e->actList.resize (n);
-		for (uint32_t i = 0; i < n; i++)
-			e->actList[i] = i;
-		e->actAll = false;
-	}
-	tbf_launch P;
 	memset (&P, 0, sizeof (P));
 	P.bank      = e->bank.p;
 	P.tpls      = e->tplDesc.p;
@@ -2287,8 +2234,524 @@ static int renderBody (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, ui
 	if (e->cfg.chain_mode == TBF_CHAIN_TONEGEN && e->mixFixed.ensure (n))
 		return fail (-12, "out of device memory");
 	P.mixFixed = e->mixFixed.p;
-	/* inter-stage buffers for the longest chunk this call makes (stageBuffers): single, or
-	 * two sets by chunk parity (see the pipelining below) */
+	return 0;
+}
+
+/* the blocks of the chunk at b0: TBF_CHUNK at the most, or a steady chunk */
+static uint32_t chunkLength (const tbf_engine* e, uint32_t b0, uint32_t nblocks, uint32_t maxChunk, const tbf_event* ev,
+                             uint32_t evi, uint32_t nev)
+{
+	uint32_t want = std::min<uint32_t> (TBF_CHUNK, nblocks - b0);
+	if (nblocks - b0 > TBF_CHUNK && maxChunk > TBF_CHUNK && e->actList.empty () && !e->persistStale) {
+		/* no instance's control can change before the next event: a chunk without deltas,
+		 * up to steadyChunk blocks (as far as the stage buffers reach), ending at the next
+		 * event's block */
+		uint32_t w = std::min (maxChunk, nblocks - b0);
+		if (evi < nev)
+			w = std::min (w, ev[evi].block > b0 ? ev[evi].block - b0 : 0u);
+		if (w > TBF_CHUNK)
+			want = w;
+	}
+	return want;
+}
+
+/* device control, stage-group pipelining: a delta chunk pipelines like any other; its
+ * uploads and k_tgctl go on the first stage group's stream after the chunk before
+ * last (the previous user of this control region) has finished every stage (nst stages) */
+static int usWait (tbf_engine* e, Chunk& ck, hipStream_t s, int nst)
+{
+	if (ck.usWaited || !ck.dpipe)
+		return 0;
+	ck.usWaited = true;
+	if (!e->stagesBusy) { /* after the caller's stream (earlier non-pipelined work) */
+		HIPCHK (hipEventRecord (e->sjoin, s));
+		HIPCHK (hipStreamWaitEvent (ck.us, e->sjoin, 0));
+	}
+	HIPCHK (hipStreamWaitEvent (ck.us, e->pev[(ck.cix + 2) & 3][nst - 1], 0));
+	return 0;
+}
+
+/* Before the chunk's host control: the persistent control pool when it is stale (after
+ * instances were added or retuned), and under device control the wait for the chunk's
+ * staging set and its control region's persistent entries */
+static int refreshControlPool (tbf_engine* e, ChunkStaging& cs, Chunk& ck, uint32_t n, hipStream_t s, int nst)
+{
+	int rc;
+	if (e->devCtl && e->persistStale) {
+		e->ctlVer++; /* the regions refresh below */
+		e->persistStale = false;
+	}
+	if (e->persistStale) {
+		/* the persistent pool (entry i = instance i's current control and programme) as
+		 * of the START of this chunk: an instance without a delta at some block renders
+		 * that block with entry i, so it must not yet hold a later block's events.
+		 * Rare (after instances are added), so it syncs. */
+		if ((rc = joinStages (e, s)))
+			return rc;
+		HIPCHK (hipMemcpyAsync (e->ctl.p, e->hCtl.data (), n * sizeof (tbf_seg_ctl), hipMemcpyHostToDevice, s));
+		if (!e->devCtl) /* device control keeps the persistent programs on the device */
+			HIPCHK (hipMemcpyAsync (e->prog.p, e->hProg.data (), PERSIST (n) * sizeof (tbf_prog_entry),
+			                        hipMemcpyHostToDevice, s));
+		HIPCHK (hipStreamSynchronize (s));
+		e->persistStale = false;
+	}
+	if (e->devCtl) {
+		/* the set was the chunk before last's (its uploads are done once its event is) */
+		const auto w0 = std::chrono::steady_clock::now ();
+		HIPCHK (hipEventSynchronize (cs.upEv));
+		if (e->dbgPhases)
+			fprintf (stderr, "chunk %llu: staging wait %.3f ms\n", (unsigned long long)e->chunkSeq,
+			         std::chrono::duration<double, std::milli> (std::chrono::steady_clock::now () - w0).count ());
+	}
+	if (e->devCtl && e->regionVer[ck.rp] != e->ctlVer) {
+		/* this region's persistent entries: the control as of the START of this chunk (an
+		 * instance renders its blocks before its first delta with entry i) */
+		if (!ck.dpipe && (rc = joinStages (e, s)))
+			return rc;
+		if ((rc = usWait (e, ck, s, nst)))
+			return rc;
+		cs.hCtlPin.resize (n);
+		memcpy ((void*)cs.hCtlPin.data (), e->hCtl.data (), n * sizeof (tbf_seg_ctl));
+		HIPCHK (hipMemcpyAsync (e->ctl.p + ck.rp * CTL_REGION (n), cs.hCtlPin.data (), n * sizeof (tbf_seg_ctl),
+		                        hipMemcpyHostToDevice, ck.us));
+		e->regionVer[ck.rp] = e->ctlVer;
+	}
+	return 0;
+}
+
+/* The serial host control step, block by block: entry indices per (block, instance), new
+ * pool entries only where an instance's control changes.  Host control's one path; device
+ * control's for few active instances or a programme event.  May end the chunk early. */
+static int stepChunkSerial (tbf_engine* e, ChunkStaging& cs, Chunk& ck, uint32_t n, const tbf_event* ev)
+{
+	const size_t           dprogCap = DPROG_CAP (n);
+	std::vector<uint32_t>& cur      = e->curIdx;
+	uint32_t&              len      = ck.len;
+	for (; len < ck.want; len++) {
+		if (!e->devCtl && e->dProg.size () + (size_t)n * SLOT > dprogCap && len > 0)
+			break; /* delta program pool full: end the chunk here */
+		if (ck.delta && len >= TBF_CHUNK)
+			break; /* a chunk with deltas ends at TBF_CHUNK blocks, before the next block's events */
+		for (; ck.evBeg < ck.evEnd && ev[ck.evBeg].block <= ck.b0 + len; ck.evBeg++) {
+			if (int rc = applyEvent (e, ev[ck.evBeg]))
+				return rc;
+			markActive (e, ev[ck.evBeg].inst);
+		}
+		/* only the instances whose control may still change are stepped: one that
+		 * steps to no change stays unchanged until an event touches it */
+		const bool hadDelta = ck.delta;
+		size_t     keep     = 0;
+		for (size_t a = 0; a < e->actList.size (); a++) {
+			const uint32_t i = e->actList[a];
+			bool           pc;
+			tbf_tgc_rec    rec;
+			if (stepControl (e, cs, i, pc, e->devCtl ? &rec : nullptr)) {
+				tbf_seg_ctl c = e->hCtl[i];
+				if (e->devCtl) {
+					/* a stepped delta gets its own program slot, which k_tgctl fills; the
+					 * others play the program before them */
+					if (pc) {
+						c.prog_off = (uint32_t)(PERSIST (n) + ((size_t)ck.rp * n * TBF_CHUNK + cs.dCtl.size ()) * SLOT);
+						if (!e->stepped[i]) {
+							e->stepped[i] = 1;
+							cs.hCtlInst.push_back (i);
+						}
+					} else {
+						memset (&rec, 0, sizeof (rec));
+						if (cur[i] >= n)
+							c.prog_off = cs.dCtl[cur[i] - n].prog_off;
+					}
+					if (!e->dhas[i]) {
+						e->dhas[i] = 1;
+						cs.hDInst.push_back (i);
+					}
+					cs.hFull.push_back (c); /* every delta a full entry on this path */
+					rec.full = (uint32_t)cs.hFull.size ();
+					cs.hRec.push_back (rec);
+				} else if (pc) {
+					c.prog_off = (uint32_t)(PERSIST (n) + e->dProg.size ());
+					e->dProg.insert (e->dProg.end (), e->hProg.begin () + PSLOTS * i * SLOT,
+					                 e->hProg.begin () + PSLOTS * i * SLOT + 1 + c.prog_len);
+				} else if (cur[i] >= n)
+					c.prog_off = cs.dCtl[cur[i] - n].prog_off; /* program of the previous delta */
+				cur[i] = n + (uint32_t)cs.dCtl.size ();
+				cs.dCtl.push_back (c);
+				e->chg[i] = 1;
+				ck.delta  = true;
+				e->actList[keep++] = i;
+			} else
+				e->inAct[i] = 0;
+		}
+		e->actList.resize (keep);
+		/* entry index table: written only once the chunk has a delta (before that
+		 * every row is the identity) */
+		if (ck.delta) {
+			if (!hadDelta)
+				for (uint32_t r = 0; r < len; r++)
+					for (uint32_t i = 0; i < n; i++)
+						cs.hIdx[(size_t)r * n + i] = i;
+			std::copy (cur.begin (), cur.end (), cs.hIdx.begin () + (size_t)len * n);
+		}
+	}
+	return 0;
+}
+
+/* The chunk's host control: its events [evBeg, evEnd) found and checked, then stepped by
+ * one of stepChunkFront, stepChunkParallel and stepChunkSerial into a cleared staging set.
+ * Leaves ck.len, ck.delta, ck.dfront, and ck.evBeg behind the events applied. */
+static int hostControl (tbf_engine* e, ChunkStaging& cs, Chunk& ck, uint32_t n, const tbf_event* ev, uint32_t nev)
+{
+	const uint32_t b0 = ck.b0, want = ck.want, evi = ck.evBeg;
+	cs.dCtl.clear (), cs.hRec.clear (), cs.hMsg.clear (), cs.hGain.clear (), cs.hWh.clear ();
+	cs.hCtlInst.clear (), cs.hDInst.clear (), cs.hFull.clear ();
+	e->dSeg.clear (), e->dProg.clear ();
+	e->stepped.assign (n, 0), e->dhas.assign (n, 0);
+	cs.hIdx.resize ((size_t)want * n);
+	e->curIdx.resize (n);
+	for (uint32_t i = 0; i < n; i++)
+		e->curIdx[i] = i;
+	const auto hc0 = std::chrono::steady_clock::now ();
+	/* the chunk's events (sorted by block: a binary search), checked in parallel (a serial
+	 * pass cost ~0.5 ms at 524k events) */
+	const uint32_t evEnd = ck.evEnd = (uint32_t)(
+	    std::partition_point (ev + evi, ev + nev, [&] (const tbf_event& x) { return x.block < b0 + want; }) - ev);
+	/* a chunk of note, drawbar and switch events only (frontParam) on clean instances: the
+	 * device front end */
+	bool       progEv = false, badEv = false, front = false;
+	const bool frontCand = e->devCtl && ck.dpipe && e->frontOn && evEnd - evi >= e->frontMin && frontCleanAll (e);
+	const auto sc0       = std::chrono::steady_clock::now ();
+	scanChunk (n, b0, ev, evi, evEnd, frontCand ? e->fclean.data () : nullptr, progEv, badEv, front, e->scan);
+	if (e->dbgPhases)
+		fprintf (stderr, "chunk %llu: clean %.3f ms, scan %.3f ms (%u events)\n", (unsigned long long)e->chunkSeq,
+		         std::chrono::duration<double, std::milli> (sc0 - hc0).count (),
+		         std::chrono::duration<double, std::milli> (std::chrono::steady_clock::now () - sc0).count (), evEnd - evi);
+	if (badEv)
+		return fail (-22, "event for a bad instance");
+	int rc;
+	if (frontCand && front && !progEv) {
+		if ((rc = stepChunkFront (e, cs, ck, n)))
+			return rc;
+		ck.dfront = true;
+		e->frontChunks[0]++;
+		if (e->dbgPhases)
+			fprintf (stderr, "chunk %llu: device front end, %u note events\n", (unsigned long long)e->chunkSeq,
+			         cs.hFevOff[n]);
+	} else {
+		if (evEnd > evi)
+			e->frontChunks[1]++;
+		/* device control with many instances to step (active now, or touched by this chunk's
+		 * events): the chunk's host control on worker threads (serial when a programme change
+		 * is among the events) */
+		if (e->devCtl && !progEv && e->parCtl && e->actList.size () + (evEnd - evi) >= 1024)
+			rc = stepChunkParallel (e, cs, ck, n, ev);
+		else
+			rc = stepChunkSerial (e, cs, ck, n, ev);
+		if (rc)
+			return rc;
+	}
+	e->hostCtlNs += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds> (
+	                    std::chrono::steady_clock::now () - hc0)
+	                    .count ();
+	e->hostCtlBlocks += ck.len;
+	if (ck.delta && ck.len > TBF_CHUNK)
+		return fail (-5, "internal: a chunk with control deltas longer than 64 blocks");
+	return 0;
+}
+
+/* a delta chunk's uploads: control deltas, delta programs, index table, whirl sets (P.whSets) */
+static int uploadDeltas (tbf_engine* e, ChunkStaging& cs, Chunk& ck, tbf_launch& P, hipStream_t s)
+{
+	const uint32_t n = P.nInst;
+	int            rc;
+	if (ck.delta) {
+		/* device control: both regions' delta slots, sized once for a delta per
+		 * instance and block (growProg synchronizes the device when it grows) */
+		if (e->devCtl && (rc = growProg (e, PERSIST (n) + 2 * (size_t)n * TBF_CHUNK * SLOT, n)))
+			return rc;
+		if ((rc = usWait (e, ck, s, tbf_chain_stages (P.chain))))
+			return rc;
+		if (!e->devCtl) /* device control: k_tgctl writes the deltas' entries (records + full entries) */
+			HIPCHK (hipMemcpyAsync (e->ctl.p + ck.rp * CTL_REGION (n) + n, cs.dCtl.data (),
+			                        cs.dCtl.size () * sizeof (tbf_seg_ctl), hipMemcpyHostToDevice, ck.us));
+		if (!e->dProg.empty ())
+			HIPCHK (hipMemcpyAsync (e->prog.p + PERSIST (n), e->dProg.data (),
+			                        e->dProg.size () * sizeof (tbf_prog_entry), hipMemcpyHostToDevice, ck.us));
+		if (!ck.dfront) /* (k_front writes the index table) */
+			HIPCHK (hipMemcpyAsync (e->ctlIdx.p + (size_t)ck.rp * n * TBF_CHUNK, cs.hIdx.data (),
+			                        (size_t)ck.len * n * sizeof (uint32_t), hipMemcpyHostToDevice, ck.us));
+	}
+	P.whSets = nullptr;
+	if (ck.delta && !cs.hWh.empty ()) {
+		/* the whirl parameter sets of the chunk's deltas, by region parity like the records */
+		if (cs.dwh.cap < cs.hWh.size ())
+			HIPCHK (hipDeviceSynchronize ()); /* growing: nothing may still read the old buffer */
+		if (cs.dwh.ensure (std::max<size_t> (cs.hWh.size (), 64)))
+			return fail (-12, "out of device memory (whirl parameter sets)");
+		HIPCHK (hipMemcpyAsync (cs.dwh.p, cs.hWh.data (), cs.hWh.size () * sizeof (tbf_wh_params), hipMemcpyHostToDevice, ck.us));
+		P.whSets = cs.dwh.p;
+	}
+	return 0;
+}
+
+/* the chunk's launch fields: stage buffers (`need` samples a set), control region, blocks */
+static void chunkLaunch (tbf_engine* e, const Chunk& ck, tbf_launch& P, size_t need)
+{
+	const uint32_t n = P.nInst, len = ck.len;
+	auto at = [&] (int b) { return stageBufAlternates (e, b) ? (size_t)ck.bset * need : (size_t)0; };
+	P.mid0 = e->mid0.p ? e->mid0.p + 2 * at (SB_MID0) : nullptr;
+	P.mid1 = e->mid1.p ? e->mid1.p + at (SB_MID1) : nullptr;
+	P.mid2 = e->mid2.p ? e->mid2.p + at (SB_MID2) : nullptr;
+	P.rvA  = e->rvA.p ? e->rvA.p + 2 * at (SB_RVA) : nullptr;
+	P.rvB  = e->rvB.p ? e->rvB.p + 2 * at (SB_RVB) : nullptr;
+	P.prog      = e->prog.p;
+	P.ctl       = e->ctl.p + ck.rp * CTL_REGION (n);
+	P.ctlIdx    = ck.delta ? e->ctlIdx.p + (size_t)ck.rp * n * TBF_CHUNK : nullptr;
+	P.nBlocks   = len;
+	/* k_tonegen block ranges (chunks without deltas) for small batches: about 2048 waves,
+	 * ranges of >= 4 blocks (each range after the first renders one warm-up block).  At
+	 * 4096 instances a split measured no gain (0.73 ms alone either way: the kernel is
+	 * bound by its bank gathers and VALU, not by waves in flight). */
+	P.tgSplit = e->tgSplit >= 0 ? (uint32_t)std::max (e->tgSplit, 1)
+	                            : std::max (1u, std::min ({8u, 2048u / std::max (n, 1u), len / 4}));
+	P.tgSplit = std::min (P.tgSplit, std::max (len, 1u));
+	P.outOffset = (uint64_t)ck.b0 * TBF_BLK;
+	P.extOffset = (uint64_t)ck.b0 * TBF_BLK;
+	P.nCtlInst  = 0;
+}
+
+/* device control: the chunk's control kernels on us, ahead of k_tonegen, with their uploads:
+ * k_front (a front-end chunk: the records, messages and index table from the key states and
+ * events) and k_tgctl (the stepped blocks' programs); then the event that frees the set */
+static int controlKernels (tbf_engine* e, ChunkStaging& cs, Chunk& ck, tbf_launch& P)
+{
+	const uint32_t    n = P.nInst, len = ck.len;
+	const bool        dfront = ck.dfront;
+	const hipStream_t us     = ck.us;
+	int               rc;
+	if (e->devCtl && (dfront ? ck.delta : !cs.hDInst.empty ())) {
+		/* the device buffers are the staging set's: k_tgctl of the chunk before last (same
+		 * stream, or the caller's stream when not pipelined) read the other set */
+		const size_t nRec  = dfront ? (size_t)n * len : cs.hRec.size ();
+		const size_t nMsg  = dfront ? 2 * (size_t)cs.hFevOff[n] : cs.hMsg.size ();
+		const size_t nGain = dfront ? (size_t)e->frontGain : cs.hGain.size ();
+		if (cs.drec.cap < nRec || cs.dmsg.cap < nMsg || cs.dctlInst.cap < cs.hDInst.size () || cs.dgain.cap < nGain ||
+		    cs.dfull.cap < (dfront ? (size_t)n * len : cs.hFull.size ()))
+		{
+			if (e->dbgPhases)
+				fprintf (stderr, "chunk %llu: control record buffers grow (device sync)\n", (unsigned long long)e->chunkSeq);
+			HIPCHK (hipDeviceSynchronize ()); /* growing: nothing may still read the old buffers */
+		}
+		const size_t nFull = dfront ? (size_t)n * len : cs.hFull.size (); /* k_front writes its effect entries */
+		if (cs.drec.ensure (std::max<size_t> (nRec, 1)) || cs.dmsg.ensure (std::max<size_t> (nMsg, 1)) ||
+		    cs.dgain.ensure (std::max<size_t> (nGain, 27)) ||
+		    cs.dctlInst.ensure (cs.hDInst.size ()) || cs.dfull.ensure (std::max<size_t> (nFull, 1)))
+			return fail (-12, "out of device memory (control records)");
+		P.rec   = cs.drec.p;
+		P.msgs  = cs.dmsg.p;
+		P.gains = cs.dgain.p;
+		P.fulls = cs.dfull.p;
+		if (dfront) {
+			if (cs.dfront.cap < n || cs.dfev.cap < cs.hFev.size () || cs.dfval.cap < cs.hFev.size () ||
+			    cs.dfoff.cap < (size_t)n + 1 || e->dident.cap < n)
+				HIPCHK (hipDeviceSynchronize ()); /* growing: nothing may still read the old buffers */
+			if (cs.dfront.ensure (n) || cs.dfev.ensure (cs.hFev.size ()) || cs.dfval.ensure (cs.hFev.size ()) ||
+			    cs.dfoff.ensure ((size_t)n + 1) || e->dident.ensure (n))
+				return fail (-12, "out of device memory (front end)");
+			if (e->hIdent.size () != n) {
+				e->hIdent.resize (n);
+				for (uint32_t i = 0; i < n; i++)
+					e->hIdent[i] = i;
+				HIPCHK (hipMemcpy (e->dident.p, e->hIdent.data (), (size_t)n * 4, hipMemcpyHostToDevice));
+			}
+			HIPCHK (hipMemcpyAsync (cs.dfront.p, cs.hFront.data (), (size_t)n * sizeof (tbf_front_state), hipMemcpyHostToDevice, us));
+			HIPCHK (hipMemcpyAsync (cs.dfev.p, cs.hFev.data (), cs.hFev.size () * 4, hipMemcpyHostToDevice, us));
+			HIPCHK (hipMemcpyAsync (cs.dfoff.p, cs.hFevOff.data (), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, us));
+			HIPCHK (hipMemcpyAsync (cs.dfval.p, cs.hFevVal.data (), cs.hFev.size () * 4, hipMemcpyHostToDevice, us));
+			P.front   = cs.dfront.p;
+			P.fev     = cs.dfev.p;
+			P.fevVal  = cs.dfval.p;
+			P.fevOff  = cs.dfoff.p;
+			P.keyComp = e->dkeyComp.p;
+			if ((rc = tbf_launch_front (&P, us)))
+				return fail (rc, std::string ("k_front launch failed: ") + hipGetErrorString (hipGetLastError ()));
+		}
+		if (!dfront && e->dSeg.empty ())
+			HIPCHK (hipMemcpyAsync (cs.drec.p, cs.hRec.data (), cs.hRec.size () * sizeof (tbf_tgc_rec),
+			                        hipMemcpyHostToDevice, us));
+		for (const auto& g : e->dSeg)
+			if (!dfront && g.second)
+				HIPCHK (hipMemcpyAsync (cs.drec.p + g.first, cs.hRec.data () + g.first,
+				                        g.second * sizeof (tbf_tgc_rec), hipMemcpyHostToDevice, us));
+		if (!dfront && !cs.hMsg.empty ())
+			HIPCHK (hipMemcpyAsync (cs.dmsg.p, cs.hMsg.data (), cs.hMsg.size () * sizeof (uint16_t),
+			                        hipMemcpyHostToDevice, us));
+		if (!dfront && !cs.hGain.empty ())
+			HIPCHK (hipMemcpyAsync (cs.dgain.p, cs.hGain.data (), cs.hGain.size () * sizeof (float),
+			                        hipMemcpyHostToDevice, us));
+		if (!dfront && !cs.hFull.empty ())
+			HIPCHK (hipMemcpyAsync (cs.dfull.p, cs.hFull.data (), cs.hFull.size () * sizeof (tbf_seg_ctl),
+			                        hipMemcpyHostToDevice, us));
+		if (!dfront)
+			HIPCHK (hipMemcpyAsync (cs.dctlInst.p, cs.hDInst.data (), cs.hDInst.size () * 4, hipMemcpyHostToDevice, us));
+		P.tgc      = e->tgc.p;
+		P.ctlInst  = dfront ? e->dident.p : cs.dctlInst.p;
+		P.nCtlInst = dfront ? n : (uint32_t)cs.hDInst.size ();
+		P.progBase = (uint32_t)(PERSIST (n) + (size_t)ck.rp * n * TBF_CHUNK * SLOT);
+		P.coff     = e->coff.p;
+		P.contrib  = e->contrib.p;
+		P.ctlNw    = e->ctlNw;
+		if ((rc = tbf_launch_tgctl (&P, us)))
+			return fail (rc, std::string ("k_tgctl launch failed: ") + hipGetErrorString (hipGetLastError ()));
+	}
+	if (e->devCtl)
+		HIPCHK (hipEventRecord (cs.upEv, us)); /* this parity's staging is free after it */
+	if (ck.usWaited && ck.piped) /* the stage streams now follow the uploads on us */
+		e->stagesBusy = true;
+	return 0;
+}
+
+/* The chunk's stage launches (aheadOn: k_rv_pre ahead is possible in this call; more: a
+ * chunk follows in it).  Not pipelined: one after another on the caller's stream.
+ * Pipelined: every chunk's stage k on stream gs[grp[k]], so a stage runs as soon as this
+ * chunk's previous stage and the previous chunk's same stage are done, whatever the later
+ * stages of the previous chunk are doing.  A stage buffer of this chunk's parity was last
+ * read by the chunk before last: its producer waits for those readers (stageBuf) when they
+ * run on another stream. */
+static int issueChunk (tbf_engine* e, const Chunk& ck, tbf_launch& P, hipStream_t s, bool aheadOn, bool more)
+{
+	const int      nst = tbf_chain_stages (P.chain);
+	/* an effects-only chain starts at stage 1, which reads the caller's rows */
+	const int      st0 = tbf_chain_first_stage (e->cfg.chain_mode);
+	int            rc;
+	/* k_rv_pre ahead: this chunk's k_rv_pre goes in front of the held-back k_whirl of the
+	 * chunk before when neither chunk has control deltas or uploads and this one takes
+	 * k_rv_core_lds (a shorter chunk's k_rv_pre is too small to matter); its own k_whirl
+	 * is held back when a chunk follows in this call.  Anything else runs as before, behind
+	 * the held-back launch. */
+	const bool plain = aheadOn && ck.piped && !ck.delta && !ck.usWaited && nst == TBF_NSTAGES;
+	const bool ahead = plain && e->defPending && P.rvLds && ck.len >= RVL_MIN_BLOCKS;
+	if (!ahead && (rc = issueDeferred (e)))
+		return rc;
+	if (!ck.piped) {
+		for (int k = st0; k < nst; k++)
+			if ((rc = timedLaunch (e, P, k, s)))
+				return rc;
+		return 0;
+	}
+	auto strm = [&] (int k) { return e->gs[e->grp[k == 2 && ahead ? TBF_NSTAGES - 1 : k]]; };
+	for (int k = st0; k < nst; k++) {
+		hipStream_t sk = strm (k);
+		if (k == nst - 1 && plain && more) { /* held back for the next chunk's k_rv_pre */
+			e->defP       = P;
+			e->defCix     = ck.cix;
+			e->defPending = true;
+			break;
+		}
+		/* after the caller's stream (uploads, earlier chunks).  A generator needs that only
+		 * when the stage streams are idle; a stage that reads the caller's input needs it on
+		 * every call: the input is complete only where the caller's stream reaches the call
+		 * (later chunks of the call follow the first on the stage's stream) */
+		if (k == st0 && (!e->stagesBusy || (st0 > 0 && !e->inWait))) {
+			HIPCHK (hipEventRecord (e->sjoin, s));
+			HIPCHK (hipStreamWaitEvent (sk, e->sjoin, 0));
+			e->inWait = true;
+		}
+		if (k == nst - 1 && !e->outWait) { /* the output stage writes the caller's buffers */
+			HIPCHK (hipEventRecord (e->sjoin, s));
+			HIPCHK (hipStreamWaitEvent (sk, e->sjoin, 0));
+			e->outWait = true;
+		}
+		if (k > 0 && strm (k - 1) != sk)
+			HIPCHK (hipStreamWaitEvent (sk, e->sdone[k - 1], 0));
+		if (k == 2 && ahead) {
+			/* behind k_rv_core of the chunk before (sdone[3] is still its event): that
+			 * puts the launch in the k_rv_post phase, orders it behind that chunk's
+			 * k_rv_pre (the stage's state) and keeps rvA a single buffer */
+			HIPCHK (hipStreamWaitEvent (sk, e->sdone[3], 0));
+		} else
+			for (const StageBuf& b : stageBuf) /* the readers of the buffer stage k writes */
+				for (int r : b.rd)
+					if (b.prod == k && r >= 0 && r < nst && strm (r) != sk)
+						HIPCHK (hipStreamWaitEvent (sk, e->pev[(ck.cix + 2) & 3][r], 0));
+		P.preAhead = k == 2 && ahead;
+		if ((rc = issueStage (e, P, k, sk, ck.cix)))
+			return rc;
+		if (k == 2 && ahead) {
+			e->aheadCount++;
+			if ((rc = issueDeferred (e))) /* k_whirl of the chunk before, behind it */
+				return rc;
+		}
+	}
+	P.preAhead = 0;
+	e->stagesBusy = true;
+	return 0;
+}
+
+/* after a chunk with control deltas: the instances' final entries become their current
+ * (pool 0..n-1) control for the next chunk (one-shots cleared).  Device control: k_tgctl
+ * left each stepped instance's last program in its other persistent slot; the regions'
+ * persistent entries refresh at the start of the chunks that use them.  Host control:
+ * uploaded now, and the staging is reused, so it synchronizes. */
+static int endDelta (tbf_engine* e, ChunkStaging& cs, uint32_t n, hipStream_t s)
+{
+	uint32_t lo = n, hi = 0;
+	for (uint32_t i = 0; i < n; i++)
+		if (e->chg[i]) {
+			e->hCtl[i].whRevOption = -1;
+			e->hCtl[i].whSet       = 0;
+			/* a one-shot in the chunk's last block left the instance dirty only so that the
+			 * next block clears it: the entry it ends with is cleared here already */
+			Instance& in = e->inst[i];
+			if (in.ctlDirty && !in.progDirty && in.revOpt < 0 && !in.whDirty)
+				in.ctlDirty = false;
+			lo                     = std::min (lo, i);
+			hi                     = std::max (hi, i + 1);
+			e->chg[i]              = 0;
+		}
+	if (e->devCtl) {
+		for (uint32_t i : cs.hCtlInst) {
+			e->pslot[i]         = (uint8_t)((e->pslot[i] + 1) % PSLOTS);
+			e->hCtl[i].prog_off = (uint32_t)((PSLOTS * i + e->pslot[i]) * SLOT);
+		}
+		e->ctlVer++;
+		return 0;
+	}
+	HIPCHK (hipMemcpyAsync (e->ctl.p, e->hCtl.data (), n * sizeof (tbf_seg_ctl), hipMemcpyHostToDevice, s));
+	if (hi > lo)
+		HIPCHK (hipMemcpyAsync (e->prog.p + lo * PSLOTS * SLOT, e->hProg.data () + lo * PSLOTS * SLOT,
+		                        (size_t)(hi - lo) * PSLOTS * SLOT * sizeof (tbf_prog_entry), hipMemcpyHostToDevice, s));
+	HIPCHK (hipStreamSynchronize (s));
+	return 0;
+}
+
+/* One render call: prepare it, then chunk by chunk plan the chunk (Chunk), run its host
+ * control into its staging set, upload, issue, and take the deltas over; then the tail. */
+static int renderBody (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, uint64_t stride, hipStream_t s,
+                       const tbf_event* ev, uint32_t nev)
+{
+	int rc = ensureDevice (e);
+	if (rc)
+		return rc;
+	const uint32_t n = (uint32_t)e->inst.size ();
+	if (n == 0 || nblocks == 0)
+		return 0;
+	if (chainFx (e->cfg.chain_mode) && !e->extIn)
+		return fail (-5, "internal: an effects-only render without an input");
+	if (!e->retuned.empty () && (rc = resetRetuned (e, s)))
+		return rc;
+	if (stride < (uint64_t)nblocks * TBF_BLK)
+		return fail (-22, "stride smaller than nblocks*128");
+	if (e->actAll || e->inAct.size () != n) { /* new instances: step every one */
+		e->inAct.assign (n, 1);
+		e->actList.resize (n);
+		for (uint32_t i = 0; i < n; i++)
+			e->actList[i] = i;
+		e->actAll = false;
+	}
+	tbf_launch P;
+	if ((rc = fillLaunch (e, P, n, dL, dR, stride)))
+		return rc;
+	/* inter-stage buffers for the longest chunk this call makes: single, or two sets by chunk parity */
 	if ((rc = stageBuffers (e, n, nblocks, s)))
 		return rc;
 	const size_t   need     = (size_t)n * e->stageBlocks * TBF_BLK;
@@ -2301,529 +2764,68 @@ static int renderBody (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, ui
 	 * caller's stream after joining.  With tbf_debug_kernel_times on, each launch is
 	 * bracketed by events on its own stream (durations then include the overlap with the
 	 * other streams' kernels). */
-	const bool   pipe  = e->pipeline && P.chain == TBF_CHAIN_FULL && !e->timeSerial;
-	/* an effects-only chain starts at stage 1, which reads the caller's rows */
-	const int    st0   = tbf_chain_first_stage (e->cfg.chain_mode);
+	const bool pipe = e->pipeline && P.chain == TBF_CHAIN_FULL && !e->timeSerial;
 	/* k_rv_pre ahead (tbf_engine.preAhead): with the default stage groups only */
 	static const int defGrp[TBF_NSTAGES] = {0, 0, 1, 1, 1, 2};
 	const bool       aheadOn = e->preAhead && pipe && std::equal (defGrp, defGrp + TBF_NSTAGES, e->grp);
-	const size_t dprogCap = DPROG_CAP (n);
+	const int        nst     = tbf_chain_stages (P.chain);
 	e->chg.assign (n, 0);
-	/* after a chunk with control deltas: the instances' final entries become their current
-	 * (pool 0..n-1) control for the next chunk (one-shots cleared).  Device control: k_tgctl
-	 * left each stepped instance's last program in its other persistent slot; the regions'
-	 * persistent entries refresh at the start of the chunks that use them.  Host control:
-	 * uploaded now, and the staging is reused, so it synchronizes. */
-	auto endDelta = [&] () -> int {
-		uint32_t lo = n, hi = 0;
-		for (uint32_t i = 0; i < n; i++)
-			if (e->chg[i]) {
-				e->hCtl[i].whRevOption = -1;
-				e->hCtl[i].whSet       = 0;
-				/* a one-shot in the chunk's last block left the instance dirty only so that the
-				 * next block clears it: the entry it ends with is cleared here already */
-				Instance& in = e->inst[i];
-				if (in.ctlDirty && !in.progDirty && in.revOpt < 0 && !in.whDirty)
-					in.ctlDirty = false;
-				lo                     = std::min (lo, i);
-				hi                     = std::max (hi, i + 1);
-				e->chg[i]              = 0;
-			}
-		if (e->devCtl) {
-			for (uint32_t i : e->hCtlInst) {
-				e->pslot[i]         = (uint8_t)((e->pslot[i] + 1) % PSLOTS);
-				e->hCtl[i].prog_off = (uint32_t)((PSLOTS * i + e->pslot[i]) * SLOT);
-			}
-			e->ctlVer++;
-			return 0;
-		}
-		HIPCHK (hipMemcpyAsync (e->ctl.p, e->hCtl.data (), n * sizeof (tbf_seg_ctl), hipMemcpyHostToDevice, s));
-		if (hi > lo)
-			HIPCHK (hipMemcpyAsync (e->prog.p + lo * PSLOTS * SLOT, e->hProg.data () + lo * PSLOTS * SLOT,
-			                        (size_t)(hi - lo) * PSLOTS * SLOT * sizeof (tbf_prog_entry), hipMemcpyHostToDevice, s));
-		HIPCHK (hipStreamSynchronize (s));
-		return 0;
-	};
 	uint32_t b0 = 0, evi = 0;
 	while (b0 < nblocks) {
-		/* host control for the chunk, block by block: entry indices per (block, instance),
-		 * new pool entries only where an instance's control changes */
-		uint32_t want = std::min<uint32_t> (TBF_CHUNK, nblocks - b0);
-		if (nblocks - b0 > TBF_CHUNK && maxChunk > TBF_CHUNK && e->actList.empty () && !e->persistStale) {
-			/* no instance's control can change before the next event: a chunk without deltas,
-			 * up to steadyChunk blocks (as far as the stage buffers reach), ending at the next
-			 * event's block */
-			uint32_t w = std::min (maxChunk, nblocks - b0);
-			if (evi < nev)
-				w = std::min (w, ev[evi].block > b0 ? ev[evi].block - b0 : 0u);
-			if (w > TBF_CHUNK)
-				want = w;
-		}
-		const uint64_t cix  = e->chunkSeq++;
-		const bool     par  = (cix & 1) != 0;
-		const uint32_t bset = (uint32_t)(cix & 1); /* stage-buffer set of this chunk */
-		const int      rp   = e->devCtl ? (int)par : 0; /* control region of this chunk */
-		/* device control, stage-group pipelining: a delta chunk pipelines like any other; its
-		 * uploads and k_tgctl go on the first stage group's stream after the chunk before
-		 * last (the previous user of this control region) has finished every stage */
-		const bool     dpipe = e->devCtl && pipe;
-		hipStream_t    us    = dpipe ? e->gs[0] : s;
-		bool           usWaited = false;
-		auto           usWait   = [&] () -> int {
-            if (usWaited || !dpipe)
-                return 0;
-            usWaited = true;
-            if (!e->stagesBusy) { /* after the caller's stream (earlier non-pipelined work) */
-                HIPCHK (hipEventRecord (e->sjoin, s));
-                HIPCHK (hipStreamWaitEvent (us, e->sjoin, 0));
-            }
-            HIPCHK (hipStreamWaitEvent (us, e->pev[(cix + 2) & 3][tbf_chain_stages (P.chain) - 1], 0));
-            return 0;
-		};
-		if (e->devCtl && e->persistStale) {
-			e->ctlVer++; /* the regions refresh below */
-			e->persistStale = false;
-		}
-		if (e->persistStale) {
-			/* the persistent pool (entry i = instance i's current control and programme) as
-			 * of the START of this chunk: an instance without a delta at some block renders
-			 * that block with entry i, so it must not yet hold a later block's events.
-			 * Rare (after instances are added), so it syncs. */
-			if ((rc = joinStages (e, s)))
-				return rc;
-			HIPCHK (hipMemcpyAsync (e->ctl.p, e->hCtl.data (), n * sizeof (tbf_seg_ctl), hipMemcpyHostToDevice, s));
-			if (!e->devCtl) /* device control keeps the persistent programs on the device */
-				HIPCHK (hipMemcpyAsync (e->prog.p, e->hProg.data (), PERSIST (n) * sizeof (tbf_prog_entry),
-				                        hipMemcpyHostToDevice, s));
-			HIPCHK (hipStreamSynchronize (s));
-			e->persistStale = false;
-		}
-		if (e->devCtl) {
-			/* staging of the chunk before last (its uploads are done once its event is) */
-			e->dCtl.swap (e->dCtlB);
-			e->hRec.swap (e->hRecB);
-			e->hMsg.swap (e->hMsgB);
-			e->hGain.swap (e->hGainB);
-			e->hWh.swap (e->hWhB);
-			e->hCtlInst.swap (e->hCtlInstB);
-			e->hDInst.swap (e->hDInstB);
-			e->hFull.swap (e->hFullB);
-			e->hFront.swap (e->hFrontB);
-			e->hFev.swap (e->hFevB);
-			e->hFevVal.swap (e->hFevValB);
-			e->hFevOff.swap (e->hFevOffB);
-			e->hIdx.swap (e->hIdxB);
-			e->hCtlPin.swap (e->hCtlPinB);
-			std::swap (e->upEv, e->upEvB);
-			const auto w0 = std::chrono::steady_clock::now ();
-			HIPCHK (hipEventSynchronize (e->upEv));
-			if (getenv ("TBF_DEBUG_HOST_PHASES"))
-				fprintf (stderr, "chunk %llu: staging wait %.3f ms\n", (unsigned long long)e->chunkSeq,
-				         std::chrono::duration<double, std::milli> (std::chrono::steady_clock::now () - w0).count ());
-		}
-		if (e->devCtl && e->regionVer[rp] != e->ctlVer) {
-			/* this region's persistent entries: the control as of the START of this chunk (an
-			 * instance renders its blocks before its first delta with entry i) */
-			if (!dpipe && (rc = joinStages (e, s)))
-				return rc;
-			if ((rc = usWait ()))
-				return rc;
-			e->hCtlPin.resize (n);
-			memcpy ((void*)e->hCtlPin.data (), e->hCtl.data (), n * sizeof (tbf_seg_ctl));
-			HIPCHK (hipMemcpyAsync (e->ctl.p + rp * CTL_REGION (n), e->hCtlPin.data (), n * sizeof (tbf_seg_ctl),
-			                        hipMemcpyHostToDevice, us));
-			e->regionVer[rp] = e->ctlVer;
-		}
-		e->dCtl.clear ();
-		e->dSeg.clear ();
-		e->dProg.clear ();
-		e->hRec.clear ();
-		e->hMsg.clear ();
-		e->hGain.clear ();
-		e->hWh.clear ();
-		e->hCtlInst.clear ();
-		e->hDInst.clear ();
-		e->hFull.clear ();
-		e->stepped.assign (n, 0);
-		e->dhas.assign (n, 0);
-		e->hIdx.resize ((size_t)want * n);
-		std::vector<uint32_t>& cur = e->curIdx;
-		cur.resize (n);
-		for (uint32_t i = 0; i < n; i++)
-			cur[i] = i;
-		bool       delta = false;
-		uint32_t   len   = 0;
-		const auto hc0   = std::chrono::steady_clock::now ();
-		/* device control with many active instances: the chunk's host control on worker
-		 * threads (serial when a programme change is among the events) */
-		/* the chunk's events (sorted by block: a binary search), checked in parallel (a serial
-		 * pass cost ~0.5 ms at 524k events) */
-		uint32_t evEnd = evi;
-		{
-			uint32_t lo = evi, hi = nev;
-			while (lo < hi) {
-				const uint32_t mid = lo + (hi - lo) / 2;
-				if (ev[mid].block < b0 + want)
-					lo = mid + 1;
-				else
-					hi = mid;
-			}
-			evEnd = lo;
-		}
-		/* a chunk of note, drawbar and switch events only (frontParam) on clean instances: the
-		 * device front end */
-		bool       progEv = false, badEv = false, front = false;
-		const bool frontCand = e->devCtl && dpipe && e->frontOn && evEnd - evi >= e->frontMin && frontCleanAll (e);
-		ChunkScan& cs        = e->scan;
-		const auto sc0       = std::chrono::steady_clock::now ();
-		scanChunk (n, b0, ev, evi, evEnd, frontCand ? e->fclean.data () : nullptr, progEv, badEv, front, cs);
-		if (getenv ("TBF_DEBUG_HOST_PHASES"))
-			fprintf (stderr, "chunk %llu: clean %.3f ms, scan %.3f ms (%u events)\n", (unsigned long long)e->chunkSeq,
-			         std::chrono::duration<double, std::milli> (sc0 - hc0).count (),
-			         std::chrono::duration<double, std::milli> (std::chrono::steady_clock::now () - sc0).count (), evEnd - evi);
-		if (badEv)
-			return fail (-22, "event for a bad instance");
-		bool dfront = false;
-		if (frontCand && front && !progEv) {
-			if ((rc = stepChunkFront (e, n, want, b0, ev, evi, evEnd, cs, delta)))
-				return rc;
-			evi    = evEnd;
-			len    = want;
-			dfront = true;
-			e->frontChunks[0]++;
-			if (getenv ("TBF_DEBUG_HOST_PHASES"))
-				fprintf (stderr, "chunk %llu: device front end, %u note events\n", (unsigned long long)e->chunkSeq,
-				         e->hFevOff[n]);
-		}
-		else {
-			if (evEnd > evi)
-				e->frontChunks[1]++;
-			/* many instances to step: active now, or touched by this chunk's events */
-			if (e->devCtl && !progEv && e->parCtl && e->actList.size () + (evEnd - evi) >= 1024) {
-				if ((rc = stepChunkParallel (e, n, want, b0, ev, evi, evEnd, rp, delta)))
-					return rc;
-				evi = evEnd;
-				len = want;
-			}
-		}
-		for (; len < want; len++) {
-			if (!e->devCtl && e->dProg.size () + (size_t)n * SLOT > dprogCap && len > 0)
-				break; /* delta program pool full: end the chunk here */
-			if (delta && len >= TBF_CHUNK)
-				break; /* a chunk with deltas ends at TBF_CHUNK blocks, before the next block's events */
-			for (; evi < nev && ev[evi].block <= b0 + len; evi++) {
-				rc = applyEvent (e, ev[evi]);
-				if (rc)
-					return rc;
-				markActive (e, ev[evi].inst);
-			}
-			/* only the instances whose control may still change are stepped: one that
-			 * steps to no change stays unchanged until an event touches it */
-			const bool hadDelta = delta;
-			size_t     keep     = 0;
-			for (size_t a = 0; a < e->actList.size (); a++) {
-				const uint32_t i = e->actList[a];
-				bool           pc;
-				tbf_tgc_rec    rec;
-				if (stepControl (e, i, pc, e->devCtl ? &rec : nullptr)) {
-					tbf_seg_ctl c = e->hCtl[i];
-					if (e->devCtl) {
-						/* a stepped delta gets its own program slot, which k_tgctl fills; the
-						 * others play the program before them */
-						if (pc) {
-							c.prog_off = (uint32_t)(PERSIST (n) + ((size_t)rp * n * TBF_CHUNK + e->dCtl.size ()) * SLOT);
-							if (!e->stepped[i]) {
-								e->stepped[i] = 1;
-								e->hCtlInst.push_back (i);
-							}
-						} else {
-							memset (&rec, 0, sizeof (rec));
-							if (cur[i] >= n)
-								c.prog_off = e->dCtl[cur[i] - n].prog_off;
-						}
-						if (!e->dhas[i]) {
-							e->dhas[i] = 1;
-							e->hDInst.push_back (i);
-						}
-						e->hFull.push_back (c); /* every delta a full entry on this path */
-						rec.full = (uint32_t)e->hFull.size ();
-						e->hRec.push_back (rec);
-					} else if (pc) {
-						c.prog_off = (uint32_t)(PERSIST (n) + e->dProg.size ());
-						e->dProg.insert (e->dProg.end (), e->hProg.begin () + PSLOTS * i * SLOT,
-						                 e->hProg.begin () + PSLOTS * i * SLOT + 1 + c.prog_len);
-					} else if (cur[i] >= n)
-						c.prog_off = e->dCtl[cur[i] - n].prog_off; /* program of the previous delta */
-					cur[i] = n + (uint32_t)e->dCtl.size ();
-					e->dCtl.push_back (c);
-					e->chg[i] = 1;
-					delta     = true;
-					e->actList[keep++] = i;
-				} else
-					e->inAct[i] = 0;
-			}
-			e->actList.resize (keep);
-			/* entry index table: written only once the chunk has a delta (before that
-			 * every row is the identity) */
-			if (delta) {
-				if (!hadDelta)
-					for (uint32_t r = 0; r < len; r++)
-						for (uint32_t i = 0; i < n; i++)
-							e->hIdx[(size_t)r * n + i] = i;
-				std::copy (cur.begin (), cur.end (), e->hIdx.begin () + (size_t)len * n);
-			}
-		}
-		e->hostCtlNs += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds> (
-		                    std::chrono::steady_clock::now () - hc0)
-		                    .count ();
-		e->hostCtlBlocks += len;
-		if (delta && len > TBF_CHUNK)
-			return fail (-5, "internal: a chunk with control deltas longer than 64 blocks");
-		const bool     piped   = pipe && (!delta || dpipe);
-		auto at = [&] (int b) { return e->stageDbl[b] ? (size_t)bset * need : (size_t)0; };
-		P.mid0 = e->mid0.p ? e->mid0.p + 2 * at (0) : nullptr;
-		P.mid1 = e->mid1.p ? e->mid1.p + at (1) : nullptr;
-		P.mid2 = e->mid2.p ? e->mid2.p + at (4) : nullptr;
-		P.rvA  = e->rvA.p ? e->rvA.p + 2 * at (2) : nullptr;
-		P.rvB  = e->rvB.p ? e->rvB.p + 2 * at (3) : nullptr;
-		if (!piped && (rc = joinStages (e, s)))
+		Chunk ck = {};
+		ck.b0    = b0;
+		ck.evBeg = evi;
+		ck.want  = chunkLength (e, b0, nblocks, maxChunk, ev, evi, nev);
+		ck.cix   = e->chunkSeq++;
+		ck.bset  = (uint32_t)(ck.cix & 1);
+		ck.rp    = e->devCtl ? (int)(ck.cix & 1) : 0;
+		ck.dpipe = e->devCtl && pipe;
+		ck.us    = ck.dpipe ? e->gs[0] : s;
+		ChunkStaging& cs = e->stg[ck.rp];
+		if ((rc = refreshControlPool (e, cs, ck, n, s, nst)))
 			return rc;
-		if (delta) {
-			/* device control: both regions' delta slots, sized once for a delta per
-			 * instance and block (growProg synchronizes the device when it grows) */
-			if (e->devCtl && (rc = growProg (e, PERSIST (n) + 2 * (size_t)n * TBF_CHUNK * SLOT, n)))
-				return rc;
-			if ((rc = usWait ()))
-				return rc;
-			if (!e->devCtl) /* device control: k_tgctl writes the deltas' entries (records + full entries) */
-				HIPCHK (hipMemcpyAsync (e->ctl.p + rp * CTL_REGION (n) + n, e->dCtl.data (),
-				                        e->dCtl.size () * sizeof (tbf_seg_ctl), hipMemcpyHostToDevice, us));
-			if (!e->dProg.empty ())
-				HIPCHK (hipMemcpyAsync (e->prog.p + PERSIST (n), e->dProg.data (),
-				                        e->dProg.size () * sizeof (tbf_prog_entry), hipMemcpyHostToDevice, us));
-			if (!dfront) /* (k_front writes the index table) */
-				HIPCHK (hipMemcpyAsync (e->ctlIdx.p + (size_t)rp * n * TBF_CHUNK, e->hIdx.data (),
-				                        (size_t)len * n * sizeof (uint32_t), hipMemcpyHostToDevice, us));
-		}
-		P.whSets = nullptr;
-		if (delta && !e->hWh.empty ()) {
-			/* the whirl parameter sets of the chunk's deltas, by region parity like the records */
-			DevBuf<tbf_wh_params>& dw = rp ? e->dwhB : e->dwh;
-			if (dw.cap < e->hWh.size ())
-				HIPCHK (hipDeviceSynchronize ()); /* growing: nothing may still read the old buffer */
-			if (dw.ensure (std::max<size_t> (e->hWh.size (), 64)))
-				return fail (-12, "out of device memory (whirl parameter sets)");
-			HIPCHK (hipMemcpyAsync (dw.p, e->hWh.data (), e->hWh.size () * sizeof (tbf_wh_params), hipMemcpyHostToDevice, us));
-			P.whSets = dw.p;
-		}
-		P.prog      = e->prog.p;
-		P.ctl       = e->ctl.p + rp * CTL_REGION (n);
-		P.ctlIdx    = delta ? e->ctlIdx.p + (size_t)rp * n * TBF_CHUNK : nullptr;
-		P.nBlocks   = len;
-		/* k_tonegen block ranges (chunks without deltas) for small batches: about 2048 waves,
-		 * ranges of >= 4 blocks (each range after the first renders one warm-up block).  At
-		 * 4096 instances a split measured no gain (0.73 ms alone either way: the kernel is
-		 * bound by its bank gathers and VALU, not by waves in flight). */
-		P.tgSplit = e->tgSplit >= 0 ? (uint32_t)std::max (e->tgSplit, 1)
-		                            : std::max (1u, std::min ({8u, 2048u / std::max (n, 1u), len / 4}));
-		P.tgSplit = std::min (P.tgSplit, std::max (len, 1u));
-		P.outOffset = (uint64_t)b0 * TBF_BLK;
-		P.extOffset = (uint64_t)b0 * TBF_BLK;
-		P.nCtlInst  = 0;
-		if (e->devCtl && (dfront ? delta : !e->hDInst.empty ())) {
-			/* k_tgctl: the stepped blocks' programs, ahead of k_tonegen on this stream */
-			/* records per region parity: k_tgctl of the chunk before last (same stream, or
-			 * the caller's stream when not pipelined) read the other set */
-			DevBuf<tbf_tgc_rec>& drec = rp ? e->drecB : e->drec;
-			DevBuf<uint16_t>&    dmsg = rp ? e->dmsgB : e->dmsg;
-			DevBuf<float>&       dgn  = rp ? e->dgainB : e->dgain;
-			DevBuf<uint32_t>&    dci  = rp ? e->dctlInstB : e->dctlInst;
-			DevBuf<tbf_seg_ctl>& dfl  = rp ? e->dfullB : e->dfull;
-			const size_t nRec  = dfront ? (size_t)n * len : e->hRec.size ();
-			const size_t nMsg  = dfront ? 2 * (size_t)e->hFevOff[n] : e->hMsg.size ();
-			const size_t nGain = dfront ? (size_t)e->frontGain : e->hGain.size ();
-			if (drec.cap < nRec || dmsg.cap < nMsg || dci.cap < e->hDInst.size () || dgn.cap < nGain ||
-			    dfl.cap < (dfront ? (size_t)n * len : e->hFull.size ()))
-			{
-				if (getenv ("TBF_DEBUG_HOST_PHASES"))
-					fprintf (stderr, "chunk %llu: control record buffers grow (device sync)\n", (unsigned long long)e->chunkSeq);
-				HIPCHK (hipDeviceSynchronize ()); /* growing: nothing may still read the old buffers */
-			}
-			const size_t nFull = dfront ? (size_t)n * len : e->hFull.size (); /* k_front writes its effect entries */
-			if (drec.ensure (std::max<size_t> (nRec, 1)) || dmsg.ensure (std::max<size_t> (nMsg, 1)) ||
-			    dgn.ensure (std::max<size_t> (nGain, 27)) ||
-			    dci.ensure (e->hDInst.size ()) || dfl.ensure (std::max<size_t> (nFull, 1)))
-				return fail (-12, "out of device memory (control records)");
-			if (dfront) {
-				/* k_front: the records, messages and index table from the key states and events */
-				DevBuf<tbf_front_state>& dfs = rp ? e->dfrontB : e->dfront;
-				DevBuf<uint32_t>&        dfe = rp ? e->dfevB : e->dfev;
-				DevBuf<uint32_t>&        dfo = rp ? e->dfoffB : e->dfoff;
-				DevBuf<float>&           dfv = rp ? e->dfvalB : e->dfval;
-				if (dfs.cap < n || dfe.cap < e->hFev.size () || dfv.cap < e->hFev.size () || dfo.cap < (size_t)n + 1 ||
-				    e->dident.cap < n)
-					HIPCHK (hipDeviceSynchronize ()); /* growing: nothing may still read the old buffers */
-				if (dfs.ensure (n) || dfe.ensure (e->hFev.size ()) || dfv.ensure (e->hFev.size ()) ||
-				    dfo.ensure ((size_t)n + 1) || e->dident.ensure (n))
-					return fail (-12, "out of device memory (front end)");
-				if (e->hIdent.size () != n) {
-					e->hIdent.resize (n);
-					for (uint32_t i = 0; i < n; i++)
-						e->hIdent[i] = i;
-					HIPCHK (hipMemcpy (e->dident.p, e->hIdent.data (), (size_t)n * 4, hipMemcpyHostToDevice));
-				}
-				HIPCHK (hipMemcpyAsync (dfs.p, e->hFront.data (), (size_t)n * sizeof (tbf_front_state), hipMemcpyHostToDevice, us));
-				HIPCHK (hipMemcpyAsync (dfe.p, e->hFev.data (), e->hFev.size () * 4, hipMemcpyHostToDevice, us));
-				HIPCHK (hipMemcpyAsync (dfo.p, e->hFevOff.data (), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, us));
-				HIPCHK (hipMemcpyAsync (dfv.p, e->hFevVal.data (), e->hFev.size () * 4, hipMemcpyHostToDevice, us));
-				P.front   = dfs.p;
-				P.fev     = dfe.p;
-				P.fevVal  = dfv.p;
-				P.fulls   = dfl.p;
-				P.fevOff  = dfo.p;
-				P.keyComp = e->dkeyComp.p;
-				P.rec     = drec.p;
-				P.msgs    = dmsg.p;
-				P.gains   = dgn.p;
-				if ((rc = tbf_launch_front (&P, us)))
-					return fail (rc, std::string ("k_front launch failed: ") + hipGetErrorString (hipGetLastError ()));
-			}
-			if (!dfront && e->dSeg.empty ())
-				HIPCHK (hipMemcpyAsync (drec.p, e->hRec.data (), e->hRec.size () * sizeof (tbf_tgc_rec),
-				                        hipMemcpyHostToDevice, us));
-			for (const auto& g : e->dSeg)
-				if (!dfront && g.second)
-					HIPCHK (hipMemcpyAsync (drec.p + g.first, e->hRec.data () + g.first,
-					                        g.second * sizeof (tbf_tgc_rec), hipMemcpyHostToDevice, us));
-			if (!dfront && !e->hMsg.empty ())
-				HIPCHK (hipMemcpyAsync (dmsg.p, e->hMsg.data (), e->hMsg.size () * sizeof (uint16_t),
-				                        hipMemcpyHostToDevice, us));
-			if (!dfront && !e->hGain.empty ())
-				HIPCHK (hipMemcpyAsync (dgn.p, e->hGain.data (), e->hGain.size () * sizeof (float),
-				                        hipMemcpyHostToDevice, us));
-			if (!dfront && !e->hFull.empty ())
-				HIPCHK (hipMemcpyAsync (dfl.p, e->hFull.data (), e->hFull.size () * sizeof (tbf_seg_ctl),
-				                        hipMemcpyHostToDevice, us));
-			if (!dfront)
-				HIPCHK (hipMemcpyAsync (dci.p, e->hDInst.data (), e->hDInst.size () * 4, hipMemcpyHostToDevice, us));
-			P.tgc      = e->tgc.p;
-			P.rec      = drec.p;
-			P.msgs     = dmsg.p;
-			P.gains    = dgn.p;
-			P.ctlInst  = dfront ? e->dident.p : dci.p;
-			P.nCtlInst = dfront ? n : (uint32_t)e->hDInst.size ();
-			P.fulls    = dfl.p;
-			P.progBase = (uint32_t)(PERSIST (n) + (size_t)rp * n * TBF_CHUNK * SLOT);
-			P.coff     = e->coff.p;
-			P.contrib  = e->contrib.p;
-			P.ctlNw    = e->ctlNw;
-			if ((rc = tbf_launch_tgctl (&P, us)))
-				return fail (rc, std::string ("k_tgctl launch failed: ") + hipGetErrorString (hipGetLastError ()));
-		}
-		if (e->devCtl)
-			HIPCHK (hipEventRecord (e->upEv, us)); /* this parity's staging is free after it */
-		if (usWaited && piped) /* the stage streams now follow the uploads on us */
-			e->stagesBusy = true;
-		const int nst = tbf_chain_stages (P.chain);
-		/* k_rv_pre ahead: this chunk's k_rv_pre goes in front of the held-back k_whirl of the
-		 * chunk before when neither chunk has control deltas or uploads and this one takes
-		 * k_rv_core_lds (a shorter chunk's k_rv_pre is too small to matter); its own k_whirl
-		 * is held back when a chunk follows in this call.  Anything else runs as before, behind
-		 * the held-back launch. */
-		const bool plain = aheadOn && piped && !delta && !usWaited && nst == TBF_NSTAGES;
-		const bool ahead = plain && e->defPending && P.rvLds && len >= RVL_MIN_BLOCKS;
-		if (!ahead && (rc = issueDeferred (e)))
+		if ((rc = hostControl (e, cs, ck, n, ev, nev)))
 			return rc;
-		if (piped) {
-			/* stage-group streams: every chunk's stage k on stream gs[grp[k]], so a stage runs
-			 * as soon as this chunk's previous stage and the previous chunk's same stage are
-			 * done, whatever the later stages of the previous chunk are doing.  Buffer parity
-			 * par was last read by the chunk before last: wait for those readers (stage k's
-			 * output mid0 is read by k_mixpre, mid1 by k_rv_pre and k_rv_post, rvA by
-			 * k_rv_core, rvB by k_rv_post, mid2 by k_whirl) when they run on another stream. */
-			static const int readers[TBF_NSTAGES][2] = {{1, -1}, {2, 4}, {3, -1}, {4, -1}, {5, -1}, {-1, -1}};
-			auto strm = [&] (int k) { return e->gs[e->grp[k == 2 && ahead ? TBF_NSTAGES - 1 : k]]; };
-			for (int k = st0; k < nst; k++) {
-				hipStream_t sk = strm (k);
-				if (k == nst - 1 && plain && b0 + len < nblocks) { /* held back for the next chunk's k_rv_pre */
-					e->defP       = P;
-					e->defCix     = cix;
-					e->defPending = true;
-					break;
-				}
-				/* after the caller's stream (uploads, earlier chunks).  A generator needs that only
-				 * when the stage streams are idle; a stage that reads the caller's input needs it on
-				 * every call: the input is complete only where the caller's stream reaches the call
-				 * (later chunks of the call follow the first on the stage's stream) */
-				if (k == st0 && (!e->stagesBusy || (st0 > 0 && !e->inWait))) {
-					HIPCHK (hipEventRecord (e->sjoin, s));
-					HIPCHK (hipStreamWaitEvent (sk, e->sjoin, 0));
-					e->inWait = true;
-				}
-				if (k == nst - 1 && !e->outWait) { /* the output stage writes the caller's buffers */
-					HIPCHK (hipEventRecord (e->sjoin, s));
-					HIPCHK (hipStreamWaitEvent (sk, e->sjoin, 0));
-					e->outWait = true;
-				}
-				if (k > 0 && strm (k - 1) != sk)
-					HIPCHK (hipStreamWaitEvent (sk, e->sdone[k - 1], 0));
-				if (k == 2 && ahead) {
-					/* behind k_rv_core of the chunk before (sdone[3] is still its event): that
-					 * puts the launch in the k_rv_post phase, orders it behind that chunk's
-					 * k_rv_pre (the stage's state) and keeps rvA a single buffer */
-					HIPCHK (hipStreamWaitEvent (sk, e->sdone[3], 0));
-				} else
-					for (int r : readers[k])
-						if (r >= 0 && r < nst && strm (r) != sk)
-							HIPCHK (hipStreamWaitEvent (sk, e->pev[(cix + 2) & 3][r], 0));
-				P.preAhead = k == 2 && ahead;
-				if ((rc = issueStage (e, P, k, sk, cix)))
-					return rc;
-				if (k == 2 && ahead) {
-					e->aheadCount++;
-					if ((rc = issueDeferred (e))) /* k_whirl of the chunk before, behind it */
-						return rc;
-				}
-			}
-			P.preAhead = 0;
-			e->stagesBusy = true;
-			if (delta && (rc = endDelta ()))
-				return rc;
-			b0 += len;
-			continue;
-		}
-		for (int k = st0; k < nst; k++) {
-			hipEvent_t e0 = nullptr, e1 = nullptr;
-			if (e->timeOn) {
-				HIPCHK (hipEventCreate (&e0));
-				HIPCHK (hipEventCreate (&e1));
-				HIPCHK (hipEventRecord (e0, s));
-			}
-			rc = launchStage (e, P, k, s);
-			if (rc)
-				return fail (rc, std::string ("kernel launch failed: ") + hipGetErrorString (hipGetLastError ()));
-			if (e->timeOn) {
-				HIPCHK (hipEventRecord (e1, s));
-				e->tev.push_back ({k, {e0, e1}});
-			}
-		}
-		if (delta && (rc = endDelta ()))
+		evi      = ck.evBeg;
+		ck.piped = pipe && (!ck.delta || ck.dpipe);
+		if (!ck.piped && (rc = joinStages (e, s)))
 			return rc;
-		b0 += len;
+		if ((rc = uploadDeltas (e, cs, ck, P, s)))
+			return rc;
+		chunkLaunch (e, ck, P, need);
+		if ((rc = controlKernels (e, cs, ck, P)))
+			return rc;
+		if ((rc = issueChunk (e, ck, P, s, aheadOn, b0 + ck.len < nblocks)))
+			return rc;
+		if (ck.delta && (rc = endDelta (e, cs, n, s)))
+			return rc;
+		b0 += ck.len;
 	}
-	for (; evi < nev; evi++) { /* events at or after the last block apply to the next render */
-		rc = applyEvent (e, ev[evi]);
-		if (rc)
+	for (; evi < nev; evi++) /* events at or after the last block apply to the next render */
+		if ((rc = applyEvent (e, ev[evi])))
 			return rc;
-	}
 	if ((rc = issueDeferred (e)))
 		return rc;
-	if (e->stagesBusy) {
-		/* the caller's stream waits for the last chunk's output stage (which follows
-		 * every earlier stage launch); later chunks keep overlapping from the streams */
-		HIPCHK (hipStreamWaitEvent (s, e->sdone[tbf_chain_stages (P.chain) - 1], 0));
-	}
+	/* the caller's stream waits for the last chunk's output stage (which follows
+	 * every earlier stage launch); later chunks keep overlapping from the streams */
+	if (e->stagesBusy)
+		HIPCHK (hipStreamWaitEvent (s, e->sdone[nst - 1], 0));
 	return 0;
+}
+
+/* renderBody, and on every way out of it the held-back k_whirl: it never outlives the call */
+static int renderImpl (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, uint64_t stride, hipStream_t s,
+                       const tbf_event* ev = nullptr, uint32_t nev = 0)
+{
+	e->callS   = s;
+	e->outWait = false;
+	e->inWait  = false;
+	const int rc = renderBody (e, nblocks, dL, dR, stride, s, ev, nev);
+	if (e->defPending) { /* an error return between two chunks */
+		(void)issueDeferred (e);
+		(void)hipStreamWaitEvent (s, e->sdone[TBF_NSTAGES - 1], 0);
+	}
+	return rc;
 }
 
 /* the tbf_render* calls and tbf_synth_sound on an effects-only engine */
@@ -3260,7 +3262,7 @@ int tbf_debug_render_program (tbf_engine* e, uint32_t i, float* out, uint32_t ca
 		e->hProg.resize (PERSIST (n));
 	}
 	bool pc;
-	(void)stepControl (e, i, pc); /* exactly the per-block step renderImpl makes */
+	(void)stepControl (e, e->stg[0], i, pc); /* exactly the per-block step renderImpl makes (host control: set 0) */
 	const std::vector<tbf_prog_entry>& prog = e->inst[i].prog;
 	for (uint32_t q = 0; q < prog.size () && q < cap; q++) {
 		const tbf_prog_entry& p = prog[q];

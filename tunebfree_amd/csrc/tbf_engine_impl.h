@@ -2,6 +2,9 @@
  * tbf_engine_impl.h -- private engine state shared by the C-ABI translation units
  * (tbf_engine.cpp: construction, device setup, rendering; tbf_control.cpp: MIDI control
  * functions and programmes).  Not part of the ABI.
+ * The render path (tbf_engine.cpp renderBody) is a chunk loop over
+ * phase functions (refreshControlPool, hostControl, uploadDeltas, controlKernels, issueChunk,
+ * endDelta) of a file-local Chunk and the chunk's staged arrays, ChunkStaging below.
  */
 #ifndef TBF_ENGINE_IMPL_H
 #define TBF_ENGINE_IMPL_H
@@ -133,13 +136,6 @@ struct PinnedVec {
 	T*     begin () { return p; }
 	T*     end () { return p + n; }
 	T&     operator[] (size_t i) { return p[i]; }
-	void   swap (PinnedVec& o)
-	{
-		std::swap (p, o.p);
-		std::swap (n, o.n);
-		std::swap (cap, o.cap);
-		std::swap (pinned, o.pinned);
-	}
 };
 
 /* a chunk's event scan (scanChunk, csrc/tbf_engine.cpp): instance ranges and event
@@ -201,6 +197,39 @@ struct DevBuf {
 	}
 };
 
+/* One chunk's staged control: what the chunk's host control step writes (pinned host
+ * arrays), the device buffers they are uploaded to, and the event behind those uploads.
+ * tbf_engine holds two, stg[chunk parity] under device control (stg[0] alone under host
+ * control): chunk c + 1's host control fills one while chunk c's uploads and kernels still
+ * read the other; a set is free again once its upEv is done.  (A new staged array goes in
+ * here, host or device side, and nothing else is needed.) */
+struct ChunkStaging {
+	PinnedVec<tbf_seg_ctl>     dCtl;     /* the chunk's control deltas (pool entries n ..) */
+	PinnedVec<uint32_t>        hIdx;     /* pool entry per (block, instance) */
+	PinnedVec<tbf_seg_ctl>     hCtlPin;  /* device control: the region's persistent entries, as uploaded */
+	PinnedVec<tbf_tgc_rec>     hRec;     /* per delta of the chunk */
+	PinnedVec<uint16_t>        hMsg;     /* the chunk's key messages */
+	PinnedVec<float>           hGain;    /* the chunk's changed drawbar gains: (bus, gain) pairs */
+	PinnedVec<tbf_wh_params>   hWh;      /* the chunk's whirl parameter sets (tbf_seg_ctl.whSet) */
+	PinnedVec<uint32_t>        hCtlInst; /* instances with a stepped delta */
+	PinnedVec<uint32_t>        hDInst;   /* instances with any delta: k_tgctl's grid */
+	PinnedVec<tbf_seg_ctl>     hFull;    /* the chunk's full control entries (tbf_tgc_rec.full) */
+	/* device front end (k_front) for note-only chunks: per instance key state at the chunk
+	 * start, the instances' note events by instance, their offsets, TBF_FEV_EFFECT events' values */
+	PinnedVec<tbf_front_state> hFront;
+	PinnedVec<uint32_t>        hFev, hFevOff;
+	PinnedVec<float>           hFevVal;
+	/* the device side (k_tgctl, k_front: tbf_ctl.hip) */
+	DevBuf<tbf_tgc_rec>        drec;
+	DevBuf<uint16_t>           dmsg;
+	DevBuf<float>              dgain, dfval;
+	DevBuf<tbf_wh_params>      dwh;
+	DevBuf<uint32_t>           dctlInst, dfev, dfoff;
+	DevBuf<tbf_seg_ctl>        dfull;
+	DevBuf<tbf_front_state>    dfront;
+	hipEvent_t                 upEv = nullptr; /* after the chunk's uploads and control kernels */
+};
+
 } // namespace tbf
 
 using namespace tbf; /* private header: the engine's own translation units only */
@@ -246,49 +275,19 @@ struct tbf_engine {
 	/* device-side tone-generator control (k_tgctl, tbf_ctl.hip) */
 	bool                                    devCtl = false;
 	DevBuf<tbf_tgc_state>                   tgc;
-	DevBuf<tbf_tgc_rec>                     drec;
-	DevBuf<uint16_t>                        dmsg;
-	DevBuf<uint32_t>                        dctlInst;
 	DevBuf<uint32_t>                        coff;
 	uint32_t                                ctlNw = 1; /* k_tgctl's staged wheels (largest wheel in coff/contrib + 1) */
 	DevBuf<tbf_contrib>                     contrib;
-	PinnedVec<tbf_tgc_rec>                  hRec;     /* per delta of the chunk */
-	PinnedVec<uint16_t>                     hMsg;     /* the chunk's key messages */
-	PinnedVec<float>                        hGain;    /* the chunk's changed drawbar gains: (bus, gain) pairs */
-	PinnedVec<float>                        hGainB;
-	DevBuf<float>                           dgain, dgainB;
-	PinnedVec<tbf_wh_params>                hWh, hWhB; /* the chunk's whirl parameter sets (tbf_seg_ctl.whSet) */
-	DevBuf<tbf_wh_params>                   dwh, dwhB;
-	PinnedVec<uint32_t>                     hCtlInst; /* instances with a stepped delta */
-	PinnedVec<uint32_t>                     hDInst, hDInstB; /* instances with any delta: k_tgctl's grid */
-	PinnedVec<tbf_seg_ctl>                  hFull, hFullB;   /* the chunk's full control entries (tbf_tgc_rec.full) */
-	DevBuf<tbf_seg_ctl>                     dfull, dfullB;
+	ChunkStaging                            stg[2];   /* the chunks' staged control, by chunk parity */
 	std::vector<tbf_seg_ctl>                lastEmit; /* per instance: the last full entry the device holds (parallel front end) */
-	std::vector<uint8_t>                    dseen, dhas; /* per chunk: lastEmit taken / in hDInst */
 	std::vector<uint32_t>                   lastProg;    /* per instance: the last delta's prog_off */
-	/* device front end (k_front) for note-only chunks: per instance key state at the chunk
-	 * start, the instances' note events by instance, their offsets; by chunk parity */
+	/* device front end (k_front) for note-only chunks (its staging: ChunkStaging) */
 	bool                                    frontOn = true; /* TBF_DEVICE_FRONT=0 disables */
 	uint32_t                                frontGain = 0;  /* device front end: the chunk's gain-pair floats */
-	PinnedVec<tbf_front_state>              hFront, hFrontB;
-	PinnedVec<uint32_t>                     hFev, hFevB, hFevOff, hFevOffB;
-	PinnedVec<float>                        hFevVal, hFevValB; /* TBF_FEV_EFFECT events' values */
-	DevBuf<tbf_front_state>                 dfront, dfrontB;
-	DevBuf<uint32_t>                        dfev, dfevB, dfoff, dfoffB;
-	DevBuf<float>                           dfval, dfvalB;
 	DevBuf<float>                           dkeyComp;   /* [tpl][128] keyCompTable */
 	DevBuf<uint32_t>                        dident;     /* 0 .. n-1: k_tgctl's grid over every instance */
 	std::vector<uint32_t>                   hIdent;
 	std::vector<uint8_t>                    fclean; /* per instance: no control change pending but notes */
-	ChunkScan                               scan;   /* the chunk's event scan (scanChunk) */
-	/* the other parity of the chunk staging (the previous chunk's, in flight), and the
-	 * events after each parity's uploads */
-	PinnedVec<tbf_seg_ctl>                  dCtlB, hCtlPin, hCtlPinB;
-	PinnedVec<tbf_tgc_rec>                  hRecB;
-	PinnedVec<uint16_t>                     hMsgB;
-	PinnedVec<uint32_t>                     hCtlInstB, hIdxB;
-	hipEvent_t                              upEv = nullptr, upEvB = nullptr;
-	std::vector<uint8_t>                    stepped;  /* membership of hCtlInst */
 	std::vector<uint8_t>                    pslot;    /* persistent program slot (0..TBF_PROG_PSLOTS-1) per instance */
 	/* device control, pipelined delta chunks: the control pool (persistent entries +
 	 * deltas), the index table and the control records come in two regions by chunk
@@ -299,6 +298,7 @@ struct tbf_engine {
 	uint32_t                                nCU     = 256; /* the device's CUs */
 	uint32_t                                frontMin = 64; /* events a chunk needs for the device front end (TBF_FRONT_MIN; 64: profiles/r05/s23) */
 	bool                                    parCtl = true; /* TBF_HOST_SERIAL=1 steps serially */
+	bool                                    dbgPhases = false; /* TBF_DEBUG_HOST_PHASES: the host phases' times on stderr */
 	/* threaded host control (stepChunkParallel): per worker, kept between chunks so the
 	 * buffers stay allocated; worker t writes its deltas straight into the staging at pool
 	 * position base_t = (first instance of its range) * blocks, and dSeg lists the filled
@@ -323,11 +323,16 @@ struct tbf_engine {
 		int                   rc = 0;
 		std::string           err; /* the worker's tbf_last_error text (it is thread-local) */
 	};
+	/* per-chunk scratch of the host control step, not double-buffered (no upload reads it
+	 * past the chunk): the workers' lists and the filled staging segments, the host path's
+	 * delta programs, membership of hCtlInst / hDInst, lastEmit taken, control changed, the
+	 * pool entry per instance at the current block, the event scan (scanChunk) */
 	std::vector<ParStep>                    parStep;
 	std::vector<std::pair<uint32_t, uint32_t>> dSeg;
-	DevBuf<tbf_tgc_rec>                     drecB;
-	DevBuf<uint16_t>                        dmsgB;
-	DevBuf<uint32_t>                        dctlInstB;
+	std::vector<tbf_prog_entry>             dProg;
+	std::vector<uint8_t>                    stepped, dhas, dseen, chg;
+	std::vector<uint32_t>                   curIdx;
+	ChunkScan                               scan;
 	DevBuf<uint32_t>                        vib;
 	DevBuf<uint32_t>                        xsj; /* xorshift32 jump table */
 	DevBuf<float>                           whTab, whBw;
@@ -345,17 +350,11 @@ struct tbf_engine {
 	DevBuf<double>                          rvA, rvB;   /* reverb inter-kernel streams (FP64) */
 	std::vector<tbf_seg_ctl>                hCtl;  /* current control per instance (pool entries 0..n-1) */
 	std::vector<tbf_prog_entry>             hProg; /* current program per instance (slots i * PROG_CAP) */
-	/* per-chunk control deltas (tbf_render_events / renderImpl) */
-	PinnedVec<tbf_seg_ctl>                  dCtl;
-	std::vector<tbf_prog_entry>             dProg;
-	PinnedVec<uint32_t>                     hIdx;
-	std::vector<uint8_t>                    chg;
 	/* instances whose control may change at the next block (renderImpl steps only
 	 * these): every entry point that changes an instance marks it (markActive) */
 	std::vector<uint32_t>                   actList;
 	std::vector<uint8_t>                    inAct;   /* membership of actList */
 	bool                                    actAll = true; /* instances added: step all */
-	std::vector<uint32_t>                   curIdx;  /* pool entry per instance, current block */
 	DevBuf<uint32_t>                        ctlIdx;
 	bool                                    persistStale = true; /* device pool entries 0..n-1 need upload */
 	/* cross-chunk pipelining (renderImpl): stage k of every chunk runs on the stream of its
@@ -409,14 +408,13 @@ struct tbf_engine {
 	/* the stage buffers as allocated (stageBuffers): blocks per chunk they hold (a power of two
 	 * from TBF_CHUNK up to steadyChunk, grown to the longest chunk a call can make, never past
 	 * what the device could allocate), for stageN instances; a buffer whose producer and
-	 * readers share a stage-group stream is single (dbl[] false), the others alternate by
-	 * chunk parity */
+	 * readers share a stage-group stream is single, the others alternate by chunk parity
+	 * (stageBufAlternates) */
 	uint32_t                                stageBlocks = 0, stageN = 0;
 	uint64_t                                frontChunks[2] = {0, 0}; /* chunks with events: device, host front end */
 	/* kernel variants launched (tbf_debug_launches, TBF_LAUNCH_*): k_tonegen with one block
 	 * range / several, k_rv_core, k_rv_core_lds, k_whirl, k_whirl_split */
 	uint64_t                                launches[6] = {0, 0, 0, 0, 0, 0};
-	bool                                    stageDbl[5] = {true, true, true, true, true}; /* mid0 mid1 rvA rvB mid2 */
 	/* programme table (.pgm), src/program.h:26 MAXPROGS; pgm.controller.offset */
 	std::vector<Programme>                  progs = std::vector<Programme> (129);
 	int                                     pgmOffset = 1;
