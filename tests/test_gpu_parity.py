@@ -2031,6 +2031,72 @@ def test_gpu_add_instances_after_render_then_events(oracle, via_events):
         assert_bits(gr, oR[0], f"instance {i} R")
 
 
+@pytest.mark.parametrize("env", [{}, {"TBF_HOST_CONTROL": "1"}], ids=["device_control", "host_control"])
+def test_gpu_programme_change_events(env, capfd):
+    """A programme change as a scheduled event (TBF_EV_PROGRAM).  300 instances (two instance
+    ranges, the second partial), 12 blocks: every instance holds a chord from block 0 and
+    releases one key and presses another on every block -- well over 1024 events in the
+    chunk, which the threaded stepper or the device front end would take -- and every third
+    instance installs a programme at block 5, some ahead of that block's notes and some
+    behind them.  The programme event sends the chunk down the serial stepper: asserted from
+    the engine's TBF_DEBUG_HOST_PHASES lines (the other two steppers each print one) and its
+    count of host-front-end chunks.  Bit for bit
+    against an engine that renders blocks 0-4, applies those instances' block-5 events
+    through tbf_note / tbf_program_install in the same order, and renders blocks 5-11 with
+    the remaining events."""
+    import torch
+    from test_control_cpu import PGM
+    n, nb, pb = 300, 12, 5
+    rows = []
+    for i in range(n):
+        for (_k, a, v) in S.jazz1_params():
+            rows.append((0, i, 1, a, float(v)))
+        for k in S.chord_for(i):
+            rows.append((0, i, 0, k, 1.0))
+        for b in range(1, nb):
+            notes = [(b, i, 0, 60 + (i + b - 1) % 12, 0.0), (b, i, 0, 60 + (i + b) % 12, 1.0)]
+            if b == pb and i % 3 == 0:
+                prog = (b, i, 3, 6 if i % 2 else 0, 0.0)  # programme 7 (tremolo, v2, ...) or 1
+                notes = [prog] + notes if i % 4 < 2 else notes + [prog]
+            rows.extend(notes)
+    rows.sort(key=lambda r: r[0])  # stable: an instance's events keep their order in a block
+    assert sum(1 for r in rows if r[0] < nb) > 1024
+    direct = [r for r in rows if r[0] == pb and r[1] % 3 == 0]
+    assert {r[3] for r in direct if r[2] == 3} == {0, 6}
+    assert {[r[2] for r in direct if r[1] == i][0] for i in range(0, n, 3)} == {0, 3}  # both orders
+
+    def organ(**more):
+        eng = _organ(n, env=dict(env, **more))
+        assert eng.program_parse(PGM) == 4
+        L = torch.zeros((n, nb * 128), dtype=torch.float32, device="cuda")
+        return eng, L, torch.zeros_like(L)
+
+    eng, LA, RA = organ(TBF_DEBUG_HOST_PHASES="1")
+    capfd.readouterr()
+    eng.render_events_device(nb, eng.events(rows), LA.data_ptr(), RA.data_ptr(), nb * 128)
+    eng.synchronize()
+    phases = capfd.readouterr().err
+    assert "chunk " in phases and "stepChunkParallel" not in phases and "device front end" not in phases, phases
+    dev, host = eng.front_chunks()  # the host front end's (host control may end a chunk early)
+    assert dev == 0 and (host >= 1 if env else host == 1), (dev, host)
+    eng.close()
+    eng, LB, RB = organ()
+    eng.render_events_device(pb, eng.events([r for r in rows if r[0] < pb]), LB.data_ptr(), RB.data_ptr(), nb * 128)
+    for (_b, i, kind, a, v) in direct:
+        if kind == 3:
+            eng.program_install(i, a)
+        else:
+            eng.note(i, a, int(v))
+    rest = [(b - pb, i, kind, a, v) for (b, i, kind, a, v) in rows if b >= pb and not (b == pb and i % 3 == 0)]
+    eng.render_events_device(nb - pb, eng.events(rest), LB.data_ptr() + 4 * pb * 128, RB.data_ptr() + 4 * pb * 128, nb * 128)
+    eng.synchronize()
+    eng.close()
+    LA, RA, LB, RB = (x.cpu().numpy() for x in (LA, RA, LB, RB))
+    assert np.isfinite(LA).all() and float(np.abs(LA[:, pb * 128:]).max()) > 1e-3
+    assert_bits(LA, LB, "programme events, one call vs split calls, L")
+    assert_bits(RA, RB, "programme events, one call vs split calls, R")
+
+
 def test_gpu_sin_fast_paths_are_ocml_bits():
     """csrc/tbf_sin.h: the kernels' sin with wave-uniform fast paths (only the sine or only
     the cosine polynomial of OCML's reduction when every lane of a wave has n = 0 or n = 1,

@@ -64,15 +64,7 @@ int tbf::fail (int code, const std::string& msg)
 	} while (0)
 
 
-/* program slots: SLOT, PSLOTS, PERSIST (n) of tbf_engine_impl.h */
-/* blocks per kernel launch chunk: bounds the inter-stage buffers to
- * n_inst x TBF_CHUNK x 128 floats each (134 MB at 4096 instances) */
-#ifndef TBF_CHUNK
-#define TBF_CHUNK 64
-#endif
-/* host-controlled path: delta program entries one chunk may add (a chunk ends early when
- * they would not fit); the device-controlled path sizes its delta slots on demand */
-#define DPROG_CAP(n) ((size_t)(n) * SLOT * 2 + 4096)
+/* (program slots and chunk sizes -- SLOT, PSLOTS, PERSIST, TBF_CHUNK, DPROG_CAP: tbf_engine_impl.h) */
 /* control pool region (one per chunk parity on the device-controlled path; the host path
  * uses region 0): n persistent entries + up to one delta per instance and block */
 #define CTL_REGION(n) ((size_t)(n) * (TBF_CHUNK + 1))
@@ -171,57 +163,6 @@ static void whirlConsts (tbf_inst_const& k, const WhirlTables& wt, const Config&
 	k.sr         = wt.sr;
 }
 
-/* preamp per-block constants, src/overdrive.cpp:64-84 and the density/out loops */
-static void odCtlCompute (const Instance& in, double sr, tbf_seg_ctl& c)
-{
-	double overallscale = 1.0;
-	overallscale /= 44100.0;
-	overallscale *= sr;
-	double density = in.odA * 4.0;
-	c.odIir        = pow (in.odB, 3) / overallscale;
-	c.odOutput     = in.odC;
-	c.odWet        = in.odD;
-	c.odDry        = 1.0 - c.odWet;
-	double out     = fabs (density);
-	density        = density * fabs (density);
-	double count   = density;
-	int    iter    = 0;
-	while (count > 1.0) {
-		iter++;
-		count = count - 1.0;
-	}
-	while (out > 1.0)
-		out = out - 1.0;
-	c.odIter       = iter;
-	c.odOut        = out;
-	c.odDensityPos = density > 0 ? 1u : 0u;
-	c.odClean      = (uint32_t)in.odClean;
-}
-
-/* the preamp fields of a control entry, recomputed only when the preamp parameters changed
- * (the pow above costs more than the rest of a dense-event step per instance and block) */
-static void odCtl (Instance& in, double sr, tbf_seg_ctl& c)
-{
-	Instance::OdCache& k = in.odc;
-	if (!k.valid || k.A != in.odA || k.B != in.odB || k.C != in.odC || k.D != in.odD || k.clean != in.odClean) {
-		odCtlCompute (in, sr, k.ctl);
-		k.A     = in.odA;
-		k.B     = in.odB;
-		k.C     = in.odC;
-		k.D     = in.odD;
-		k.clean = in.odClean;
-		k.valid = true;
-	}
-	c.odIir        = k.ctl.odIir;
-	c.odOutput     = k.ctl.odOutput;
-	c.odWet        = k.ctl.odWet;
-	c.odDry        = k.ctl.odDry;
-	c.odIter       = k.ctl.odIter;
-	c.odOut        = k.ctl.odOut;
-	c.odDensityPos = k.ctl.odDensityPos;
-	c.odClean      = k.ctl.odClean;
-}
-
 /* fsetCharacter (src/overdrive.cpp:547-574): character A and the linear-segment output
  * level C */
 void tbf::setCharacter (Instance& in, float value)
@@ -267,10 +208,8 @@ static int buildShared (tbf_engine* e)
 }
 
 /* host worker threads for per-template work: the process's lease (OMP_NUM_THREADS, set
- * on the GPU boxes) or the hardware, at most TBF_MAX_HOST_THREADS (scanChunk sizes its
- * per-range stack arrays by it) */
-#define TBF_MAX_HOST_THREADS 16u
-static unsigned hostThreads ()
+ * on the GPU boxes) or the hardware, at most TBF_MAX_HOST_THREADS */
+unsigned tbf::hostThreads ()
 {
 	unsigned    t   = std::thread::hardware_concurrency ();
 	const char* omp = getenv ("OMP_NUM_THREADS");
@@ -371,16 +310,14 @@ class HostPool {
 };
 
 /* run f(t) for t < n on up to hostThreads () threads */
-template <typename F>
-static void parallelFor (uint32_t n, F f)
+void tbf::parallelFor (uint32_t n, const std::function<void (uint32_t)>& f)
 {
 	if (n <= 1 || hostThreads () <= 1) {
 		for (uint32_t t = 0; t < n; t++)
 			f (t);
 		return;
 	}
-	const std::function<void (uint32_t)> g (f);
-	HostPool::get ().run (n, g);
+	HostPool::get ().run (n, f);
 }
 
 extern "C" {
@@ -894,46 +831,10 @@ int tbf_set_param (tbf_engine* e, uint32_t i, int32_t index, double v)
 {
 	if (!e || i >= e->inst.size ())
 		return fail (-22, "bad instance");
-	Instance& in    = e->inst[i];
-	float     value = (float)v;
 	markActive (e, i);
-	if (index >= 0 && index < 64)
-		in.params[index] = value;
-	/* src/clap.cpp:108-121 setToneGenParam + 162-207 setParam */
-	if (index >= TBF_P_DRAWBAR_MIN && index <= TBF_P_DRAWBAR_MAX)
-		in.tg.setDrawBar (index, (unsigned)rint (value));
-	else if (index == TBF_P_VIBRATO)
-		in.tg.setVibratoUpper ((int)rint (value));
-	else if (index == TBF_P_VIBRATO_TYPE)
-		in.tg.setVibratoFromInt ((int)floor (value));
-	else if (index == TBF_P_DRUM || index == TBF_P_HORN)
-		in.revOpt = (int)(floor (in.params[TBF_P_DRUM]) + 3 * floor (in.params[TBF_P_HORN]));
-	else if (index == TBF_P_OVERDRIVE)
-		in.odClean = (int)rint (1.0f - value);
-	else if (index == TBF_P_CHARACTER) {
-		setCharacter (in, value);
-	} else if (index == TBF_P_REVERB)
-		in.rvG = value;
-	else if (index == TBF_P_PERCUSSION)
-		in.tg.setPercEnabled ((int)rint (value));
-	else if (index == TBF_P_PERCUSSION_VOLUME)
-		in.tg.setPercVolume ((int)(1 - rint (value)));
-	else if (index == TBF_P_PERCUSSION_DECAY)
-		in.tg.setPercFast ((int)rint (value));
-	else if (index == TBF_P_PERCUSSION_HARMONIC)
-		in.tg.setPercFirst ((int)rint (value));
-	else if (index >= TBF_P_BUS_DRAWBAR_BASE && index < TBF_P_BUS_DRAWBAR_BASE + 27)
-		in.tg.setDrawBar (index - TBF_P_BUS_DRAWBAR_BASE, (unsigned)rint (value));
-	else if (index == TBF_P_VIBRATO_LOWER)
-		in.tg.setVibratoLower ((int)rint (value));
-	else if (index == TBF_P_SWELL) {
-		unsigned char u      = (unsigned char)rint (value * 127.0);
-		in.tg.swellPedalGain = (float)((in.tg.outputLevelTrim * ((double)u)) / 127.0);
-	} else if (index == TBF_P_WHIRL_BYPASS)
-		in.whBypass = (int)rint (value);
-	else if (!(index >= 0 && index < 64))
+	if (!setParam (e->inst[i], index, (float)v)) /* csrc/tbf_hostctl.cpp */
 		return fail (-22, "unknown parameter id");
-	in.ctlDirty = true;
+	e->inst[i].ctlDirty = true;
 	return 0;
 }
 
@@ -1252,774 +1153,6 @@ int tbf::engineDrain (tbf_engine* e)
 	return drainStages (e);
 }
 
-int tbf::controlById (Instance& in, int id, int value);
-
-/* a scheduled event (tbf_render_events) at its block boundary */
-static int applyEvent (tbf_engine* e, const tbf_event& ev)
-{
-	if (ev.inst >= e->inst.size ())
-		return fail (-22, "event for a bad instance");
-	switch (ev.kind) {
-		case TBF_EV_NOTE: return tbf_note (e, ev.inst, ev.id, ev.value != 0.0);
-		case TBF_EV_PARAM: return tbf_set_param (e, ev.inst, ev.id, ev.value);
-		case TBF_EV_CONTROL:
-			if (controlById (e->inst[ev.inst], ev.id, (int)ev.value) < 0)
-				return fail (-22, "bad control function id");
-			return 0;
-		case TBF_EV_PROGRAM: return tbf_program_install (e, ev.inst, (uint32_t)ev.id);
-		default: return fail (-22, "bad event kind");
-	}
-}
-
-/* one block of host control for instance i (the message-queue / active-list / routing
- * part of oscGenerateFragment and the effect setters' per-block constants).  Updates
- * the instance's current control e->hCtl[i] / program e->hProg; returns true when the
- * control the next block renders with changed. */
-static bool stepControl (tbf_engine* e, ChunkStaging& cs, uint32_t i, bool& progChanged, tbf_tgc_rec* rec = nullptr,
-                         std::vector<uint16_t>* msgOut = nullptr, std::vector<float>* gainOut = nullptr,
-                         std::vector<tbf_wh_params>* whOut = nullptr)
-{
-	Instance&    in      = e->inst[i];
-	tbf_seg_ctl& c       = e->hCtl[i];
-	progChanged          = false;
-	const bool   tgDirty = in.tg.dirty ();
-	if (!tgDirty && !in.progDirty && !in.ctlDirty && in.revOpt < 0)
-		return false;
-	if (tgDirty && rec) {
-		/* device control: the front end here, the per-wheel part in k_tgctl */
-		const size_t k  = in.tg.msg.size ();
-		const size_t kg = 2 * (size_t)in.tg.gainPairs (); /* the changed drawbar gains: (bus, gain) pairs */
-		if (msgOut) { /* a host worker's own message and gain lists (renderImpl merges them) */
-			const uint32_t at = (uint32_t)msgOut->size (), ag = (uint32_t)gainOut->size ();
-			msgOut->resize (at + k);
-			gainOut->resize (ag + kg);
-			in.tg.stepFront (msgOut->data () + at, at, gainOut->data () + ag, ag, *rec, c);
-		} else {
-			const uint32_t at = (uint32_t)cs.hMsg.size (), ag = (uint32_t)cs.hGain.size ();
-			cs.hMsg.resize (at + k);
-			cs.hGain.resize (ag + kg);
-			in.tg.stepFront (cs.hMsg.data () + at, at, cs.hGain.data () + ag, ag, *rec, c);
-		}
-		in.progDirty = false;
-		in.ctlDirty  = true;
-		progChanged  = true;
-	} else if (tgDirty) {
-		in.tg.step (in.prog, c);
-		in.progDirty = true;
-		in.ctlDirty  = true;
-	}
-	if (rec)
-		in.progDirty = false; /* device control: programs come from k_tgctl only */
-	if (in.progDirty) {
-		/* host control: the program in the instance's first slot, behind its header */
-		const size_t    np   = std::min (in.prog.size (), SLOT - 1);
-		tbf_prog_entry* slot = e->hProg.data () + PSLOTS * i * SLOT;
-		slot[0]              = tbf_prog_entry {};
-		slot[0].wheel        = 0xFFFF;
-		slot[0].pad          = (uint32_t)np;
-		std::copy (in.prog.begin (), in.prog.begin () + (long)np, slot + 1);
-		c.prog_off   = (uint32_t)(PSLOTS * i * SLOT);
-		c.prog_len   = (uint32_t)np;
-		in.progDirty = false;
-		progChanged  = true;
-	}
-	if (!tgDirty) {
-		/* mixdown fields that setters can change without a tonegen step */
-		c.swellPedalGain   = in.tg.swellPedalGain;
-		c.outputGain       = in.tg.swellPedalGain * in.tg.percDrawbarGain;
-		c.percEnvGainDecay = in.tg.percEnvGainDecay;
-		c.percEnvGainReset = in.tg.percEnvGainReset;
-		c.vibTable         = in.tg.vibTable;
-		c.vibMixed         = in.tg.vibMixed;
-	}
-	odCtl (in, e->cfg.sample_rate, c);
-	c.rvWet       = in.rvG;
-	c.whBypass    = (uint32_t)in.whBypass;
-	c.whRevOption = in.revOpt; /* a one-shot: the next block gets a fresh entry without it */
-	in.revOpt     = -1;
-	c.whSet       = 0;         /* a one-shot too: the whirl keeps a set until the next one */
-	if (in.whDirty) {
-		const tbf_wh_params& p = in.whr.cur;
-		if (whOut) { /* a host worker's own list (worker-local index, renderImpl rebases it) */
-			whOut->push_back (p);
-			c.whSet = (uint32_t)whOut->size ();
-		} else {
-			cs.hWh.push_back (p);
-			c.whSet = (uint32_t)cs.hWh.size ();
-		}
-		in.whDirty = false;
-	}
-	in.ctlDirty = (c.whRevOption >= 0) || c.whSet;
-	return true;
-}
-
-/* What renderBody decides for one chunk, handed to the phases of the render path beside
- * the chunk's staged arrays, e->stg[rp] (ChunkStaging). */
-struct Chunk {
-	uint64_t    cix;          /* the chunk's sequence number (tbf_engine.chunkSeq) */
-	int         rp;           /* control region and staging set: cix & 1 under device control, else 0 */
-	uint32_t    bset;         /* stage-buffer set: cix & 1 */
-	uint32_t    b0, want;     /* first block in the call, blocks planned (chunkLength) ... */
-	uint32_t    len;          /* ... and stepped: fewer when the host control ends the chunk early */
-	uint32_t    evBeg, evEnd; /* its events (block < b0 + want); evBeg moves past those the host control applied */
-	bool        delta, dfront; /* it has control deltas; the device front end (k_front) stepped it */
-	bool        dpipe, piped; /* device control and pipelining: uploads on us = gs[0]; stages on the group streams */
-	hipStream_t us;           /* the stream of the chunk's uploads and control kernels ... */
-	bool        usWaited;     /* ... which has waited for the previous user of this region (usWait) */
-};
-
-/* Device control: one chunk's host control (events + front-end steps) on host worker
- * threads, one contiguous instance range each.  Instances are independent and each keeps
- * its own events' order, so this equals the serial loop; only where the deltas sit in the
- * pool differs: worker t writes its k-th delta to position (first instance of its range) *
- * want + k of the staging (a range of m instances has at most m * want deltas), so nothing
- * is moved afterwards and the kernels reach the deltas through hIdx; dSeg lists the filled
- * segments for the uploads.  Events are [evBeg, evEnd) of ev (block < b0 + want; programme
- * changes excluded by the caller: randomizeDrawbars writes the shared programme table).
- * Fills what the serial loop fills: dCtl, hRec, hMsg, hCtlInst, stepped, hIdx (every row),
- * curIdx, chg, actList. */
-static int stepChunkParallel (tbf_engine* e, ChunkStaging& cs, Chunk& ck, uint32_t n, const tbf_event* ev)
-{
-	const uint32_t want = ck.want, b0 = ck.b0, evBeg = ck.evBeg, evEnd = ck.evEnd;
-	const unsigned T   = std::max (1u, std::min<unsigned> (hostThreads (), (n + 255) / 256));
-	const uint32_t per = (n + T - 1) / T;
-	auto&          out = e->parStep;
-	out.resize (T);
-	for (auto& o : out) {
-		o.msgs.clear (), o.gains.clear (), o.whs.clear (), o.act.clear (), o.ctlInst.clear (), o.evs.clear ();
-		o.dInst.clear (), o.fulls.clear (), o.err.clear ();
-		o.nd = 0;
-		o.rc = 0;
-	}
-	for (uint32_t a : e->actList) /* the active list by range, in order */
-		out[a / per].act.push_back (a);
-	/* the events by instance range, in order: a parallel counting partition over T segments
-	 * of the event list (a serial pass cost ~2 ms at 524k events) */
-	{
-		const uint32_t        nev = evEnd - evBeg, seg = (nev + T - 1) / T;
-		std::vector<uint32_t> cnt ((size_t)T * T, 0);
-		parallelFor (T, [&] (uint32_t sgm) {
-			const uint32_t k0 = evBeg + std::min (nev, sgm * seg), k1 = evBeg + std::min (nev, (sgm + 1) * seg);
-			for (uint32_t k = k0; k < k1; k++)
-				cnt[(size_t)sgm * T + ev[k].inst / per]++;
-		});
-		for (unsigned t = 0; t < T; t++) {
-			uint32_t tot = 0;
-			for (unsigned sgm = 0; sgm < T; sgm++) {
-				const uint32_t c                = cnt[(size_t)sgm * T + t];
-				cnt[(size_t)sgm * T + t] = tot; /* the segment's first slot in worker t's list */
-				tot += c;
-			}
-			out[t].evs.resize (tot);
-		}
-		parallelFor (T, [&] (uint32_t sgm) {
-			const uint32_t k0 = evBeg + std::min (nev, sgm * seg), k1 = evBeg + std::min (nev, (sgm + 1) * seg);
-			uint32_t*      at = cnt.data () + (size_t)sgm * T;
-			for (uint32_t k = k0; k < k1; k++) {
-				const uint32_t t = ev[k].inst / per;
-				out[t].evs[at[t]++] = k;
-			}
-		});
-	}
-	cs.hRec.resize ((size_t)n * want);
-	e->lastEmit.resize (n);
-	e->lastProg.resize (n);
-	e->dseen.assign (n, 0);
-	const auto             ph0 = std::chrono::steady_clock::now ();
-	std::vector<uint64_t>  thNs (T);
-	parallelFor (T, [&] (uint32_t t) {
-		const auto           th0  = std::chrono::steady_clock::now ();
-		tbf_engine::ParStep& o    = out[t];
-		const uint32_t       i0   = t * per, i1 = std::min (n, i0 + per);
-		const uint32_t       base = i0 * want;
-		tbf_tgc_rec*         Rr   = cs.hRec.data () + base; /* the worker's part of the staging */
-		uint32_t* const      idx  = cs.hIdx.data ();
-		tlAct                     = &o.act; /* (markActive's pushes; o.act is rebuilt below) */
-		/* instance-major: an instance's blocks one after another, so its host state stays in
-		 * the core's L1 over the chunk (block-major passes over the range missed it on every
-		 * block).  Instances are independent; each keeps its events in order (a stable
-		 * counting sort of the range's events by instance). */
-		std::vector<uint32_t>& eo = o.eoff;
-		std::vector<uint32_t>& es = o.esort;
-		eo.assign ((size_t)(i1 - i0) + 1, 0);
-		for (uint32_t k : o.evs)
-			eo[ev[k].inst - i0 + 1]++;
-		for (uint32_t i = i0; i < i1; i++)
-			eo[i - i0 + 1] += eo[i - i0];
-		es.resize (o.evs.size ());
-		{
-			std::vector<uint32_t>& fill = o.efill;
-			fill.assign (eo.begin (), eo.end () - 1);
-			for (uint32_t k : o.evs)
-				es[fill[ev[k].inst - i0]++] = k;
-		}
-		for (uint32_t i = i0; i < i1 && !o.rc; i++) {
-			uint32_t ci = i; /* the instance's pool entry at the current block */
-			uint32_t k = eo[i - i0], kEnd = eo[i - i0 + 1];
-			for (uint32_t len = 0; len < want; len++) {
-				for (; k < kEnd && ev[es[k]].block <= b0 + len; k++) {
-					if ((o.rc = applyEvent (e, ev[es[k]]))) {
-						o.err = g_err;
-						break;
-					}
-					markActive (e, i);
-				}
-				if (o.rc)
-					break;
-				if (e->inAct[i]) {
-					bool         pc;
-					tbf_tgc_rec& rec = Rr[o.nd];
-					if (!e->dseen[i]) { /* the entry the device holds for i at the chunk start */
-						e->dseen[i]    = 1;
-						e->lastEmit[i] = e->hCtl[i];
-					}
-					if (stepControl (e, cs, i, pc, &rec, &o.msgs, &o.gains, &o.whs)) {
-						const uint32_t d = base + o.nd++;
-						tbf_seg_ctl    c = e->hCtl[i];
-						if (pc) {
-							c.prog_off = (uint32_t)(PERSIST (n) + ((size_t)ck.rp * n * TBF_CHUNK + d) * SLOT);
-							if (!e->stepped[i]) {
-								e->stepped[i] = 1;
-								o.ctlInst.push_back (i);
-							}
-						} else {
-							memset (&rec, 0, sizeof (rec));
-							if (ci >= n)
-								c.prog_off = e->lastProg[i];
-						}
-						e->lastProg[i] = c.prog_off;
-						if (!e->dhas[i]) {
-							e->dhas[i] = 1;
-							o.dInst.push_back (i);
-						}
-						/* a delta that changes only what a key / drawbar step changes travels as
-						 * its record (k_tgctl rebuilds the entry); any other change as a full entry */
-						tbf_seg_ctl& le = e->lastEmit[i];
-						tbf_seg_ctl  tc = le;
-						tc.prog_off       = c.prog_off;
-						tc.keyCompTarget  = c.keyCompTarget;
-						tc.resetPercAtEnd = c.resetPercAtEnd;
-						tc.routing        = c.routing;
-						if (memcmp (&tc, &c, sizeof (c)) != 0) {
-							o.fulls.push_back (c);
-							rec.full = (uint32_t)o.fulls.size ();
-							le       = c;
-						}
-						rec.keyCompTarget = c.keyCompTarget;
-						rec.flags         = (uint8_t)((rec.flags & ~8u) | (c.resetPercAtEnd ? 8u : 0u));
-						rec.oldRouting    = (uint8_t)c.routing;
-						ci                = n + d;
-						e->chg[i]         = 1;
-					} else
-						e->inAct[i] = 0;
-				}
-				idx[(size_t)len * n + i] = ci;
-			}
-			e->curIdx[i] = ci;
-		}
-		o.act.clear (); /* the range's instances still active, in order */
-		for (uint32_t i = i0; i < i1; i++)
-			if (e->inAct[i])
-				o.act.push_back (i);
-		tlAct = nullptr;
-		thNs[t] = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds> (std::chrono::steady_clock::now () - th0).count ();
-	});
-	const auto ph1 = std::chrono::steady_clock::now ();
-	std::vector<size_t> mb (T), gb (T), wb (T), fb (T);
-	size_t              nm = 0, ng = 0, nw = 0, nf = 0;
-	e->dSeg.clear ();
-	for (unsigned t = 0; t < T; t++) {
-		if (out[t].rc)
-			return fail (out[t].rc, out[t].err); /* on the calling thread */
-		mb[t] = nm;
-		nm += out[t].msgs.size ();
-		gb[t] = ng;
-		ng += out[t].gains.size ();
-		wb[t] = nw;
-		nw += out[t].whs.size ();
-		fb[t] = nf;
-		nf += out[t].fulls.size ();
-		if (out[t].nd) {
-			e->dSeg.push_back ({t * per * want, out[t].nd});
-			ck.delta = true;
-		}
-	}
-	if (e->dSeg.empty ())
-		e->dSeg.push_back ({0, 0});
-	cs.hMsg.resize (nm);
-	cs.hGain.resize (ng);
-	cs.hWh.resize (nw);
-	cs.hFull.resize (nf);
-	if (nm || ng || nw || nf)
-		parallelFor (T, [&] (uint32_t t) { /* message, gain, full entry and whirl set offsets: worker-local -> chunk */
-			tbf_engine::ParStep& o    = out[t];
-			const size_t         base = (size_t)t * per * want;
-			for (size_t d = base; d < base + o.nd; d++) {
-				tbf_tgc_rec& r = cs.hRec[d];
-				if (r.flags & 0x80)
-					r.msgOff += (uint32_t)mb[t];
-				if (r.flags & 4)
-					r.gainOff += (uint32_t)gb[t];
-				if (r.full)
-					r.full += (uint32_t)fb[t];
-			}
-			for (tbf_seg_ctl& f : o.fulls)
-				if (f.whSet)
-					f.whSet += (uint32_t)wb[t];
-			if (!o.fulls.empty ())
-				memcpy ((void*)(cs.hFull.data () + fb[t]), o.fulls.data (), o.fulls.size () * sizeof (tbf_seg_ctl));
-			if (!o.whs.empty ())
-				memcpy ((void*)(cs.hWh.data () + wb[t]), o.whs.data (), o.whs.size () * sizeof (tbf_wh_params));
-			if (!o.msgs.empty ())
-				memcpy (cs.hMsg.data () + mb[t], o.msgs.data (), o.msgs.size () * sizeof (uint16_t));
-			if (!o.gains.empty ())
-				memcpy (cs.hGain.data () + gb[t], o.gains.data (), o.gains.size () * sizeof (float));
-		});
-	e->actList.clear ();
-	for (unsigned t = 0; t < T; t++) {
-		e->actList.insert (e->actList.end (), out[t].act.begin (), out[t].act.end ());
-		for (uint32_t i : out[t].ctlInst)
-			cs.hCtlInst.push_back (i);
-		for (uint32_t i : out[t].dInst)
-			cs.hDInst.push_back (i);
-	}
-	if (e->dbgPhases) {
-		const auto ph2 = std::chrono::steady_clock::now ();
-		auto       ms  = [] (auto a, auto b) { return std::chrono::duration<double, std::milli> (b - a).count (); };
-		uint64_t   mx = 0, sum = 0;
-		for (uint64_t v : thNs) {
-			mx = std::max (mx, v);
-			sum += v;
-		}
-		fprintf (stderr, "stepChunkParallel T=%u: step %.3f ms (thread max %.3f, mean %.3f) merge %.3f ms\n", T,
-		         ms (ph0, ph1), mx / 1e6, sum / 1e6 / T, ms (ph1, ph2));
-	}
-	ck.evBeg = evEnd;
-	ck.len   = want;
-	return 0;
-}
-
-/* Device front end: a chunk whose events are all notes or front-end parameters (drawbars,
- * the vibrato and percussion switches: frontParam), over instances whose control is
- * otherwise settled (no other parameter, programme, rotor or whirl change pending, no
- * drawbar or routing step), is stepped by k_front on the device (csrc/tbf_ctl.hip): the
- * messages, the stepped blocks, the control records and the index table come from the
- * instances' front-end state at the chunk start and their events.  The host only
- * partitions the events by instance and applies them to its own mirror state (the truth
- * for any later host-stepped chunk): no records, no index table. */
-static bool frontClean (const Instance& in)
-{
-	const TgControl& t = in.tg;
-	return !in.ctlDirty && !in.progDirty && in.revOpt < 0 && !in.whDirty && t.msg.empty () && !t.drawBarChange &&
-	       t.oldRouting == t.newRouting && t.gainsSent && t.gainMask == 0 &&
-	       /* the rotary option a drum / horn event derives stays an exact small integer */
-	       fabs (in.params[TBF_P_DRUM]) < 1e6 && fabs (in.params[TBF_P_HORN]) < 1e6;
-}
-
-/* a parameter event the device front end steps, as a TBF_FEV_* word without the block; 0
- * for any other.  Drawbars and the vibrato and percussion switches change what a control
- * record carries; the effect setters (rotary speed, overdrive on / character, reverb mix,
- * percussion volume / decay, swell, whirl bypass, vibrato type: src/clap.cpp:162-207) the
- * entry's effect fields (TBF_FEV_EFFECT, their values in fevVal).  Values the setters take
- * outside their sane range (a character outside [0, 1], a swell outside [0, 2], huge or
- * non-finite numbers) leave the chunk to the host front end. */
-static uint32_t frontParam (int32_t idx, float v)
-{
-	auto fx = [] (uint32_t k) { return TBF_FEV_PARAM | (TBF_FEV_EFFECT << 12) | k; };
-	const bool small = fabsf (v) < 1e6f; /* false for NaN too */
-	switch (idx) {
-		case TBF_P_DRUM:
-		case TBF_P_HORN: return small ? fx (TBF_FX_ROTOR) : 0;
-		case TBF_P_OVERDRIVE: return small ? fx (TBF_FX_CLEAN) : 0;
-		case TBF_P_CHARACTER: return v >= 0.0f && v <= 1.0f ? fx (TBF_FX_CHARACTER) : 0;
-		case TBF_P_REVERB: return std::isfinite (v) ? fx (TBF_FX_REVERB) : 0;
-		case TBF_P_PERCUSSION_VOLUME: return small ? fx (TBF_FX_PERC_SOFT) : 0;
-		case TBF_P_PERCUSSION_DECAY: return small ? fx (TBF_FX_PERC_FAST) : 0;
-		case TBF_P_SWELL: return v >= 0.0f && v <= 2.0f ? fx (TBF_FX_SWELL) : 0;
-		case TBF_P_WHIRL_BYPASS: return small ? fx (TBF_FX_BYPASS) : 0;
-		case TBF_P_VIBRATO_TYPE: return small ? fx (TBF_FX_VIBTYPE) : 0;
-		default: break;
-	}
-	int bus = -1;
-	if (idx >= TBF_P_DRAWBAR_MIN && idx <= TBF_P_DRAWBAR_MAX)
-		bus = idx;
-	else if (idx >= TBF_P_BUS_DRAWBAR_BASE && idx < TBF_P_BUS_DRAWBAR_BASE + 27)
-		bus = idx - TBF_P_BUS_DRAWBAR_BASE;
-	if (bus >= 0) {
-		const unsigned st = (unsigned)rint (v); /* as tbf_set_param hands it to setDrawBar */
-		return TBF_FEV_PARAM | (TBF_FEV_DRAWBAR << 12) | ((st > 8 ? 15u : st) << 5) | (uint32_t)bus;
-	}
-	const uint32_t fl = (int)rint (v) != 0 ? 1u : 0u;
-	switch (idx) {
-		case TBF_P_VIBRATO: return TBF_FEV_PARAM | (TBF_FEV_VIB_UPPER << 12) | (fl << 9);
-		case TBF_P_VIBRATO_LOWER: return TBF_FEV_PARAM | (TBF_FEV_VIB_LOWER << 12) | (fl << 9);
-		case TBF_P_PERCUSSION: return TBF_FEV_PARAM | (TBF_FEV_PERC << 12) | (fl << 9);
-		case TBF_P_PERCUSSION_HARMONIC: return TBF_FEV_PARAM | (TBF_FEV_PERC_FIRST << 12) | (fl << 9);
-		default: return 0;
-	}
-}
-static uint32_t frontParam (const tbf_event& E) { return frontParam (E.id, (float)E.value); }
-
-/* the instances' front-end cleanliness (e->fclean), once per chunk; false when an active
- * instance is not clean (its pending step is the host's) */
-static bool frontCleanAll (tbf_engine* e)
-{
-	const uint32_t        n  = (uint32_t)e->inst.size ();
-	std::vector<uint8_t>& cl = e->fclean;
-	cl.resize (n);
-	const unsigned T   = std::max (1u, std::min<unsigned> (hostThreads (), (n + 255) / 256));
-	const uint32_t per = (n + T - 1) / T;
-	parallelFor (T, [&] (uint32_t t) {
-		for (uint32_t i = t * per; i < std::min (n, (t + 1) * per); i++)
-			cl[i] = frontClean (e->inst[i]) ? 1 : 0;
-	});
-	for (uint32_t i : e->actList)
-		if (!cl[i])
-			return false;
-	return true;
-}
-
-/* One parallel pass over a chunk's events (sorted by block): a programme event among them,
- * an event for a bad instance, and -- with cl, the instances' cleanliness -- whether the
- * device front end takes them all (notes and frontParam kinds on clean instances), with
- * the events as compact records bucketed by (segment, instance range) for stepChunkFront.
- * (Three passes over the 24-B events used to do this: ~0.2 ms each at 524 k events; then a
- * scan, a partition and a gather by instance, ~0.3 ms each.) */
-static void scanChunk (uint32_t n, uint32_t b0, const tbf_event* ev, uint32_t evBeg, uint32_t evEnd, const uint8_t* cl,
-                       bool& progEv, bool& bad, bool& front, ChunkScan& cs)
-{
-	const uint32_t nev = evEnd - evBeg;
-	cs.T   = std::max (1u, std::min<unsigned> (hostThreads (), (n + 255) / 256));
-	assert (cs.T <= TBF_MAX_HOST_THREADS);
-	cs.per = (n + cs.T - 1) / cs.T;
-	cs.Te  = std::max (1u, std::min (hostThreads (), (nev + 32767) / 32768));
-	cs.seg = (nev + cs.Te - 1) / cs.Te;
-	if (cl) {
-		cs.rec.resize (std::max<uint32_t> (nev, 1));
-		cs.boff.resize ((size_t)cs.Te * (cs.T + 1));
-	}
-	std::vector<char> pe (cs.Te, 0), bd (cs.Te, 0), fr (cs.Te, 0);
-	parallelFor (cs.Te, [&] (uint32_t sgm) {
-		const uint32_t k0 = evBeg + std::min (nev, sgm * cs.seg), k1 = evBeg + std::min (nev, (sgm + 1) * cs.seg);
-		bool           p = false, b = false, f = cl != nullptr; /* locals: the flags share a cache line */
-		uint32_t       c[TBF_MAX_HOST_THREADS + 1] = {};         /* events per instance range (T <= TBF_MAX_HOST_THREADS) */
-		for (uint32_t k = k0; k < k1; k++) {
-			const tbf_event& E = ev[k];
-			p                  = p || E.kind == TBF_EV_PROGRAM;
-			if (E.inst >= n) {
-				b = true;
-				f = false;
-				continue;
-			}
-			if (f) {
-				f = (E.kind == TBF_EV_NOTE || (E.kind == TBF_EV_PARAM && frontParam (E))) && cl[E.inst];
-				c[E.inst / cs.per]++;
-			}
-		}
-		if (f) { /* the records, by range, into this segment's own part of rec (no shared lines) */
-			uint32_t* bo = cs.boff.data () + (size_t)sgm * (cs.T + 1);
-			uint32_t  at[TBF_MAX_HOST_THREADS];
-			bo[0] = k0 - evBeg;
-			for (unsigned t = 0; t < cs.T; t++) {
-				at[t]     = bo[t];
-				bo[t + 1] = bo[t] + c[t];
-			}
-			ChunkScan::Rec* rec = cs.rec.data ();
-			for (uint32_t k = k0; k < k1; k++) {
-				const tbf_event& E = ev[k];
-				rec[at[E.inst / cs.per]++] = {E.inst, (E.block - b0) << 2 | (E.kind == TBF_EV_PARAM ? 1u : 0u) |
-				                                          (E.value != 0.0 ? 2u : 0u),
-				                              E.id, (float)E.value};
-			}
-		}
-		pe[sgm] = p;
-		bd[sgm] = b;
-		fr[sgm] = f;
-	});
-	progEv = bad = false;
-	front        = cl != nullptr;
-	for (unsigned t = 0; t < cs.Te; t++) {
-		progEv = progEv || pe[t];
-		bad    = bad || bd[t];
-		front  = front && fr[t];
-	}
-}
-
-static int stepChunkFront (tbf_engine* e, ChunkStaging& cs, Chunk& ck, uint32_t n)
-{
-	const ChunkScan& sc = e->scan; /* the chunk's events, bucketed by scanChunk */
-	const unsigned T   = sc.T;
-	const uint32_t per = sc.per;
-	auto&          out = e->parStep;
-	const auto     f0  = std::chrono::steady_clock::now ();
-	out.resize (T);
-	for (auto& o : out) {
-		o.act.clear ();
-		o.ctlInst.clear ();
-		o.evs.clear ();
-		o.gainLocal = 0;
-		o.fx        = false;
-	}
-	/* the events by instance range come from scanChunk's buckets, in event order */
-	const auto            f1 = std::chrono::steady_clock::now ();
-	std::vector<uint32_t> wbase (T + 1, 0);
-	auto seg = [&] (unsigned sgm, unsigned t) { return sc.boff.data () + (size_t)sgm * (T + 1) + t; };
-	for (unsigned t = 0; t < T; t++) {
-		size_t c = 0;
-		for (unsigned sgm = 0; sgm < sc.Te; sgm++)
-			c += seg (sgm, t)[1] - seg (sgm, t)[0];
-		wbase[t + 1] = wbase[t] + (uint32_t)c;
-	}
-	cs.hFevOff.resize (n + 1);
-	cs.hFev.resize (std::max<uint32_t> (wbase[T], 1));
-	cs.hFevVal.resize (std::max<uint32_t> (wbase[T], 1));
-	cs.hFront.resize (n);
-	const bool          dbgPh = e->dbgPhases;
-	std::vector<double> thMs (dbgPh ? 3 * T : 0);
-	parallelFor (T, [&] (uint32_t t) {
-		const auto             g0 = std::chrono::steady_clock::now ();
-		tbf_engine::ParStep&   o  = out[t];
-		const uint32_t         i0 = t * per, i1 = std::min (n, i0 + per);
-		std::vector<uint32_t>& eo = o.eoff;
-		auto&                  es = o.erec;
-		eo.assign ((size_t)(i1 > i0 ? i1 - i0 : 0) + 1, 0);
-		for (unsigned sgm = 0; sgm < sc.Te; sgm++)
-			for (uint32_t k = seg (sgm, t)[0]; k < seg (sgm, t)[1]; k++)
-				eo[sc.rec[k].inst - i0 + 1]++;
-		for (uint32_t i = i0; i < i1; i++)
-			eo[i - i0 + 1] += eo[i - i0];
-		es.resize (wbase[t + 1] - wbase[t]);
-		{ /* the range's events by instance (a stable counting sort of its buckets, read in
-		   * order, so the per-instance pass below reads them sequentially) */
-			std::vector<uint32_t>& fill = o.efill;
-			fill.assign (eo.begin (), eo.end () - 1);
-			for (unsigned sgm = 0; sgm < sc.Te; sgm++)
-				for (uint32_t k = seg (sgm, t)[0]; k < seg (sgm, t)[1]; k++) {
-					const ChunkScan::Rec& r = sc.rec[k];
-					es[fill[r.inst - i0]++] = {r.bf >> 2, r.id, r.v, r.bf & 3u};
-				}
-		}
-		const auto g1 = std::chrono::steady_clock::now ();
-		for (uint32_t i = i0; i < i1; i++) {
-			Instance&        in = e->inst[i];
-			TgControl&       tg = in.tg;
-			tbf_front_state& F  = cs.hFront[i];
-			memset (&F, 0, sizeof (F));
-			static_assert (sizeof (F.keys) == sizeof (tg.keyBits), "384 key bits");
-			memcpy (F.keys, tg.keyBits, sizeof (F.keys));
-			F.keyDown         = tg.keyDownCount;
-			F.upperDown       = (int32_t)tg.upperKeyCount;
-			F.pending         = tg.steadyPending ? 1u : 0u;
-			F.percSendBus     = tg.percSendBus;
-			F.routing         = tg.oldRouting;
-			F.percEnabled     = tg.percEnabled ? 1 : 0;
-			F.percTrigRestore = tg.percTrigRestore;
-			F.percTriggerBus  = tg.percTriggerBus;
-			F.percSendBusA    = tg.percSendBusA;
-			F.percSendBusB    = tg.percSendBusB;
-			F.gainOff         = o.gainLocal; /* + the thread's base, below */
-			F.percReset[0]    = tg.percEnvScaling * tg.percEnvGainResetNorm; /* as setPercVolume */
-			F.percReset[1]    = tg.percEnvScaling * tg.percEnvGainResetSoft;
-			F.percDrawbar[0]  = tg.percDrawbarNormalGain;
-			F.percDrawbar[1]  = tg.percDrawbarSoftGain;
-			F.percDecay[0]    = tg.percEnvGainDecaySlowNorm;
-			F.percDecay[1]    = tg.percEnvGainDecaySlowSoft;
-			F.percDecay[2]    = tg.percEnvGainDecayFastNorm;
-			F.percDecay[3]    = tg.percEnvGainDecayFastSoft;
-			F.percSoft        = tg.percIsSoft != 0;
-			F.percFast        = tg.percIsFast != 0;
-			F.swell           = tg.swellPedalGain;
-			cs.hFevOff[i]     = wbase[t] + eo[i - i0];
-			/* the host's front state takes the events too (it stays the truth for any later
-			 * host-stepped chunk): the same setters, block by block, and the same steps as
-			 * the device -- a block with inputs steps, and so does the one after it */
-			bool     stepped = F.pending != 0, pend = F.pending != 0, fxd = false;
-			uint32_t oldR = tg.oldRouting, ng = 0, msgsB = 0;
-			int      curB = -1;
-			auto     closeBlock = [&] () {
-                const bool rcp = tg.newRouting != oldR, in = msgsB > 0 || tg.drawBarChange || rcp;
-                ng += (uint32_t)__builtin_popcount (tg.gainMask);
-                stepped = stepped || in;
-                pend    = in;
-                oldR    = tg.newRouting;
-                tg.drawBarChange = 0;
-                tg.gainMask      = 0;
-                msgsB            = 0;
-			};
-			for (uint32_t j = eo[i - i0]; j < eo[i - i0 + 1]; j++) {
-				const auto&    E   = es[j];
-				const uint32_t blk = E.blk;
-				if ((int)blk != curB) {
-					if (curB >= 0)
-						closeBlock ();
-					if (curB >= 0 ? blk > (uint32_t)curB + 1 : blk > 0)
-						pend = false; /* blocks without events between: the pending step is done */
-					curB = (int)blk;
-				}
-				if (E.flag & 1u) {
-					const float    v = E.v;
-					const uint32_t w = frontParam (E.id, v);
-					cs.hFev[wbase[t] + j] = w | (blk << 16);
-					if (E.id >= 0 && E.id < 64)
-						in.params[E.id] = v;
-					const uint32_t op = (w >> 12) & 7u;
-					if (op == TBF_FEV_EFFECT) {
-						/* tbf_set_param's setter on the mirror, and the value k_front applies */
-						float x = 0.0f;
-						switch (w & 31u) {
-							case TBF_FX_ROTOR:
-								x = (float)(int)(floor (in.params[TBF_P_DRUM]) + 3 * floor (in.params[TBF_P_HORN]));
-								break;
-							case TBF_FX_CLEAN:
-								in.odClean = (int)rint (1.0f - v);
-								x          = (float)in.odClean;
-								break;
-							case TBF_FX_CHARACTER:
-								setCharacter (in, v);
-								x = v;
-								break;
-							case TBF_FX_REVERB:
-								in.rvG = v;
-								x      = v;
-								break;
-							case TBF_FX_PERC_SOFT: {
-								const int soft = (int)(1 - rint (v));
-								tg.setPercVolume (soft);
-								x = soft != 0 ? 1.0f : 0.0f;
-								break;
-							}
-							case TBF_FX_PERC_FAST: {
-								const int fast = (int)rint (v);
-								tg.setPercFast (fast);
-								x = fast != 0 ? 1.0f : 0.0f;
-								break;
-							}
-							case TBF_FX_SWELL: {
-								unsigned char u   = (unsigned char)rint (v * 127.0);
-								tg.swellPedalGain = (float)((tg.outputLevelTrim * ((double)u)) / 127.0);
-								x                 = tg.swellPedalGain;
-								break;
-							}
-							case TBF_FX_BYPASS:
-								in.whBypass = (int)rint (v);
-								x           = (float)in.whBypass;
-								break;
-							case TBF_FX_VIBTYPE: {
-								const int p = (int)floor (v);
-								tg.setVibratoFromInt (p);
-								x = (float)p;
-								break;
-							}
-						}
-						cs.hFevVal[wbase[t] + j] = x;
-						fxd                      = true;
-						continue;
-					}
-					if (op == TBF_FEV_DRAWBAR)
-						tg.setDrawBar ((int)(w & 31u), (unsigned)rint (v));
-					else if (op == TBF_FEV_VIB_UPPER)
-						tg.setVibratoUpper ((int)rint (v));
-					else if (op == TBF_FEV_VIB_LOWER)
-						tg.setVibratoLower ((int)rint (v));
-					else if (op == TBF_FEV_PERC)
-						tg.setPercEnabled ((int)rint (v));
-					else
-						tg.setPercFirst ((int)rint (v));
-					continue;
-				}
-				const bool on = (E.flag & 2u) != 0;
-				const bool ok = E.id >= 0 && E.id < 384; /* oscKeyOn/Off ignore keys >= MAX_KEYS */
-				cs.hFev[wbase[t] + j] = (ok ? (uint32_t)E.id : 0x0fffu) | (on ? 1u << 12 : 0u) | (blk << 16);
-				msgsB += ok ? (uint32_t)tg.noteCount (E.id, on) : 0u;
-			}
-			if (curB >= 0) {
-				closeBlock ();
-				if ((uint32_t)curB + 1 < ck.want)
-					pend = false;
-			} else
-				pend = false; /* no events: block 0 takes the pending step */
-			o.gainLocal += 2 * ng;
-			tg.oldRouting = tg.newRouting;
-			if (fxd) {
-				/* effect setters: the control entry the instance ends the chunk with (the
-				 * device wrote the chunk's own entries); the rotary option was a one-shot */
-				tbf_seg_ctl& c     = e->hCtl[i];
-				odCtl (in, e->cfg.sample_rate, c);
-				c.rvWet            = in.rvG;
-				c.whBypass         = (uint32_t)in.whBypass;
-				c.swellPedalGain   = tg.swellPedalGain;
-				c.outputGain       = tg.swellPedalGain * tg.percDrawbarGain;
-				c.percEnvGainDecay = tg.percEnvGainDecay;
-				c.percEnvGainReset = tg.percEnvGainReset;
-				c.vibTable         = tg.vibTable;
-				c.vibMixed         = tg.vibMixed;
-				c.whRevOption      = -1;
-				c.whSet            = 0;
-				in.revOpt          = -1;
-				in.ctlDirty        = false;
-				e->chg[i]          = 1;
-				o.fx               = true;
-			}
-			if (stepped) { /* stepped blocks: control deltas */
-				e->stepped[i] = 1;
-				o.ctlInst.push_back (i);
-				e->chg[i] = 1;
-				const int kd = tg.keyDownCount;
-				e->hCtl[i].keyCompTarget  = tg.tpl->keyCompTable[kd < 0 ? 0 : (kd > 127 ? 127 : kd)];
-				e->hCtl[i].resetPercAtEnd = tg.upperKeyCount == 0;
-				e->hCtl[i].routing        = tg.oldRouting;
-			}
-			const bool last = pend;
-			tg.steadyPending = last;
-			e->inAct[i]      = tg.steadyPending ? 1 : 0;
-			if (e->inAct[i])
-				o.act.push_back (i);
-		}
-		if (dbgPh) {
-			const auto g2 = std::chrono::steady_clock::now ();
-			thMs[3 * t]     = std::chrono::duration<double, std::milli> (g0 - f1).count (); /* start delay */
-			thMs[3 * t + 1] = std::chrono::duration<double, std::milli> (g1 - g0).count (); /* sort */
-			thMs[3 * t + 2] = std::chrono::duration<double, std::milli> (g2 - g1).count (); /* mirror */
-		}
-	});
-	cs.hFevOff[n] = wbase[T];
-	{ /* the gain-pair slots: each range's base */
-		std::vector<uint32_t> gb (T + 1, 0);
-		for (unsigned t = 0; t < T; t++)
-			gb[t + 1] = gb[t] + out[t].gainLocal;
-		e->frontGain = gb[T];
-		parallelFor (T, [&] (uint32_t t) {
-			for (uint32_t i = t * per; i < std::min (n, (t + 1) * per); i++)
-				cs.hFront[i].gainOff += gb[t];
-		});
-	}
-	e->actList.clear ();
-	for (unsigned t = 0; t < T; t++) {
-		e->actList.insert (e->actList.end (), out[t].act.begin (), out[t].act.end ());
-		for (uint32_t i : out[t].ctlInst)
-			cs.hCtlInst.push_back (i);
-	}
-	ck.delta = !cs.hCtlInst.empty ();
-	for (unsigned t = 0; t < T; t++)
-		ck.delta = ck.delta || out[t].fx;
-	if (dbgPh) {
-		auto ms = [] (auto a, auto b) { return std::chrono::duration<double, std::milli> (b - a).count (); };
-		fprintf (stderr, "stepChunkFront T=%u: partition %.3f ms, instances %.3f ms\n", T, ms (f0, f1),
-		         ms (f1, std::chrono::steady_clock::now ()));
-		double mx[3] = {0, 0, 0}, sm[3] = {0, 0, 0};
-		for (unsigned t = 0; t < T; t++)
-			for (int q = 0; q < 3; q++) {
-				mx[q] = std::max (mx[q], thMs[3 * t + q]);
-				sm[q] += thMs[3 * t + q] / T;
-			}
-		fprintf (stderr, "  threads (mean / max ms): start %.3f / %.3f, sort %.3f / %.3f, mirror %.3f / %.3f\n", sm[0], mx[0],
-		         sm[1], mx[1], sm[2], mx[2]);
-	}
-	ck.evBeg = ck.evEnd;
-	ck.len   = ck.want;
-	return 0;
-}
-
 /* The inter-stage buffers for a call of nblocks blocks: each holds, per instance, one
  * chunk of stageBlocks blocks -- a power of two from TBF_CHUNK up to steadyChunk, just
  * enough for the longest chunk this call can make, so a caller that renders 64 blocks at a
@@ -2319,145 +1452,6 @@ static int refreshControlPool (tbf_engine* e, ChunkStaging& cs, Chunk& ck, uint3
 	return 0;
 }
 
-/* The serial host control step, block by block: entry indices per (block, instance), new
- * pool entries only where an instance's control changes.  Host control's one path; device
- * control's for few active instances or a programme event.  May end the chunk early. */
-static int stepChunkSerial (tbf_engine* e, ChunkStaging& cs, Chunk& ck, uint32_t n, const tbf_event* ev)
-{
-	const size_t           dprogCap = DPROG_CAP (n);
-	std::vector<uint32_t>& cur      = e->curIdx;
-	uint32_t&              len      = ck.len;
-	for (; len < ck.want; len++) {
-		if (!e->devCtl && e->dProg.size () + (size_t)n * SLOT > dprogCap && len > 0)
-			break; /* delta program pool full: end the chunk here */
-		if (ck.delta && len >= TBF_CHUNK)
-			break; /* a chunk with deltas ends at TBF_CHUNK blocks, before the next block's events */
-		for (; ck.evBeg < ck.evEnd && ev[ck.evBeg].block <= ck.b0 + len; ck.evBeg++) {
-			if (int rc = applyEvent (e, ev[ck.evBeg]))
-				return rc;
-			markActive (e, ev[ck.evBeg].inst);
-		}
-		/* only the instances whose control may still change are stepped: one that
-		 * steps to no change stays unchanged until an event touches it */
-		const bool hadDelta = ck.delta;
-		size_t     keep     = 0;
-		for (size_t a = 0; a < e->actList.size (); a++) {
-			const uint32_t i = e->actList[a];
-			bool           pc;
-			tbf_tgc_rec    rec;
-			if (stepControl (e, cs, i, pc, e->devCtl ? &rec : nullptr)) {
-				tbf_seg_ctl c = e->hCtl[i];
-				if (e->devCtl) {
-					/* a stepped delta gets its own program slot, which k_tgctl fills; the
-					 * others play the program before them */
-					if (pc) {
-						c.prog_off = (uint32_t)(PERSIST (n) + ((size_t)ck.rp * n * TBF_CHUNK + cs.dCtl.size ()) * SLOT);
-						if (!e->stepped[i]) {
-							e->stepped[i] = 1;
-							cs.hCtlInst.push_back (i);
-						}
-					} else {
-						memset (&rec, 0, sizeof (rec));
-						if (cur[i] >= n)
-							c.prog_off = cs.dCtl[cur[i] - n].prog_off;
-					}
-					if (!e->dhas[i]) {
-						e->dhas[i] = 1;
-						cs.hDInst.push_back (i);
-					}
-					cs.hFull.push_back (c); /* every delta a full entry on this path */
-					rec.full = (uint32_t)cs.hFull.size ();
-					cs.hRec.push_back (rec);
-				} else if (pc) {
-					c.prog_off = (uint32_t)(PERSIST (n) + e->dProg.size ());
-					e->dProg.insert (e->dProg.end (), e->hProg.begin () + PSLOTS * i * SLOT,
-					                 e->hProg.begin () + PSLOTS * i * SLOT + 1 + c.prog_len);
-				} else if (cur[i] >= n)
-					c.prog_off = cs.dCtl[cur[i] - n].prog_off; /* program of the previous delta */
-				cur[i] = n + (uint32_t)cs.dCtl.size ();
-				cs.dCtl.push_back (c);
-				e->chg[i] = 1;
-				ck.delta  = true;
-				e->actList[keep++] = i;
-			} else
-				e->inAct[i] = 0;
-		}
-		e->actList.resize (keep);
-		/* entry index table: written only once the chunk has a delta (before that
-		 * every row is the identity) */
-		if (ck.delta) {
-			if (!hadDelta)
-				for (uint32_t r = 0; r < len; r++)
-					for (uint32_t i = 0; i < n; i++)
-						cs.hIdx[(size_t)r * n + i] = i;
-			std::copy (cur.begin (), cur.end (), cs.hIdx.begin () + (size_t)len * n);
-		}
-	}
-	return 0;
-}
-
-/* The chunk's host control: its events [evBeg, evEnd) found and checked, then stepped by
- * one of stepChunkFront, stepChunkParallel and stepChunkSerial into a cleared staging set.
- * Leaves ck.len, ck.delta, ck.dfront, and ck.evBeg behind the events applied. */
-static int hostControl (tbf_engine* e, ChunkStaging& cs, Chunk& ck, uint32_t n, const tbf_event* ev, uint32_t nev)
-{
-	const uint32_t b0 = ck.b0, want = ck.want, evi = ck.evBeg;
-	cs.dCtl.clear (), cs.hRec.clear (), cs.hMsg.clear (), cs.hGain.clear (), cs.hWh.clear ();
-	cs.hCtlInst.clear (), cs.hDInst.clear (), cs.hFull.clear ();
-	e->dSeg.clear (), e->dProg.clear ();
-	e->stepped.assign (n, 0), e->dhas.assign (n, 0);
-	cs.hIdx.resize ((size_t)want * n);
-	e->curIdx.resize (n);
-	for (uint32_t i = 0; i < n; i++)
-		e->curIdx[i] = i;
-	const auto hc0 = std::chrono::steady_clock::now ();
-	/* the chunk's events (sorted by block: a binary search), checked in parallel (a serial
-	 * pass cost ~0.5 ms at 524k events) */
-	const uint32_t evEnd = ck.evEnd = (uint32_t)(
-	    std::partition_point (ev + evi, ev + nev, [&] (const tbf_event& x) { return x.block < b0 + want; }) - ev);
-	/* a chunk of note, drawbar and switch events only (frontParam) on clean instances: the
-	 * device front end */
-	bool       progEv = false, badEv = false, front = false;
-	const bool frontCand = e->devCtl && ck.dpipe && e->frontOn && evEnd - evi >= e->frontMin && frontCleanAll (e);
-	const auto sc0       = std::chrono::steady_clock::now ();
-	scanChunk (n, b0, ev, evi, evEnd, frontCand ? e->fclean.data () : nullptr, progEv, badEv, front, e->scan);
-	if (e->dbgPhases)
-		fprintf (stderr, "chunk %llu: clean %.3f ms, scan %.3f ms (%u events)\n", (unsigned long long)e->chunkSeq,
-		         std::chrono::duration<double, std::milli> (sc0 - hc0).count (),
-		         std::chrono::duration<double, std::milli> (std::chrono::steady_clock::now () - sc0).count (), evEnd - evi);
-	if (badEv)
-		return fail (-22, "event for a bad instance");
-	int rc;
-	if (frontCand && front && !progEv) {
-		if ((rc = stepChunkFront (e, cs, ck, n)))
-			return rc;
-		ck.dfront = true;
-		e->frontChunks[0]++;
-		if (e->dbgPhases)
-			fprintf (stderr, "chunk %llu: device front end, %u note events\n", (unsigned long long)e->chunkSeq,
-			         cs.hFevOff[n]);
-	} else {
-		if (evEnd > evi)
-			e->frontChunks[1]++;
-		/* device control with many instances to step (active now, or touched by this chunk's
-		 * events): the chunk's host control on worker threads (serial when a programme change
-		 * is among the events) */
-		if (e->devCtl && !progEv && e->parCtl && e->actList.size () + (evEnd - evi) >= 1024)
-			rc = stepChunkParallel (e, cs, ck, n, ev);
-		else
-			rc = stepChunkSerial (e, cs, ck, n, ev);
-		if (rc)
-			return rc;
-	}
-	e->hostCtlNs += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds> (
-	                    std::chrono::steady_clock::now () - hc0)
-	                    .count ();
-	e->hostCtlBlocks += ck.len;
-	if (ck.delta && ck.len > TBF_CHUNK)
-		return fail (-5, "internal: a chunk with control deltas longer than 64 blocks");
-	return 0;
-}
-
 /* a delta chunk's uploads: control deltas, delta programs, index table, whirl sets (P.whSets) */
 static int uploadDeltas (tbf_engine* e, ChunkStaging& cs, Chunk& ck, tbf_launch& P, hipStream_t s)
 {
@@ -2575,13 +1569,9 @@ static int controlKernels (tbf_engine* e, ChunkStaging& cs, Chunk& ck, tbf_launc
 			if ((rc = tbf_launch_front (&P, us)))
 				return fail (rc, std::string ("k_front launch failed: ") + hipGetErrorString (hipGetLastError ()));
 		}
-		if (!dfront && e->dSeg.empty ())
-			HIPCHK (hipMemcpyAsync (cs.drec.p, cs.hRec.data (), cs.hRec.size () * sizeof (tbf_tgc_rec),
-			                        hipMemcpyHostToDevice, us));
-		for (const auto& g : e->dSeg)
-			if (!dfront && g.second)
-				HIPCHK (hipMemcpyAsync (cs.drec.p + g.first, cs.hRec.data () + g.first,
-				                        g.second * sizeof (tbf_tgc_rec), hipMemcpyHostToDevice, us));
+		for (const auto& g : e->dSeg) /* the filled segments of hRec (none in a front-end chunk) */
+			HIPCHK (hipMemcpyAsync (cs.drec.p + g.first, cs.hRec.data () + g.first,
+			                        g.second * sizeof (tbf_tgc_rec), hipMemcpyHostToDevice, us));
 		if (!dfront && !cs.hMsg.empty ())
 			HIPCHK (hipMemcpyAsync (cs.dmsg.p, cs.hMsg.data (), cs.hMsg.size () * sizeof (uint16_t),
 			                        hipMemcpyHostToDevice, us));
@@ -3248,29 +2238,6 @@ int tbf_debug_step (tbf_engine* e, uint32_t i, float* out, uint32_t cap)
 		o[3] = p.sg; o[4] = p.pg; o[5] = p.vg; o[6] = p.nsg; o[7] = p.npg; o[8] = p.nvg;
 	}
 	return (int)in.prog.size ();
-}
-
-int tbf_debug_render_program (tbf_engine* e, uint32_t i, float* out, uint32_t cap)
-{
-	if (!e || i >= e->inst.size ())
-		return fail (-22, "bad instance");
-	if (e->devCtl)
-		return fail (-95, "host programs: the per-wheel control runs on the device (TBF_HOST_CONTROL=1 for the host path)");
-	const size_t n = e->inst.size ();
-	if (e->hCtl.size () < n) { /* a host-only engine never sized the pool */
-		e->hCtl.resize (n);
-		e->hProg.resize (PERSIST (n));
-	}
-	bool pc;
-	(void)stepControl (e, e->stg[0], i, pc); /* exactly the per-block step renderImpl makes (host control: set 0) */
-	const std::vector<tbf_prog_entry>& prog = e->inst[i].prog;
-	for (uint32_t q = 0; q < prog.size () && q < cap; q++) {
-		const tbf_prog_entry& p = prog[q];
-		float*                o = out + 9 * q;
-		o[0] = p.wheel; o[1] = p.env; o[2] = p.row;
-		o[3] = p.sg; o[4] = p.pg; o[5] = p.vg; o[6] = p.nsg; o[7] = p.npg; o[8] = p.nvg;
-	}
-	return (int)prog.size ();
 }
 
 int tbf_debug_exact (int32_t op, const double* in, double* out, uint32_t n)

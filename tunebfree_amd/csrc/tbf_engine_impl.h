@@ -1,10 +1,12 @@
 /*
  * tbf_engine_impl.h -- private engine state shared by the C-ABI translation units
- * (tbf_engine.cpp: construction, device setup, rendering; tbf_control.cpp: MIDI control
- * functions and programmes).  Not part of the ABI.
+ * (tbf_engine.cpp: construction, device setup, rendering; tbf_hostctl.cpp: a render chunk's
+ * host control; tbf_control.cpp: MIDI control functions and programmes; tbf_fork.cpp: clone,
+ * save, load).  Not part of the ABI.
  * The render path (tbf_engine.cpp renderBody) is a chunk loop over
  * phase functions (refreshControlPool, hostControl, uploadDeltas, controlKernels, issueChunk,
- * endDelta) of a file-local Chunk and the chunk's staged arrays, ChunkStaging below.
+ * endDelta) of a Chunk and the chunk's staged arrays, ChunkStaging below.  hostControl is
+ * tbf_hostctl.cpp's one entry for it; the others are tbf_engine.cpp's own.
  */
 #ifndef TBF_ENGINE_IMPL_H
 #define TBF_ENGINE_IMPL_H
@@ -14,6 +16,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <functional>
 #include <memory>
 #include <string>
 #include <utility>
@@ -138,7 +141,7 @@ struct PinnedVec {
 	T&     operator[] (size_t i) { return p[i]; }
 };
 
-/* a chunk's event scan (scanChunk, csrc/tbf_engine.cpp): instance ranges and event
+/* a chunk's event scan (scanChunk, csrc/tbf_hostctl.cpp): instance ranges and event
  * segments of the device front end's partition, with the per-segment counts */
 struct ChunkScan {
 	unsigned              T = 1, Te = 1; /* instance ranges, event segments */
@@ -230,6 +233,21 @@ struct ChunkStaging {
 	hipEvent_t                 upEv = nullptr; /* after the chunk's uploads and control kernels */
 };
 
+/* What renderBody decides for one chunk, handed to the phases of the render path beside
+ * the chunk's staged arrays, e->stg[rp] (ChunkStaging). */
+struct Chunk {
+	uint64_t    cix;          /* the chunk's sequence number (tbf_engine.chunkSeq) */
+	int         rp;           /* control region and staging set: cix & 1 under device control, else 0 */
+	uint32_t    bset;         /* stage-buffer set: cix & 1 */
+	uint32_t    b0, want;     /* first block in the call, blocks planned (chunkLength) ... */
+	uint32_t    len;          /* ... and stepped: fewer when the host control ends the chunk early */
+	uint32_t    evBeg, evEnd; /* its events (block < b0 + want); evBeg moves past those the host control applied */
+	bool        delta, dfront; /* it has control deltas; the device front end (k_front) stepped it */
+	bool        dpipe, piped; /* device control and pipelining: uploads on us = gs[0]; stages on the group streams */
+	hipStream_t us;           /* the stream of the chunk's uploads and control kernels ... */
+	bool        usWaited;     /* ... which has waited for the previous user of this region (usWait) */
+};
+
 } // namespace tbf
 
 using namespace tbf; /* private header: the engine's own translation units only */
@@ -240,6 +258,16 @@ using namespace tbf; /* private header: the engine's own translation units only 
 #define SLOT ((size_t)TBF_PROG_SLOT)
 #define PSLOTS ((size_t)TBF_PROG_PSLOTS)
 #define PERSIST(n) ((size_t)(n) * PSLOTS * SLOT)
+/* blocks per kernel launch chunk with control deltas: bounds the inter-stage buffers to
+ * n_inst x TBF_CHUNK x 128 floats each (134 MB at 4096 instances) */
+#ifndef TBF_CHUNK
+#define TBF_CHUNK 64
+#endif
+/* host-controlled path: delta program entries one chunk may add (a chunk ends early when
+ * they would not fit); the device-controlled path sizes its delta slots on demand */
+#define DPROG_CAP(n) ((size_t)(n) * SLOT * 2 + 4096)
+/* the most host worker threads (hostThreads; scanChunk sizes its per-range stack arrays by it) */
+#define TBF_MAX_HOST_THREADS 16u
 
 #define TBF_NSTAGES 6 /* k_tonegen, k_mixpre, k_rv_pre, k_rv_core, k_rv_post, k_whirl */
 
@@ -299,25 +327,22 @@ struct tbf_engine {
 	uint32_t                                frontMin = 64; /* events a chunk needs for the device front end (TBF_FRONT_MIN; 64: profiles/r05/s23) */
 	bool                                    parCtl = true; /* TBF_HOST_SERIAL=1 steps serially */
 	bool                                    dbgPhases = false; /* TBF_DEBUG_HOST_PHASES: the host phases' times on stderr */
-	/* threaded host control (stepChunkParallel): per worker, kept between chunks so the
-	 * buffers stay allocated; worker t writes its deltas straight into the staging at pool
-	 * position base_t = (first instance of its range) * blocks, and dSeg lists the filled
-	 * segments {base_t, count_t} that are uploaded (empty: the pool is [0, dCtl.size ())) */
+	/* A stepper's sink (csrc/tbf_hostctl.cpp): what one instance range's control steps emit
+	 * beside the records -- key messages, gain pairs, whirl sets, full entries, the instances
+	 * with a stepped delta (ctlInst) and with any (dInst), the delta count nd -- at offsets
+	 * within the sink until mergeSinks moves them into the staging.  One per worker, kept
+	 * between chunks so the buffers stay allocated; the serial stepper uses the first.  Worker t
+	 * writes its records straight into the staging at base_t = (first instance of its range) *
+	 * blocks, and dSeg lists the filled segments {base_t, count_t} of hRec to upload. */
 	struct alignas (128) ParStep { /* own cache lines: workers bump these per delta */
 		std::vector<uint16_t> msgs;
 		std::vector<float>    gains;
 		std::vector<tbf_wh_params> whs;
 		std::vector<uint32_t> act, ctlInst, evs, dInst, eoff, esort, efill;
-		/* a front-end chunk's events of the range, by instance: what the mirror pass reads */
-		struct FrontRec {
-			uint32_t blk;  /* block in the chunk */
-			int32_t  id;   /* key / parameter index */
-			float    v;    /* (float) value */
-			uint32_t flag; /* 1: parameter event, 2: value != 0 */
-		};
-		std::vector<FrontRec> erec;
+		std::vector<ChunkScan::Rec> erec; /* a front-end chunk's events of the range, by instance: what the mirror reads */
 		std::vector<tbf_seg_ctl> fulls;
 		uint32_t              nd = 0;
+		uint32_t              nMsg = 0, nGain = 0; /* msgs and gains in use (the vectors are their room) */
 		uint32_t              gainLocal = 0; /* device front end: the range's gain-pair floats */
 		bool                  fx = false;    /* ... and whether an effect setter stepped an entry */
 		int                   rc = 0;
@@ -426,6 +451,15 @@ struct tbf_engine {
 };
 
 namespace tbf {
+/* csrc/tbf_hostctl.cpp: one chunk's host control into its staging set (renderBody's phase);
+ * a scheduled event applied; tbf_set_param's setter.  (tbf_debug_render_program of the
+ * debug ABI is defined there too: it makes one stepControl call.) */
+int  hostControl (tbf_engine* e, ChunkStaging& cs, Chunk& ck, uint32_t n, const tbf_event* ev, uint32_t nev);
+int  applyEvent (tbf_engine* e, const tbf_event& ev);
+bool setParam (Instance& in, int32_t index, float value);
+/* csrc/tbf_engine.cpp: the host worker pool */
+unsigned hostThreads ();
+void     parallelFor (uint32_t n, const std::function<void (uint32_t)>& f);
 /* the calling thread's active list while renderImpl steps an instance range on a host
  * worker thread (nullptr: the engine's own list) */
 extern thread_local std::vector<uint32_t>* tlAct;
