@@ -193,6 +193,36 @@ int tbf_instances_save (tbf_engine* e, uint32_t n, const uint32_t* inst, void* b
  * everything is validated before anything is touched: a failed load changes nothing.
  * -16 while the tbf_synth_sound FIFO holds unserved frames. */
 int tbf_instances_load (tbf_engine* e, uint32_t n, const uint32_t* inst, const void* blob, uint64_t size);
+/* Removes the n distinct existing instances inst[0..n) and gives their memory back.  The
+ * survivors keep their relative order and are renumbered densely, like a vector after an
+ * erase: a survivor's new index is its old index minus the number of removed instances
+ * below it, and tbf_instance_count drops by n.  new_index may be NULL; otherwise it has room
+ * for the old instance count, and on success new_index[i] is the new index of old instance
+ * i, or UINT32_MAX if it was removed.
+ * A survivor's state is copied, never re-derived, the same contract as a clone: every later
+ * sample is bit-identical to what it would have rendered had the call never been made.  That
+ * covers its device DSP state, its whole host control state including what is pending and
+ * not yet rendered (queued key messages, dirty drawbars / routing, a pending rotary option,
+ * whirl parameter set or retune, the control rand() stream), its persistent program slot
+ * rotation and its row of the tbf_synth_sound FIFO (frames pending there are no -16 case:
+ * the rows are compacted like every other per-instance array).  Nothing of a removed
+ * instance remains, its pending events and its pending retune included.  Templates are
+ * untouched and template ids stay valid.
+ * -22 if an index does not exist or is listed twice, or if inst is NULL with n > 0; n == 0
+ * is a successful no-op (new_index: the identity); -12 on out of memory, -5 if the mover
+ * fails.  Everything is validated before anything is touched, and on any failure nothing
+ * changes: count, indices, device state and host state are as before.  Removing every
+ * instance is allowed: the engine then renders nothing (returns 0) and takes
+ * tbf_instances_add again; the table-shaping cfg keys stay refused (-16) once any instance
+ * has ever been added.
+ * On the device the survivors are compacted into fresh arrays sized for the new count by one
+ * k_state_move pass, and the old arrays are released only after it has finished, so the
+ * transient peak is the old state plus the new state (about 343 KB per survivor: 1.4 GB
+ * extra when a few of 4096 are removed).  The stage buffers are released with the call and
+ * come back, for the new count, at the next render.  Synchronisation as for a clone.  Works
+ * on every chain mode, on both control paths and front ends, on a host-only engine (device
+ * -1: the control plane alone) and before the first render. */
+int tbf_instances_remove (tbf_engine* e, uint32_t n, const uint32_t* inst, uint32_t* new_index);
 
 int tbf_note (tbf_engine* e, uint32_t inst, int32_t key, int32_t on);
 int tbf_set_param (tbf_engine* e, uint32_t inst, int32_t param, double value);
@@ -348,6 +378,14 @@ int tbf_debug_launches (const tbf_engine* e, uint64_t* counts, uint32_t cap);
 /* test hook: k_rv_pre launches since the engine was created that ran ahead, on the k_whirl
  * stream beside the previous chunk's k_rv_post (TBF_PRE_AHEAD=1; 0 otherwise) */
 int tbf_debug_pre_ahead (const tbf_engine* e, uint64_t* launches);
+/* test hook: device memory the engine holds now.  instance_bytes: the bytes allocated for
+ * the arrays whose size is a function of the instance count alone (st, wring, rslab, tgc,
+ * cst, the persistent slots of the program pool, the control pool ctl and its index table
+ * ctlIdx).  The delta part of the program pool is left out: under device control it grows
+ * with the deltas of a call, and it grows by a quarter more than asked for.  stage_bytes:
+ * the stage buffers mid0 / mid1 / mid2 / rvA / rvB.  Either pointer may be NULL; a host-only
+ * engine reports zeros. */
+int tbf_debug_device_bytes (const tbf_engine* e, uint64_t* instance_bytes, uint64_t* stage_bytes);
 /* the longest render chunk without control deltas, in blocks (64 .. 2048, default 512).
  * The stage buffers hold one chunk per instance (56 B per instance and sample at the
  * default stage groups: 15 GB at 4096 instances and 512 blocks, 60 GB at 2048) and

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/fork_bench.py -- tbf_instances_clone / _save / _load at the bench batch.
+"""tools/fork_bench.py -- tbf_instances_clone / _save / _load / _remove at the bench batch.
 
 Times, each as one synchronous call on an engine whose instances have rendered --blocks
 blocks of the bench registration:
@@ -7,6 +7,9 @@ blocks of the bench registration:
   clone 2048 from 2048    every instance forked once, 2048 -> 4096 instances
   save 4096 / load 4096   k_state_move into / out of the packed staging plus the one
                           device <-> host copy of the blob
+  remove 1 of 4096        tbf_instances_remove: the survivors compacted into fresh arrays
+  remove every other        (the bytes of a case are its survivors' records), the old arrays
+  remove 4095 of 4096       and the stage buffers released, the host arrays compacted
 in milliseconds and in GB/s of device state moved (the device record of DESIGN.md's "Forking
 and checkpointing": st + wring + rslab + tgc + the persistent program slots), beside a plain
 hipMemcpy device-to-device of the same byte count in the same process.  A clone call
@@ -124,6 +127,18 @@ def main():
     case(f"save {n}", timed(save), n)
     case(f"load {n}", timed(load), n)
     res["blob_bytes"] = int(blob.nbytes)
+
+    # tbf_instances_remove: the bytes a case moves are its survivors' records (compacted into
+    # fresh arrays); the batch is cloned back up to n between the cases
+    def remove(name, gone):
+        gone = np.ascontiguousarray(gone, dtype=np.uint32)
+        assert eng.n_instances == n
+        case(name, timed(lambda: eng.remove(gone)), n - len(gone))
+        assert eng.n_instances == n - len(gone)
+        eng.clone(np.arange(len(gone), dtype=np.uint32) % max(eng.n_instances, 1))
+    remove(f"remove 1 of {n}", [n // 2])
+    remove(f"remove every other of {n}", np.arange(0, n, 2))
+    remove(f"remove {n - 1} of {n}", np.arange(1, n))
     eng.close()
     out = Path(a.out)
     out.parent.mkdir(parents=True, exist_ok=True)

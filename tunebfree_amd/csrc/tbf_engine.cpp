@@ -64,10 +64,8 @@ int tbf::fail (int code, const std::string& msg)
 	} while (0)
 
 
-/* (program slots and chunk sizes -- SLOT, PSLOTS, PERSIST, TBF_CHUNK, DPROG_CAP: tbf_engine_impl.h) */
-/* control pool region (one per chunk parity on the device-controlled path; the host path
- * uses region 0): n persistent entries + up to one delta per instance and block */
-#define CTL_REGION(n) ((size_t)(n) * (TBF_CHUNK + 1))
+/* (program slots, chunk sizes and the control pool region -- SLOT, PSLOTS, PERSIST, TBF_CHUNK,
+ * DPROG_CAP, CTL_REGION: tbf_engine_impl.h) */
 
 /* ------------------------------------------------------------------ construction */
 
@@ -706,6 +704,7 @@ int tbf_instances_add (tbf_engine* e, uint32_t n, const uint32_t* tpl_ids, const
 	for (uint32_t q = 0; q < n; q++) {
 		if (tpl_ids[q] >= e->tpls.size ())
 			return fail (-22, "bad template id");
+		e->everAdded = true;
 		e->inst.emplace_back ();
 		Instance& in = e->inst.back ();
 		in.tpl       = tpl_ids[q];
@@ -849,7 +848,7 @@ int tbf_config_set (tbf_engine* e, const char* key, const char* value)
 		return fail (-22, std::string ("bad value for ") + key + ": " + value);
 	if (rc == 0)
 		return 1; /* not a key of the hot path: ignored, as the reference ignores it */
-	if ((scope & CFG_SHARED) && !e->inst.empty ())
+	if ((scope & CFG_SHARED) && (e->everAdded || !e->inst.empty ()))
 		return fail (-16, std::string (key) + " shapes the engine-wide tables: set it before tbf_instances_add");
 	const Config old = e->conf;
 	e->conf          = c;
@@ -907,7 +906,7 @@ int tbf_config_parse (tbf_engine* e, const char* text)
 		scope |= sc;
 		applied++;
 	}
-	if ((scope & CFG_SHARED) && !e->inst.empty ())
+	if ((scope & CFG_SHARED) && (e->everAdded || !e->inst.empty ()))
 		return fail (-16, sharedKey + " shapes the engine-wide tables: set it before tbf_instances_add (nothing applied)");
 	const Config old = e->conf;
 	e->conf          = c;
@@ -1114,7 +1113,7 @@ static int ensureDevice (tbf_engine* e)
 		e->ctlVer++; /* both regions' persistent entries need the new pool */
 		/* program pool: the existing instances' persistent programs move along (the device
 		 * control path keeps them only there); new instances start with empty ones */
-		if (int rc = growProg (e, PERSIST (n) + (e->devCtl ? PERSIST (n) : DPROG_CAP (n)), old))
+		if (int rc = growProg (e, PROG_POOL (n, e->devCtl), old))
 			return rc;
 		HIPCHK (hipMemset (e->prog.p + PERSIST (old), 0, (PERSIST (n) - PERSIST (old)) * sizeof (tbf_prog_entry)));
 		if (e->devCtl) {
@@ -1973,7 +1972,7 @@ int tbf_render (tbf_engine* e, uint32_t nblocks, float* outL, float* outR, uint6
 	if (e->outL.ensure ((size_t)n * per) || e->outR.ensure ((size_t)n * per))
 		return fail (-12, "out of device memory (outputs)");
 	int rc = renderImpl (e, nblocks, e->outL.p, e->outR.p, per, e->stream);
-	if (rc)
+	if (rc || n == 0) /* no instance (all removed): nothing rendered, no row to copy */
 		return rc;
 	HIPCHK (hipMemcpy2DAsync (outL, stride * 4, e->outL.p, per * 4, per * 4, n, hipMemcpyDeviceToHost, e->stream));
 	HIPCHK (hipMemcpy2DAsync (outR, stride * 4, e->outR.p, per * 4, per * 4, n, hipMemcpyDeviceToHost, e->stream));

@@ -2,7 +2,7 @@
  * tbf_engine_impl.h -- private engine state shared by the C-ABI translation units
  * (tbf_engine.cpp: construction, device setup, rendering; tbf_hostctl.cpp: a render chunk's
  * host control; tbf_control.cpp: MIDI control functions and programmes; tbf_fork.cpp: clone,
- * save, load).  Not part of the ABI.
+ * save, load, remove).  Not part of the ABI.
  * The render path (tbf_engine.cpp renderBody) is a chunk loop over
  * phase functions (refreshControlPool, hostControl, uploadDeltas, controlKernels, issueChunk,
  * endDelta) of a Chunk and the chunk's staged arrays, ChunkStaging below.  hostControl is
@@ -266,6 +266,13 @@ using namespace tbf; /* private header: the engine's own translation units only 
 /* host-controlled path: delta program entries one chunk may add (a chunk ends early when
  * they would not fit); the device-controlled path sizes its delta slots on demand */
 #define DPROG_CAP(n) ((size_t)(n) * SLOT * 2 + 4096)
+/* control pool region (one per chunk parity on the device-controlled path; the host path
+ * uses region 0): n persistent entries + up to one delta per instance and block */
+#define CTL_REGION(n) ((size_t)(n) * (TBF_CHUNK + 1))
+/* entries of the device program pool as ensureDevice sizes it for n instances (growProg
+ * allocates a quarter more): the persistent slots, then the delta slots -- under device
+ * control they grow on demand with a delta chunk */
+#define PROG_POOL(n, devCtl) (PERSIST (n) + ((devCtl) ? PERSIST (n) : DPROG_CAP (n)))
 /* the most host worker threads (hostThreads; scanChunk sizes its per-range stack arrays by it) */
 #define TBF_MAX_HOST_THREADS 16u
 
@@ -285,6 +292,8 @@ struct tbf_engine {
 	std::vector<uint64_t>                   tplFp;
 	uint64_t                                engFp = 0;
 	std::vector<Instance>                   inst;
+	bool                                    everAdded = false; /* an instance was added once: the table-shaping cfg keys stay
+	                                                            * refused (-16) even after tbf_instances_remove took the last one */
 	std::vector<uint32_t>                   retuned; /* tbf_instance_retune: device state to reset */
 	uint64_t                                hostCtlNs = 0, hostCtlBlocks = 0; /* tbf_debug_host_time */
 	/* reverb ring layout (identical for all instances: A..F are fixed) */

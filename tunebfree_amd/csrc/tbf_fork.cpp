@@ -17,6 +17,8 @@
  * records; the header carries a checksum of everything behind it, and every offset and
  * length is re-derived and compared on load, so a blob that was cut or altered is refused
  * before anything is touched.
+ * tbf_instances_remove (at the end) moves the same parts of every survivor, with the same
+ * mover and the same rebase, into arrays sized for the new count.
  */
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -409,10 +411,13 @@ uint64_t deviceRecordBytes (const tbf_engine* e)
 	return align16 (o);
 }
 
-/* One k_state_move over the pairs (src[k] -> dst[k]).  mode 0: array to array (clone);
- * 1: array to record k of `stage` (save); 2: record k of `stage` to array (load).  For 1 / 2
- * the record side's index list is 0 .. np - 1.  On the engine's stream; the caller waits. */
-int moveState (tbf_engine* e, int mode, const uint32_t* src, const uint32_t* dst, uint32_t np, unsigned char* stage)
+/* One k_state_move over the pairs (src[k] -> dst[k]).  mode 0: array to array (clone; with
+ * `into`, the segments of other arrays in deviceSegments' order, from the engine's arrays into
+ * those: a removal's compaction); 1: array to record k of `stage` (save); 2: record k of
+ * `stage` to array (load).  For 1 / 2 the record side's index list is 0 .. np - 1.  On the
+ * engine's stream; the caller waits. */
+int moveState (tbf_engine* e, int mode, const uint32_t* src, const uint32_t* dst, uint32_t np, unsigned char* stage,
+               const DevSeg* into = nullptr)
 {
 	if (np == 0)
 		return 0;
@@ -429,7 +434,7 @@ int moveState (tbf_engine* e, int mode, const uint32_t* src, const uint32_t* dst
 		M.bytes         = s[g].bytes;
 		M.src           = mode == 2 ? stage + o : s[g].base;
 		M.srcStride     = mode == 2 ? rec : s[g].bytes;
-		M.dst           = mode == 1 ? stage + o : s[g].base;
+		M.dst           = mode == 1 ? stage + o : (mode == 0 && into) ? into[g].base : s[g].base;
 		M.dstStride     = mode == 1 ? rec : s[g].bytes;
 		/* the width, per segment: 16 B where both bases, both strides and the length allow */
 		M.wide = (M.bytes % 16 == 0 && M.srcStride % 16 == 0 && M.dstStride % 16 == 0 && (uintptr_t)M.src % 16 == 0 &&
@@ -832,6 +837,190 @@ int tbf_instances_load (tbf_engine* e, uint32_t n, const uint32_t* inst, const v
 		installSlot (e, inst[k], recs[k]);
 	}
 	afterInstall (e);
+	return 0;
+}
+
+/* Removal is an order-preserving compaction: survivor keep[j] (old index) becomes instance j.
+ * On the device the survivors move into fresh arrays sized for the new count, in one
+ * k_state_move pass (source and destination are different allocations, so no pair reads a
+ * slot another pair writes, which compacting in place could not promise); the new arrays
+ * replace the old ones only after the move has finished, so a failure leaves the engine as
+ * it was.  Transient peak memory: the old state plus the new state (about 343 KB per
+ * survivor; 1.4 GB extra when a few of 4096 instances go).  The host arrays are compacted
+ * in place, ascending (j <= keep[j]: a slot is read before it is overwritten), and the
+ * position-dependent fields rebased as captureSlot / installSlot do. */
+int tbf_instances_remove (tbf_engine* e, uint32_t n, const uint32_t* inst, uint32_t* new_index)
+{
+	if (int rc = checkInstances (e, n, inst, true))
+		return rc;
+	const uint32_t        old = (uint32_t)e->inst.size ();
+	const uint32_t        m   = old - n;
+	std::vector<uint32_t> map, keep;
+	try {
+		map.assign (old, 0);
+		for (uint32_t k = 0; k < n; k++)
+			map[inst[k]] = UINT32_MAX;
+		keep.reserve (m);
+		for (uint32_t i = 0; i < old; i++)
+			if (map[i] != UINT32_MAX) {
+				map[i] = (uint32_t)keep.size ();
+				keep.push_back (i);
+			}
+	} catch (const std::bad_alloc&) {
+		return fail (-12, "out of memory (index map)");
+	}
+	if (n == 0) {
+		if (new_index)
+			std::copy (map.begin (), map.end (), new_index);
+		return 0;
+	}
+	const bool dev = e->cfg.device >= 0;
+	/* the FIFO rows of the survivors (one the FIFO has not seen yet: zeros, as a clone's) */
+	std::vector<float> fL, fR;
+	if (e->fifoN > 0 && m > 0) {
+		try {
+			const size_t len = e->fifoLen;
+			fL.assign ((size_t)m * len, 0.f);
+			fR.assign ((size_t)m * len, 0.f);
+			for (uint32_t j = 0; j < m && keep[j] < e->fifoN; j++) {
+				std::copy_n (e->fifoL.begin () + (long)(keep[j] * len), len, fL.begin () + (long)(j * len));
+				std::copy_n (e->fifoR.begin () + (long)(keep[j] * len), len, fR.begin () + (long)(j * len));
+			}
+		} catch (const std::bad_alloc&) {
+			return fail (-12, "out of memory (FIFO rows)");
+		}
+	}
+	if (dev) {
+		/* every launch so far done, and every instance on the device (one added since the last
+		 * render then has its s0 there, which the move carries) */
+		if (int rc = engineDrain (e))
+			return rc;
+		if (int rc = engineDevice (e))
+			return rc;
+		DevBuf<tbf_inst_state> nst;
+		DevBuf<float>          nwr;
+		DevBuf<double>         nsl;
+		DevBuf<tbf_tgc_state>  ntg;
+		DevBuf<tbf_prog_entry> npr;
+		DevBuf<tbf_inst_const> ncs;
+		DevBuf<tbf_seg_ctl>    nct;
+		DevBuf<uint32_t>       nix;
+		if (m) {
+			/* the sizes ensureDevice gives an engine that gets m instances at once */
+			const size_t pool = PROG_POOL (m, e->devCtl);
+			if (nst.ensure (m) || nwr.ensure ((size_t)m * 4 * e->wringLen) || nsl.ensure ((size_t)m * e->slabLen) ||
+			    (e->devCtl && ntg.ensure (m)) || npr.ensure (pool + pool / 4) || ncs.ensure (m) ||
+			    nct.ensure (2 * CTL_REGION (m)) || nix.ensure (2 * (size_t)m * TBF_CHUNK)) {
+				(void)hipGetLastError ();
+				return fail (-12, "out of device memory (compacted instances)");
+			}
+			DevSeg   into[TBF_MOVE_SEGS];
+			uint32_t g = 0;
+			into[g++]  = {(unsigned char*)nst.p, sizeof (tbf_inst_state)};
+			into[g++]  = {(unsigned char*)nwr.p, (uint64_t)4 * e->wringLen * sizeof (float)};
+			into[g++]  = {(unsigned char*)nsl.p, (uint64_t)e->slabLen * sizeof (double)};
+			if (e->devCtl)
+				into[g++] = {(unsigned char*)ntg.p, sizeof (tbf_tgc_state)};
+			into[g++] = {(unsigned char*)npr.p, PSLOTS * SLOT * sizeof (tbf_prog_entry)};
+			std::vector<uint32_t>       dst (m);
+			std::vector<tbf_inst_const> k (m);
+			for (uint32_t j = 0; j < m; j++) {
+				dst[j] = j;
+				k[j]   = e->inst[keep[j]].k;
+			}
+			if (int rc = moveState (e, 0, keep.data (), dst.data (), m, nullptr, into))
+				return rc;
+			HIPCHK (hipMemcpyAsync (ncs.p, k.data (), (size_t)m * sizeof (tbf_inst_const), hipMemcpyHostToDevice, e->stream));
+			if (hipStreamSynchronize (e->stream) != hipSuccess)
+				return fail (-5, "k_state_move failed");
+		}
+		/* only now: the new arrays in, the old ones (and the stage buffers, which the next render
+		 * allocates for the new count) released */
+		e->st    = std::move (nst);
+		e->wring = std::move (nwr);
+		e->rslab = std::move (nsl);
+		e->tgc   = std::move (ntg);
+		e->prog  = std::move (npr);
+		e->cst   = std::move (ncs);
+		e->ctl   = std::move (nct);
+		e->ctlIdx = std::move (nix);
+		e->mid0.release (), e->mid1.release (), e->mid2.release (), e->rvA.release (), e->rvB.release ();
+		e->stageBlocks = e->stageN = 0;
+		e->devInst     = m;
+	}
+	/* the host side, slot by slot; each array as far as it reaches (a host-only engine sizes
+	 * its pool on demand, lastEmit / lastProg exist under device control only) */
+	auto reach = [&] (size_t have) { return (size_t)(std::lower_bound (keep.begin (), keep.end (), (uint32_t)std::min<size_t> (have, old)) - keep.begin ()); };
+	const size_t nCtl = e->hCtl.size (), nProg = e->hProg.size () / PERSIST (1), nSlot = e->pslot.size (),
+	             nEmit = e->lastEmit.size (), nLast = e->lastProg.size ();
+	for (uint32_t j = 0; j < m; j++) {
+		const uint32_t i = keep[j];
+		if (i == j)
+			continue;
+		const uint32_t shift = progBase (j) - progBase (i); /* modulo 2^32, as the offsets are */
+		e->inst[j]           = std::move (e->inst[i]);
+		if (i < nCtl) {
+			e->hCtl[j] = e->hCtl[i];
+			e->hCtl[j].prog_off += shift;
+		}
+		if (i < nProg)
+			std::copy_n (e->hProg.begin () + (long)PERSIST (i), PERSIST (1), e->hProg.begin () + (long)PERSIST (j));
+		if (i < nSlot)
+			e->pslot[j] = e->pslot[i];
+		if (i < nEmit) {
+			e->lastEmit[j] = e->lastEmit[i];
+			e->lastEmit[j].prog_off += shift;
+		}
+		if (i < nLast)
+			e->lastProg[j] = e->lastProg[i] + shift;
+	}
+	e->inst.erase (e->inst.begin () + m, e->inst.end ());
+	e->hCtl.resize (reach (nCtl));
+	e->hProg.resize (PERSIST (reach (nProg)));
+	e->pslot.resize (reach (nSlot));
+	e->lastEmit.resize (reach (nEmit));
+	e->lastProg.resize (reach (nLast));
+	/* pending retunes: the removed instances' go, the others follow their instances */
+	size_t r = 0;
+	for (uint32_t i : e->retuned)
+		if (map[i] != UINT32_MAX)
+			e->retuned[r++] = map[i];
+	e->retuned.resize (r);
+	if (e->fifoN > 0) {
+		e->fifoL.swap (fL);
+		e->fifoR.swap (fR);
+		e->fifoN = m;
+	}
+	/* per-chunk scratch and lists indexed by instance: the next chunk fills them again (every
+	 * instance is stepped then: inAct all set, so markActive adds nothing before the rebuild) */
+	e->actList.clear ();
+	e->inAct.assign (m, 1);
+	e->hIdent.resize (std::min<size_t> (e->hIdent.size (), m)); /* 0 .. m - 1, as dident still holds */
+	e->fclean.resize (std::min<size_t> (e->fclean.size (), m));
+	e->stepped.clear (), e->dhas.clear (), e->dseen.clear (), e->chg.clear (), e->curIdx.clear ();
+	afterInstall (e);
+	if (new_index)
+		std::copy (map.begin (), map.end (), new_index);
+	return 0;
+}
+
+int tbf_debug_device_bytes (const tbf_engine* e, uint64_t* instance_bytes, uint64_t* stage_bytes)
+{
+	if (!e)
+		return fail (-22, "null argument");
+	uint64_t ib = 0, sb = 0;
+	if (e->cfg.device >= 0) {
+		ib = e->st.cap * sizeof (tbf_inst_state) + e->wring.cap * sizeof (float) + e->rslab.cap * sizeof (double) +
+		     e->tgc.cap * sizeof (tbf_tgc_state) + e->cst.cap * sizeof (tbf_inst_const) + e->ctl.cap * sizeof (tbf_seg_ctl) +
+		     e->ctlIdx.cap * sizeof (uint32_t);
+		if (e->prog.p) /* the persistent slots of the pool (its delta part grows with a call's deltas) */
+			ib += std::min<uint64_t> (PERSIST (e->devInst), e->prog.cap) * sizeof (tbf_prog_entry);
+		sb = (e->mid0.cap + e->mid1.cap + e->mid2.cap) * sizeof (float) + (e->rvA.cap + e->rvB.cap) * sizeof (double);
+	}
+	if (instance_bytes)
+		*instance_bytes = ib;
+	if (stage_bytes)
+		*stage_bytes = sb;
 	return 0;
 }
 

@@ -47,6 +47,7 @@ SIGNATURES = {
     "tbf_instances_clone": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u32p]),
     "tbf_instances_save": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "tbf_instances_load": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, C.c_void_p, C.c_uint64]),
+    "tbf_instances_remove": (C.c_int, [C.c_void_p, C.c_uint32, _u32p, _u32p]),
     "tbf_note": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int32, C.c_int32]),
     "tbf_set_param": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int32, C.c_double]),
     "tbf_render": (C.c_int, [C.c_void_p, C.c_uint32, _fp, _fp, C.c_uint64]),
@@ -258,6 +259,27 @@ class Engine:
         a = np.ascontiguousarray(np.atleast_1d(inst), dtype=np.uint32)
         b = np.ascontiguousarray(blob, dtype=np.uint8)
         _check(self._lib.tbf_instances_load(self._h, len(a), a.ctypes.data_as(_u32p), b.ctypes.data, b.nbytes))
+
+    def remove(self, inst):
+        """tbf_instances_remove: remove the instances inst (an index or a list of distinct
+        indices); the survivors keep their order and are renumbered densely.  Returns the map
+        old index -> new index as an int64 array, -1 for a removed instance."""
+        a = np.ascontiguousarray(np.atleast_1d(inst), dtype=np.uint32)
+        old = self.n_instances
+        m = np.zeros(old + 1, np.uint32)
+        _check(self._lib.tbf_instances_remove(self._h, len(a), a.ctypes.data_as(_u32p), m.ctypes.data_as(_u32p)))
+        out = m[:old].astype(np.int64)
+        out[out == 0xFFFFFFFF] = -1
+        return out
+
+    def device_bytes(self):
+        """tbf_debug_device_bytes: (instance_bytes, stage_bytes) of device memory held now --
+        the arrays sized by the instance count alone, and the stage buffers."""
+        f = self._lib.tbf_debug_device_bytes
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        ib, sb = C.c_uint64(), C.c_uint64()
+        _check(f(self._h, C.byref(ib), C.byref(sb)))
+        return ib.value, sb.value
 
     @property
     def n_instances(self):
