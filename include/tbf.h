@@ -75,7 +75,11 @@ typedef struct tbf_engine tbf_engine;
                                    * fallbacks; slow) */
 
 typedef struct tbf_engine_config {
-	double   sample_rate; /* Hz, 8000 .. 192000 */
+	double   sample_rate; /* Hz, 8000 .. 192000; a chain that runs the whirl (TBF_CHAIN_FULL, TBF_CHAIN_FX)
+	                       * needs every rotor write-ahead >= 64 samples: from about 35.5 kHz with the
+	                       * default geometry (44100 and up are safe), higher with the microphone nearer
+	                       * than the default (whirl.mic.distance under 27 cm at 48 kHz); below that
+	                       * tbf_engine_create / tbf_config_set / tbf_config_parse return -22 */
 	int32_t  device;      /* HIP device ordinal */
 	uint32_t chain_mode;  /* TBF_CHAIN_* */
 	uint32_t debug_flags; /* TBF_DEBUG_*, 0 in production */
@@ -355,6 +359,10 @@ int tbf_debug_pool_check (uint32_t jobs);
 /* the cfg-derived HBM layout: the compact whirl ring window (512 / 1024 / 2048 samples
  * per ring, from the geometry's largest write-ahead) and the reverb slab length */
 int tbf_debug_layout (const tbf_engine* e, uint32_t* wring_len, float* max_ahead, uint32_t* slab_len);
+/* the geometry's smallest whirl write-ahead in samples (the nearest a motion's ring add
+ * lands to its own sample) and the bound under which a chain that runs the whirl is
+ * refused (one 64-sample sub-block plus rounding slack) */
+int tbf_debug_whirl_lead (const tbf_engine* e, float* min_ahead, float* bound);
 /* blocks per render chunk: with control deltas (64) and without (TBF_STEADY_CHUNK, up to 2048) */
 int tbf_debug_chunks (const tbf_engine* e, uint32_t* delta_blocks, uint32_t* steady_blocks);
 /* chunks with events since the engine was created, by the front end that stepped them:

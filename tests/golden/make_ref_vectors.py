@@ -44,17 +44,35 @@ CASES = [
 ]
 
 
-# the vectors are stored in PARTS archives (case i in part i mod PARTS, the case table in
-# part 0) so that every committed file stays under 1 MiB
+# the rates the other cases leave out, in an archive of their own (ref_vectors_3.npz, with its
+# own case table): the full chain at the lowest rate a chain with the whirl is accepted at
+# (35500 Hz: smallest whirl write-ahead 64.1 samples; tests/test_gpu_rates.py finds that rate
+# from the engine), at 88.2 kHz and at the top rate, and the tone generator alone at the bottom
+# rate, which only the chains without the whirl take
+RATE_CASES = [
+    ("events35k5_19tet", 35500.0, "19TET", 5, 4301, ("events", 1), 40, 0),
+    ("sweep88_duodene", 88200.0, "duodene", 9, 4302, ("sweep", 3), 40, 0),
+    ("events192_p4", 192000.0, "p4", 11, 4303, ("events", 4), 40, 0),
+    ("tonegen8", 8000.0, None, 3, 4304, ("bench_tg", 2), 40, 1),
+]
+
+
+# the vectors are stored in PARTS archives (case i of CASES in part i mod PARTS, their case
+# table in part 0) so that every committed file stays under 1 MiB; RATE_CASES and their
+# table in part PARTS
 PARTS = 3
 
 
 def load_vectors():
-    """Every array of the committed ref_vectors_<i>.npz parts, merged into one dict."""
-    out = {}
-    for i in range(PARTS):
+    """Every array of the committed ref_vectors_<i>.npz parts, merged into one dict; `cases`
+    is the case tables joined."""
+    out, table = {}, []
+    for i in range(PARTS + 1):
         with np.load(HERE / f"ref_vectors_{i}.npz") as z:
-            out.update({k: z[k] for k in z.files})
+            out.update({k: z[k] for k in z.files if k != "cases"})
+            if "cases" in z.files:
+                table += json.loads(str(z["cases"]))
+    out["cases"] = np.array(json.dumps(table))
     return out
 
 
@@ -74,29 +92,41 @@ def scenario(kind, i):
     raise ValueError(kind)
 
 
-def main():
-    orc, ref = load_oracle(), load_ref()
-    if ref is None:
-        raise SystemExit("oracle/_ref/libtbfref.so not built (make -C oracle ref)")
-    tunings = json.loads((HERE / "tunings.json").read_text())
+def render(orc, ref, tunings, cases):
     out, table = {}, []
-    for (name, sr, tun, tseed, iseed, (kind, arg), nb, chain) in CASES:
+    for (name, sr, tun, tseed, iseed, (kind, arg), nb, chain) in cases:
         m = None if tun is None else np.array(tunings[tun], np.float64)
         tpl = Template(orc, sr=sr, mts128=m, seed=tseed)
         ch = Chain(ref, tpl, iseed, ref=True)
         ch.chain(chain)
         L, R, A, B, C = S.run(ch, scenario(kind, arg), nb, stages=True)
         for k, v in zip("LRABC", (L, R, A, B, C)):
+            assert np.isfinite(v).all() and float(np.abs(v).max()) > 1e-3, (name, k)
             out[f"{name}/{k}"] = v.astype(np.float32)
         table.append({"name": name, "sr": sr, "tuning": tun, "tpl_seed": tseed, "inst_seed": iseed,
                       "scenario": [kind, arg], "nblocks": nb, "chain": chain})
-    parts = [{k: v for k, v in out.items() if k.split("/")[0] in [t["name"] for t in table[i::PARTS]]}
-             for i in range(PARTS)]
-    parts[0]["cases"] = np.array(json.dumps(table))
-    for i, part in enumerate(parts):
-        np.savez_compressed(HERE / f"ref_vectors_{i}.npz", **part)
-    print(f"wrote ref_vectors_0..{PARTS - 1}.npz: {len(table)} cases")
+    return out, table
+
+
+def main(which):
+    """which: "all", or "rates" for ref_vectors_<PARTS>.npz alone"""
+    orc, ref = load_oracle(), load_ref()
+    if ref is None:
+        raise SystemExit("oracle/_ref/libtbfref.so not built (make -C oracle ref)")
+    tunings = json.loads((HERE / "tunings.json").read_text())
+    if which == "all":
+        out, table = render(orc, ref, tunings, CASES)
+        parts = [{k: v for k, v in out.items() if k.split("/")[0] in [t["name"] for t in table[i::PARTS]]}
+                 for i in range(PARTS)]
+        parts[0]["cases"] = np.array(json.dumps(table))
+        for i, part in enumerate(parts):
+            np.savez_compressed(HERE / f"ref_vectors_{i}.npz", **part)
+        print(f"wrote ref_vectors_0..{PARTS - 1}.npz: {len(table)} cases")
+    out, table = render(orc, ref, tunings, RATE_CASES)
+    out["cases"] = np.array(json.dumps(table))
+    np.savez_compressed(HERE / f"ref_vectors_{PARTS}.npz", **out)
+    print(f"wrote ref_vectors_{PARTS}.npz: {len(table)} cases")
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1] if len(sys.argv) > 1 else "all")

@@ -9,7 +9,8 @@ pins the oracle's and the product's template builders
 on machines without /root/reference.
 
 Cases: the 7 tunings of tests/golden/tunings.json x 48 / 96 kHz, template seed 300 + j
-(j = tuning index in sorted order), the frequency table of each from the oracle's
+(j = tuning index in sorted order), the osc.* cfg sets, and one template each at 8000 and
+192000 Hz; the frequency table of each from the oracle's
 getFrequencies restatement (pinned by the reference's osc.txt fixtures).
 """
 import hashlib
@@ -47,6 +48,11 @@ def cases():
     for k, cfgname in enumerate(("envelopes", "envelopes2", "osc_lists", "osc_models")):
         yield "12TET", 48000.0, 400 + k, None, cfgname
     yield "19TET", 96000.0, 410, np.array(tun["19TET"], np.float64), "osc_lists"
+    # the ends of the accepted sample-rate range: at 8000 Hz every wave is at its shortest
+    # (three blocks) and the click envelopes last 2-15 samples, at 192000 Hz the waves reach
+    # 16384 samples
+    yield "12TET", 8000.0, 420, None, None
+    yield "19TET", 192000.0, 421, np.array(tun["19TET"], np.float64), None
 
 
 def main():

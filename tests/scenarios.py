@@ -150,6 +150,10 @@ CFG_SETS = {
                  "whirl.horn.offset.x": 3, "whirl.horn.offset.z": -2},
     # a wider horn: the compact whirl ring window doubles to 1024 at 48 kHz (2048 at 96)
     "geometry_wide": {"whirl.horn.radius": 60, "whirl.drum.radius": 30, "whirl.mic.distance": 50},
+    # the microphone nearer than the default 42 cm: at 48 kHz the nearest whole centimetre whose
+    # smallest write-ahead (65.2 samples; 63.8 at 26 cm) still clears a 64-sample sub-block, i.e. the nearest
+    # the engine accepts on a chain with the whirl (test_gpu_rates.py scans for it)
+    "geometry_near": {"whirl.mic.distance": 27},
     "filters": {"whirl.drum.filter.type": 6, "whirl.drum.filter.hz": 700, "whirl.drum.filter.q": 1.2,
                 "whirl.drum.filter.gain": -20, "whirl.horn.filter.a.hz": 3800, "whirl.horn.filter.a.q": 1.8,
                 "whirl.horn.filter.b.type": 7, "whirl.horn.filter.b.hz": 350, "whirl.horn.filter.b.gain": -25,
@@ -240,6 +244,23 @@ def whirl_control_scenario(i, seed=None):
     c(58, "whirl.horn.brakepos", 1 + int(g.integers(0, 127)))
     c(58, "whirl.drum.brakepos", 1 + int(g.integers(0, 127)))
     return sorted(ev, key=lambda r: r[0])
+
+
+def fast_scens(n):
+    """Both rotors fast from the first block at the shortest ramp (time constant 0.01 s),
+    over 150 blocks (300 at 96 kHz): at the fast horn speed of 7.06 turns per second, 0.4 s
+    hold more than two horn turns, so every phase of the ring slots' spacing against each
+    other occurs, and every write-ahead between the geometry's smallest and largest; a
+    bypass in the middle."""
+    scens = []
+    for i in range(n):
+        e = [(0, k, a, b) for (k, a, b) in jazz1_params() if a not in (P_DRUM, P_HORN)]
+        e += [(0, "note", k, 1) for k in chord_for(i)]
+        e += [(0, "control", "whirl.horn.acceleration", 0), (0, "control", "whirl.drum.acceleration", 0)]
+        e += [(0, "param", P_HORN, 2), (0, "param", P_DRUM, 2)]
+        e += [(100 + i % 3, "param", P_WHIRL_BYPASS, 1), (102 + i % 3, "param", P_WHIRL_BYPASS, 0)]
+        scens.append(sorted(e, key=lambda r: r[0]))
+    return scens
 
 
 def random_drawbar_scenario(i, seed=None):

@@ -1225,21 +1225,23 @@ def _oracle_bank_worker(args):
     return out
 
 
-@pytest.mark.parametrize("sr", [48000.0, 96000.0])
+@pytest.mark.parametrize("sr", [48000.0, 96000.0, 8000.0, 192000.0])
 def test_gpu_device_banks_random_mts_no_flips(oracle, sr):
     """the device wave banks (k_tpl_wave: FP64 sin of the device library,
     rounded to float) against the oracle's (glibc sin) for 200 seeded random MTS tables
     per sample rate: the number of float samples that differ (a 1-ulp FP64 sin
-    difference flipping a float rounding) must be 0."""
+    difference flipping a float rounding) must be 0.  At the ends of the accepted range, 8000
+    and 192000 Hz (waves of up to 16384 samples), 16 tables each; 8000 Hz on the
+    tone-generator chain, the only kind of chain that rate is accepted on."""
     import multiprocessing as mp
     import os
     import tunebfree_amd as T
-    seeds = [7000 + int(sr) // 1000 * 1000 + k for k in range(200)]
+    seeds = [7000 + int(sr) // 1000 * 1000 + k for k in range(200 if sr in (48000.0, 96000.0) else 16)]
     workers = max(1, min(16, (os.cpu_count() or 1)))
     parts = [seeds[k::workers] for k in range(workers)]
     with mp.get_context("spawn").Pool(workers) as pool:
         ref = {sd: (b, l) for part in pool.map(_oracle_bank_worker, [(sr, p) for p in parts]) for sd, b, l in part}
-    eng = T.Engine(sample_rate=sr, device=0)
+    eng = T.Engine(sample_rate=sr, device=0, chain=1 if sr < 40000.0 else 0)
     ids = eng.templates(seeds, mts128=np.stack([_random_mts(sd) for sd in seeds]))
     flips, samples, worst = 0, 0, 0.0
     for tid, sd in zip(ids, seeds):
@@ -1259,7 +1261,7 @@ def test_gpu_device_banks_random_mts_no_flips(oracle, sr):
     assert flips == 0
 
 
-@pytest.mark.parametrize("sr", [48000.0, 96000.0])
+@pytest.mark.parametrize("sr", [48000.0, 96000.0, 8000.0, 192000.0])
 def test_gpu_device_templates_match_oracle_and_reference(oracle, sr):
     """§8(f) row 2: templates built on the device (tbf_templates_create: per-chunk
     jumps of the glibc rand() stream + the writeSamples sines) against
@@ -1269,7 +1271,9 @@ def test_gpu_device_templates_match_oracle_and_reference(oracle, sr):
         tests/golden/template_pins.json, generated by oracle/ref_tpl_pin.cpp): the 7
         tunings at this sample rate with their pinned seeds.
     A second batch (the 6 table tunings again with other seeds, plus three 12-TET
-    templates) is checked against the oracle."""
+    templates) is checked against the oracle.  8000 and 192000 Hz have one pin each; their
+    second batch is three of the table tunings and one 12-TET template (8000 Hz on the
+    tone-generator chain, the only kind of chain that rate is accepted on)."""
     import ctypes as C
     import hashlib
     import json
@@ -1281,7 +1285,8 @@ def test_gpu_device_templates_match_oracle_and_reference(oracle, sr):
     tunings = json.loads((gold / "tunings.json").read_text())
     allpins = json.loads((gold / "template_pins.json").read_text())
     pins = [p for p in allpins if p["sr"] == sr and not p.get("cfg")]
-    eng = T.Engine(sample_rate=sr, device=0)
+    assert len(pins) == (7 if sr in (48000.0, 96000.0) else 1)
+    eng = T.Engine(sample_rate=sr, device=0, chain=1 if sr < 40000.0 else 0)
     lib = T.load_library()
     lib.tbf_debug_tables.restype = C.c_int
     lib.tbf_debug_tables.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1305,17 +1310,23 @@ def test_gpu_device_templates_match_oracle_and_reference(oracle, sr):
     # built in its own call (tbf_templates_create takes all-or-none frequency tables)
     table_pins = [p for p in pins if tunings[p["tuning"]] is not None]
     t0 = time.perf_counter()
-    ids = eng.templates([p["seed"] for p in table_pins], mts128=np.stack([mts(p["tuning"]) for p in table_pins]))
+    ids = []
+    if table_pins:
+        ids = eng.templates([p["seed"] for p in table_pins], mts128=np.stack([mts(p["tuning"]) for p in table_pins]))
     t_dev = time.perf_counter() - t0
     tet = [p for p in pins if tunings[p["tuning"]] is None]
-    ids += eng.templates([p["seed"] for p in tet])
+    if tet:
+        ids += eng.templates([p["seed"] for p in tet])
     cases = [(tid, p["tuning"], p["seed"], p) for tid, p in zip(ids, table_pins + tet)]
     # batch 2: other seeds, checked against the oracle only
     names = [k for k in sorted(tunings) if tunings[k] is not None]
+    tets = (1, 2, 3)
+    if len(pins) < 7:
+        names, tets = names[::2], (1,)
     ids2 = eng.templates([500 + j for j in range(len(names))], mts128=np.stack([mts(nm) for nm in names]))
-    ids2 += eng.templates([1, 2, 3])
+    ids2 += eng.templates(list(tets))
     cases += [(tid, nm, 500 + j, None) for j, (tid, nm) in enumerate(zip(ids2, names))]
-    cases += [(tid, "12TET", s, None) for tid, s in zip(ids2[len(names):], (1, 2, 3))]
+    cases += [(tid, "12TET", s, None) for tid, s in zip(ids2[len(names):], tets)]
     for tid, nm, seed, pin in cases:
         got = tables(tid)
         o = Template(oracle, sr=sr, mts128=mts(nm), seed=seed)

@@ -172,20 +172,7 @@ def test_gpu_whirl_split_equals_k_whirl_on_breakers(breaker_render):
 
 
 # ---------------------------------------------------------------- 3. rotor at fast speed
-def _fast_scens(n):
-    """Both rotors fast from the first block at the shortest ramp (time constant 0.01 s),
-    over 150 blocks (300 at 96 kHz): at the fast horn speed of 7.06 turns per second, 0.4 s
-    hold more than two horn turns, so every phase of the ring slots' spacing against each other occurs; a bypass in the
-    middle."""
-    scens = []
-    for i in range(n):
-        e = [(0, k, a, b) for (k, a, b) in S.jazz1_params() if a not in (S.P_DRUM, S.P_HORN)]
-        e += [(0, "note", k, 1) for k in S.chord_for(i)]
-        e += [_c(0, "whirl.horn.acceleration", 0), _c(0, "whirl.drum.acceleration", 0)]
-        e += [(0, "param", S.P_HORN, 2), (0, "param", S.P_DRUM, 2)]
-        e += _bypass(100 + i % 3, 102 + i % 3)
-        scens.append(sorted(e, key=lambda r: r[0]))
-    return scens
+_fast_scens = S.fast_scens  # shared with test_gpu_rates.py and test_oracle_cpu.py
 
 
 @pytest.mark.parametrize("rate", [48000.0, 44100.0, 96000.0])

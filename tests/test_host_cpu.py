@@ -75,14 +75,17 @@ def _orc_bind_debug(lib):
     lib.orc_debug_program.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 
 
-@pytest.mark.parametrize("sr,seed,tuning", [(48000.0, 7, None), (44100.0, 3, "19TET"), (96000.0, 11, "p4")])
+@pytest.mark.parametrize("sr,seed,tuning", [(48000.0, 7, None), (44100.0, 3, "19TET"), (96000.0, 11, "p4"),
+                                            (8000.0, 5, None), (192000.0, 9, "19TET")])
 def test_host_template_matches_oracle(oracle, sr, seed, tuning):
+    """(8000 Hz on the tone-generator chain: a chain with the whirl is refused there; the
+    template builders are the same.)"""
     import json
     mts = None
     if tuning:
         mts = np.array(json.loads((ROOT / "tests" / "golden" / "tunings.json").read_text())[tuning], np.float64)
     ot = Template(oracle, sr=sr, mts128=mts, seed=seed)
-    eng = T.Engine(sample_rate=sr, device=-1)
+    eng = T.Engine(sample_rate=sr, device=-1, chain=1 if sr < 40000.0 else 0)
     tid = eng.template(mts128=mts, seed=seed)
     ob, ol = ot.bank()
     pb, pl = eng.template_bank(tid)
@@ -530,8 +533,8 @@ def test_host_templates_vs_reference_pins(tunings):
     """The product's host template builder (tbf_template_create on a host-only engine)
     gives the wave banks, lengths, envelopes, key-compression tables and play matrices of
     the reference's own src/tonegen.cpp builders (digests in tests/golden/template_pins.json,
-    see tests/golden/make_template_pins.py), bit for bit: 7 tunings x 48 / 96 kHz and the
-    osc.* cfg sets (envelope models, wheel EQ, harmonics, terminal / taper / crosstalk
+    see tests/golden/make_template_pins.py), bit for bit: 7 tunings x 48 / 96 kHz, one
+    template each at 8000 and 192000 Hz, and the osc.* cfg sets (envelope models, wheel EQ, harmonics, terminal / taper / crosstalk
     lists, crosstalk levels, contribution floor / minimum)."""
     import hashlib
     import json
@@ -543,7 +546,8 @@ def test_host_templates_vs_reference_pins(tunings):
     for p in pins:
         key = (p["sr"], p.get("cfg"))
         if key not in engines:
-            engines[key] = T.Engine(sample_rate=p["sr"], device=-1)
+            # (8000 Hz: on the tone-generator chain, a chain with the whirl is refused there)
+            engines[key] = T.Engine(sample_rate=p["sr"], device=-1, chain=1 if p["sr"] < 40000.0 else 0)
             if p.get("cfg"):
                 engines[key].config(S.CFG_SETS[p["cfg"]])
         eng = engines[key]
@@ -672,3 +676,127 @@ def test_host_pool_runs_every_task_once():
     assert out.returncode == 0, out.stderr[-2000:]
     assert out.stdout.strip().splitlines()[-1] == "0"
 
+
+
+# --------------------------------------------------------------------------- whirl write-ahead
+WHIRL_CHAINS = (0, T.engine.CHAIN_FX)              # run the whirl stage
+TAP_CHAINS = (1, 2, 3, T.engine.CHAIN_FX_TAP_PREAMP, T.engine.CHAIN_FX_TAP_REVERB)  # end before it
+LEAD_REFUSAL = r"-22.*whirl write-ahead [0-9.]+ samples is under the 64\.001"
+
+
+def _lead_model(sr, cfg=None):
+    """(smallest, largest, ring-sizing) write-ahead in samples: the formulas of the reference's
+    initValues / computeOffsets (src/whirl.cpp:43-134, 338-420) restated in float64 NumPy,
+    independent of the engine's table builder.  Motion p adds at spacing[p] + displacement
+    (angle): horn motions 0, 3, 4 read the forward table (distance + x offset), 1, 2, 5 the
+    backward one (distance - x offset); the drum's tables hold the same values."""
+    g = {"whirl.horn.radius": 19.2, "whirl.drum.radius": 22.0, "whirl.mic.distance": 42.0,
+         "whirl.horn.offset.x": 0.0, "whirl.horn.offset.z": 0.0}
+    g.update({k: v for k, v in (cfg or {}).items() if k in g})
+    f = sr / 100.0 / 340.0
+    hr, dr, md = g["whirl.horn.radius"] * f, g["whirl.drum.radius"] * f, g["whirl.mic.distance"] * f
+    mx, mz = g["whirl.horn.offset.x"] * f, g["whirl.horn.offset.z"] * f
+    v = 2.0 * np.pi * np.arange(16384) / 16384
+    hd = np.hypot(md - hr * np.cos(v), mz + hr * np.sin(v))
+    dd = np.hypot(md - dr * np.cos(v), dr * np.sin(v))
+    hs = np.array([12.0, 18.0, 53.0, 50.0, 106.0, 116.0]) * sr / 22100.0 + hr + 1.0
+    ds = np.array([36.0, 39.0, 79.0, 86.0, 123.0, 116.0]) * sr / 22100.0 + dr + 1.0
+    sx = np.array([mx, -mx, -mx, mx, mx, -mx])
+    lo = min((hs + sx + hd.min()).min(), (ds + dd.min()).min())
+    hi = max((hs + sx + hd.max()).max(), (ds + dd.max()).max())
+    # what sizes the ring: every motion taken with the larger of the two tables' maxima, an
+    # upper bound of hi that equals it unless the horn has an x offset
+    size = max((hs + abs(mx) + hd.max()).max(), (ds + dd.max()).max())
+    return float(lo), float(hi), float(size)
+
+
+@pytest.mark.parametrize("sr", [8000.0, 36000.0, 48000.0, 192000.0])
+@pytest.mark.parametrize("geo", ["default", "mic20", "geometry"])
+def test_layout_write_ahead_matches_formulas(sr, geo):
+    """layout()'s min_ahead / max_ahead against the NumPy restatement, to 1e-3 samples (a
+    float32 ulp at these magnitudes is at most 1.2e-4, 3e-5 below 512).  On the tone-generator
+    chain, which builds the same tables and has no write-ahead bound."""
+    cfg = {"default": None, "mic20": {"whirl.mic.distance": 20}, "geometry": S.CFG_SETS["geometry"]}[geo]
+    eng = T.Engine(sample_rate=sr, device=-1, chain=1)
+    if cfg:
+        eng.config(cfg)
+    lay = eng.layout()
+    lo, hi, size = _lead_model(sr, cfg)
+    assert abs(lay["min_ahead"] - lo) <= 1e-3, (lay, lo)
+    assert abs(lay["max_ahead"] - size) <= 1e-3 and hi <= size, (lay, hi, size)
+    assert (hi == size) == (geo != "geometry")
+    assert lay["min_ahead_bound"] == 64.0 + 2.0 ** -10
+    eng.close()
+
+
+def test_lead_model_reproduces_known_leads():
+    """the restatement itself, against values worked out by hand from the formulas: the
+    default geometry's smallest lead is sr (12 / 22100 + 0.42 / 340) + 1"""
+    for sr in (32000.0, 44100.0, 192000.0):
+        assert abs(_lead_model(sr)[0] - (sr * (12 / 22100.0 + 0.42 / 340.0) + 1.0)) < 1e-6
+    assert abs(_lead_model(44100.0)[0] - 79.4) < 0.05
+
+
+@pytest.mark.parametrize("sr", [8000.0, 22050.0, 32000.0])
+def test_short_write_ahead_refused_on_whirl_chains_only(sr):
+    """Below about 35.5 kHz the default geometry's nearest ring add lands inside its own
+    64-sample sub-block, which the whirl kernels read and clear first: chains that run the
+    whirl are refused when the engine is created, with the lead and the bound in the
+    message; chains that end before the whirl keep the whole 8000 .. 192000 Hz range."""
+    for chain in WHIRL_CHAINS:
+        with pytest.raises(T.TbfError, match=LEAD_REFUSAL):
+            T.Engine(sample_rate=sr, device=-1, chain=chain)
+    for chain in TAP_CHAINS:
+        eng = T.Engine(sample_rate=sr, device=-1, chain=chain)
+        assert eng.layout()["min_ahead"] < 64.0
+        eng.add_instances([eng.template(seed=3)], [5])
+        eng.close()
+
+
+def test_accepted_rates_and_geometries():
+    for chain in WHIRL_CHAINS:
+        eng = T.Engine(sample_rate=44100.0, device=-1, chain=chain)
+        assert 79.0 < eng.layout()["min_ahead"] < 80.0
+        eng.close()
+        for sr, name in ((48000.0, "geometry"), (96000.0, "geometry"), (48000.0, "geometry_wide"),
+                         (96000.0, "geometry_wide"), (192000.0, "geometry_wide"), (48000.0, "geometry_near")):
+            eng = T.Engine(sample_rate=sr, device=-1, chain=chain)
+            eng.config(S.CFG_SETS[name])
+            lay = eng.layout()
+            assert lay["min_ahead"] >= lay["min_ahead_bound"], (sr, name, lay)
+            eng.add_instances([eng.template(seed=3)], [5])
+            eng.close()
+    eng = T.Engine(sample_rate=192000.0, device=-1)
+    eng.config(S.CFG_SETS["geometry_wide"])
+    lay = eng.layout()
+    assert lay["wring_len"] == 2048 and 1968.0 < lay["max_ahead"] < 1970.0, lay
+    # past the reference's ring the existing check still refuses, and leaves the engine as it was
+    with pytest.raises(T.TbfError, match="-22.*exceeds the reference ring"):
+        eng.config_set("whirl.horn.radius", 80)
+    assert eng.layout() == lay
+    eng.close()
+
+
+@pytest.mark.parametrize("chain", WHIRL_CHAINS)
+def test_near_microphone_refused_by_config_and_engine_unchanged(chain):
+    """whirl.mic.distance = 20 at 48 kHz (lead 55.3): refused through tbf_config_set and
+    tbf_config_parse (nothing of the text applied), the tables as before, and the engine
+    still takes a template and an instance."""
+    eng = T.Engine(sample_rate=48000.0, device=-1, chain=chain)
+    lay = eng.layout()
+    with pytest.raises(T.TbfError, match=LEAD_REFUSAL):
+        eng.config_set("whirl.mic.distance", 20)
+    assert eng.layout() == lay
+    with pytest.raises(T.TbfError, match=LEAD_REFUSAL):
+        eng.config_parse("whirl.drum.radius = 18\nwhirl.mic.distance = 20\nreverb.mix = 0.3\n")
+    assert eng.layout() == lay
+    assert eng.config_set("whirl.mic.distance", 27) == 0  # the nearest whole centimetre accepted
+    assert 65.0 < eng.layout()["min_ahead"] < 65.4
+    assert eng.config_set("whirl.mic.distance", 42) == 0
+    assert eng.layout() == lay
+    eng.add_instances([eng.template(seed=3)], [5])
+    assert eng.n_instances == 1
+    eng.close()
+    tap = T.Engine(sample_rate=48000.0, device=-1, chain=3)
+    assert tap.config_set("whirl.mic.distance", 20) == 0  # no whirl stage, no bound
+    tap.close()

@@ -141,7 +141,47 @@ def test_oracle_tonegen_only_vs_reference(oracle, refchk):
         assert np.array_equal(x.view(np.uint32), y.view(np.uint32))
 
 
-@pytest.mark.parametrize("sr", [44100.0, 48000.0, 96000.0])
+# the rates the CPU comparisons run beyond 44.1 / 48 / 96 kHz: the ends of the accepted range,
+# rates on both sides of the whirl chains' lower edge, and the multiples of 44.1 kHz.  Not
+# 11025 or 16000 Hz: there the reference's reverb biquad (10 kHz) lies above Nyquist and the
+# reference itself goes non-finite
+MORE_RATES = [8000.0, 22050.0, 32000.0, 36000.0, 88200.0, 176400.0, 192000.0]
+
+
+def _audible(x, what):
+    assert np.isfinite(x).all(), what
+    assert float(np.abs(x).max()) > 1e-3, what
+
+
+@pytest.mark.parametrize("sr", MORE_RATES)
+def test_oracle_chain_bitexact_vs_reference_at_rate(oracle, refchk, sr):
+    """test_oracle_chain_bitexact_vs_reference at the other accepted rates: the full
+    quartet, all five outputs, finite and audible."""
+    tpl = Template(oracle, sr=sr, seed=7)
+    for scen, nb in ((S.bench_scenario(3), 24), (S.event_scenario(5), 72)):
+        oa = S.run(Chain(oracle, tpl, 11), scen, nb, stages=True)
+        ob = S.run(Chain(refchk, tpl, 11, ref=True), scen, nb, stages=True)
+        for k, x, y in zip("LRABC", oa, ob):
+            assert np.array_equal(x.view(np.uint32), y.view(np.uint32)), (sr, k)
+            _audible(x, (sr, k))
+
+
+@pytest.mark.parametrize("sr", [36000.0, 192000.0])
+def test_oracle_fast_rotor_vs_reference(oracle, refchk, sr):
+    """Both rotors fast for 0.45 s, more than two horn turns (scenarios.fast_scens): the
+    reference passes through its smallest and its largest write-ahead, just above the
+    whirl chains' lower rate edge and at the top rate (the 2048-sample ring)."""
+    nb = int(np.ceil(0.45 * sr / 128))
+    tpl = Template(oracle, sr=sr, seed=7)
+    for i, sc in enumerate(S.fast_scens(2)):
+        oa = S.run(Chain(oracle, tpl, 6300 + i), sc, nb, stages=True)
+        ob = S.run(Chain(refchk, tpl, 6300 + i, ref=True), sc, nb, stages=True)
+        for k, x, y in zip("LRABC", oa, ob):
+            assert np.array_equal(x.view(np.uint32), y.view(np.uint32)), (sr, i, k)
+            _audible(x, (sr, i, k))
+
+
+@pytest.mark.parametrize("sr", [44100.0, 48000.0, 96000.0] + MORE_RATES)
 def test_stage_units_vs_reference(oracle, refchk, sr):
     """Each effect stage alone on seeded noise + impulses + silence (denormal path)."""
     rng = np.random.default_rng(int(sr))
@@ -158,6 +198,8 @@ def test_stage_units_vs_reference(oracle, refchk, sr):
         refchk.ref_whirl_proc3(wr, fptr(x), fptr(a[2]), fptr(a[3]), 128 * 20)
         assert np.array_equal(a[0].view(np.uint32), a[2].view(np.uint32))
         assert np.array_equal(a[1].view(np.uint32), a[3].view(np.uint32))
+        _audible(a[0], (sr, "whirl L", opt))
+        _audible(a[1], (sr, "whirl R", opt))
         oracle.orc_whirl_free(wo)
         refchk.ref_whirl_free(wr)
     for seed in (1, 99):
@@ -169,6 +211,7 @@ def test_stage_units_vs_reference(oracle, refchk, sr):
             oracle.orc_reverb_proc(ro, fptr(x), fptr(a), n)
             refchk.ref_reverb_proc(rr, fptr(x), fptr(b), n)
             assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+            _audible(a, (sr, "reverb", seed, g))
         oracle.orc_reverb_free(ro)
         refchk.ref_reverb_free(rr)
     for ch in (0.0, 0.3, 0.5, 0.9, 1.0):
@@ -179,6 +222,7 @@ def test_stage_units_vs_reference(oracle, refchk, sr):
         oracle.orc_preamp_proc(po, fptr(x), fptr(a), n)
         refchk.ref_preamp_proc(pr, fptr(x), fptr(b), n)
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+        _audible(a, (sr, "preamp", ch))
         oracle.orc_preamp_free(po)
         refchk.ref_preamp_free(pr)
 
@@ -230,11 +274,12 @@ def test_oracle_templates_vs_reference_pins(oracle, tunings):
     initKeyCompTable / initEnvelopes / applyManualDefaults / compilePlayMatrix ... reached
     by oracle/ref_tpl_pin.cpp; digests committed in tests/golden/template_pins.json by
     tests/golden/make_template_pins.py): 7 tunings x 48 / 96 kHz, plus the osc.* cfg sets
-    (envelope models, wheel EQ, harmonics, terminal / taper / crosstalk lists)."""
+    (envelope models, wheel EQ, harmonics, terminal / taper / crosstalk lists), plus one
+    template each at 8000 and 192000 Hz, the ends of the accepted range."""
     import hashlib
     from orc_bind import Cfg
     pins = _template_pins()
-    assert len(pins) == 19
+    assert len(pins) == 21 and {8000.0, 192000.0} <= {p["sr"] for p in pins}
     for p in pins:
         m = None if tunings[p["tuning"]] is None else np.array(tunings[p["tuning"]], np.float64)
         cfg = Cfg(oracle, S.CFG_SETS[p["cfg"]]) if p.get("cfg") else None

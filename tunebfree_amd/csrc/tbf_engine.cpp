@@ -192,6 +192,39 @@ static int buildShared (tbf_engine* e)
 		W *= 2;
 	if (W > 2048)
 		return fail (-22, "whirl write-ahead exceeds the reference ring (2048 samples): geometry out of range");
+	/* The smallest write-ahead the whirl kernels render exactly.  The reference adds sample
+	 * m's motions at slots floor (t), floor (t) + 1 with t = spacing + intp + (float)outpos
+	 * and only then reads and clears slot outpos (src/whirl.cpp:1432-1469, 1590-1612), so
+	 * an add with a lead under the distance to a later sample of the block is heard by
+	 * that sample.
+	 *   k_whirl: the 64 lanes of a sub-block starting at outpos B read and clear slots
+	 *   B .. B + 63 of all four rings before any of the sub-block's adds (the fast passes
+	 *   and the serial replay alike).  Sample m's add at slot s in [B + m, B + 63] is read
+	 *   by sample s - B of this sub-block in the reference, but one ring length late here;
+	 *   any s >= B + 64 is read by a later sub-block, after the add, as in the reference.
+	 *   Exact iff floor (t) >= B + 64 for every m >= 0, i.e. for m = 0: lead >= TBF_SUB.
+	 *   k_whirl_split: the horn wave reads and clears its window like k_whirl.  The drum
+	 *   wave leaves dL / dR in window k, the horn wave reads them behind the barrier the
+	 *   drum wave passes before its adds of sub-block k, and window k is cleared behind
+	 *   the next barrier.  An add of sub-block k inside window k would race with that
+	 *   read and then be cleared; from B + 64 on it lands in windows not yet consumed.
+	 *   The same condition: lead >= TBF_SUB.
+	 * Rounding: minAhead = fl (spacing + min table value).  intp = fl (fl (x fl (1 - hd)) +
+	 * fl (hd y)) with fl (1 - hd) + hd >= 1 - 2^-25 and three roundings of 2^-24 each is
+	 * >= min (x, y) (1 - 3.5 * 2^-24), at most 2048 * 3.5 * 2^-24 = 4.3e-4 under the table's
+	 * minimum (a table value is below the 2048-sample ring), and fl (spacing + intp), an
+	 * ulp of 7.6e-6 at 64, is monotone in intp: with minAhead >= 64 + 2^-10 it is >= 64.
+	 * Then spacing + intp + outpos >= 64 + outpos, an integer a float holds exactly up to
+	 * outpos 2047, so the last rounding cannot go below it and floor (t) >= outpos + 64.
+	 * Chains that end before the whirl (tonegen, preamp and reverb taps) have no bound. */
+	if (tbf_chain_stages (e->cfg.chain_mode) == TBF_NSTAGES && !(e->wt.minAhead >= TBF_WH_MIN_LEAD)) {
+		char msg[200];
+		snprintf (msg, sizeof msg,
+		          "whirl write-ahead %.3f samples is under the %.3f the whirl kernels render exactly: sample rate too low "
+		          "or microphone too near the rotors",
+		          (double)e->wt.minAhead, (double)TBF_WH_MIN_LEAD);
+		return fail (-22, msg);
+	}
 	e->wringLen = W;
 	/* vibrato tables (src/vibrato.cpp:91-95, 224-251) */
 	e->vibTab.resize (3 * 2048);
@@ -2140,6 +2173,15 @@ int tbf_debug_layout (const tbf_engine* e, uint32_t* wring_len, float* max_ahead
 	if (wring_len) *wring_len = e->wringLen;
 	if (max_ahead) *max_ahead = e->wt.maxAhead;
 	if (slab_len) *slab_len = e->slabLen;
+	return 0;
+}
+
+int tbf_debug_whirl_lead (const tbf_engine* e, float* min_ahead, float* bound)
+{
+	if (!e)
+		return fail (-22, "null argument");
+	if (min_ahead) *min_ahead = e->wt.minAhead;
+	if (bound) *bound = TBF_WH_MIN_LEAD;
 	return 0;
 }
 

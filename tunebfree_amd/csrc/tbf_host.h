@@ -147,6 +147,7 @@ struct WhirlTables {
 	float              drf[5];
 	double             revHorn[9], revDrum[9];
 	float              maxAhead; /* largest write-ahead in samples */
+	float              minAhead; /* smallest write-ahead (lead) of the twelve motions in samples */
 	void build (double sr, const Config& c);
 };
 

@@ -659,6 +659,7 @@ void WhirlTables::build (double rate, const Config& c)
 	const double micZ  = (hornZOffsetCm * sr / 100.0) / airSpeed;
 	float*       hnFwd = displ.data (), *hnBwd = hnFwd + 16384, *drFwd = hnBwd + 16384, *drBwd = drFwd + 16384;
 	float        maxhn = 0.f, maxdr = 0.f;
+	float        minhf = INFINITY, minhb = INFINITY, mindr = INFINITY; /* hnFwd, hnBwd, drFwd (= drBwd reversed) */
 	for (int i = 0; i < 16384; i++) {
 		double       v    = (2.0 * M_PI * (double)i) / (double)16384;
 		double       a    = micD - (hornR * cos (v));
@@ -672,16 +673,24 @@ void WhirlTables::build (double rate, const Config& c)
 		drBwd[16384 - (i + 1)]    = drFwd[i];
 		maxhn                     = std::max (maxhn, std::max (hnFwd[i], hnBwd[16384 - (i + 1)]));
 		maxdr                     = std::max (maxdr, drFwd[i]);
+		minhf                     = std::min (minhf, hnFwd[i]);
+		minhb                     = std::min (minhb, hnBwd[16384 - (i + 1)]);
+		mindr                     = std::min (mindr, drFwd[i]);
 	}
 	static const float hs[6] = {12.0f, 18.0f, 53.0f, 50.0f, 106.0f, 116.0f};
 	static const float ds[6] = {36.0f, 39.0f, 79.0f, 86.0f, 123.0f, 116.0f};
 	static const int   ph[6] = {0, 16384 >> 1, (16384 * 2) / 6, (16384 * 5) / 6, (16384 * 1) / 6, (16384 * 4) / 6};
 	maxAhead                 = 0.f;
+	minAhead                 = INFINITY;
 	for (int i = 0; i < 6; i++) {
 		hornSpacing[i] = (float)(hs[i] * sr / 22100.0 + hornR + 1.0);
 		drumSpacing[i] = (float)(ds[i] * sr / 22100.0 + drumR + 1.0);
 		phase[i]       = ph[i];
 		maxAhead       = std::max (maxAhead, std::max (hornSpacing[i] + maxhn, drumSpacing[i] + maxdr));
+		/* motions 0, 3, 4 read the forward displacement table, 1, 2, 5 the backward one
+		 * (src/whirl.cpp:1542-1585); the sums in float, as HN_MOTION / DR_MOTION form them */
+		const bool fwd = i == 0 || i == 3 || i == 4;
+		minAhead       = std::min (minAhead, std::min (hornSpacing[i] + (fwd ? minhf : minhb), drumSpacing[i] + mindr));
 	}
 	/* initTables (338-517) */
 	std::vector<float> bfw (16384 * 5, 0.f);

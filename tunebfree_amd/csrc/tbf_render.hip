@@ -15,8 +15,9 @@
  *
  * Inside a stage: lane = sample (tonegen: 2 samples/lane; reverb/whirl: 64-sample
  * sub-blocks).  Every ring read of a sub-block happens before its ring writes, which is
- * exact because every ring delay exceeds the sub-block (reverb >= 560, whirl >= 79
- * samples ahead).  Per-sample IIR/phase recurrences run on single lanes in the
+ * exact because every ring delay exceeds the sub-block (reverb >= 560 samples; whirl >=
+ * TBF_WH_MIN_LEAD, which buildShared, csrc/tbf_engine.cpp, enforces when the engine is
+ * created or configured).  Per-sample IIR/phase recurrences run on single lanes in the
  * reference's literal operation order.
  * Float discipline: compiled with -ffp-contract=off, no fast-math, denormals kept;
  * every expression follows the reference's evaluation order so results are
@@ -2947,8 +2948,10 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 		const uint32_t outpos = (R.outpos + (uint32_t)n) & 2047u;
 		const int32_t  unwrap = (int32_t)(R.outpos + (uint32_t)n - outpos); /* 0 or 2048 */
 		const float    xin    = (float)((double)(sb == 0 ? in0 : in1) + 1e-14);
-		/* ring reads + clear at outpos: before this sub-block's writes, which land >= 79
-		 * slots ahead (src/whirl.cpp:1585-1600); the drum rings' outputs are read by the
+		/* ring reads + clear at outpos: before this sub-block's writes, which land at
+		 * least one sub-block ahead of their own sample (TBF_WH_MIN_LEAD, enforced by
+		 * buildShared, csrc/tbf_engine.cpp) and so past the window read here
+		 * (src/whirl.cpp:1585-1600); the drum rings' outputs are read by the
 		 * shelves in place first */
 		const uint32_t o   = outpos & WM;
 		const float    hlv = sm.wring[0][o], hrv = sm.wring[1][o];
@@ -3349,7 +3352,8 @@ k_whirl (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf_s
  * which the drum wave leaves in its ring slots at outpos (just consumed by the shelves)
  * and the horn wave reads after one workgroup barrier per sub-block; the drum wave clears
  * those slots after the next barrier, before its own adds of that sub-block (the adds land
- * >= 79 slots ahead and the ring holds write-ahead + 68 slots, so an add of sub-block k + 1
+ * >= TBF_SUB slots ahead of their own sample, i.e. past window k, which buildShared's
+ * TBF_WH_MIN_LEAD check in csrc/tbf_engine.cpp enforces, and the ring holds write-ahead + 68 slots, so an add of sub-block k + 1
  * may wrap into window k only after it is cleared).  Each rotor's speed update is its own
  * half of whirl_speed.  So every instance is two waves of about half the instructions
  * (a latency-bound kernel: one wave alone per SIMD ran 7.1 ms per 512 blocks against 9.4

@@ -12,6 +12,10 @@
 
 #define TBF_BLK 128   /* BUFFER_SIZE_SAMPLES, src/tonegen.h:53 */
 #define TBF_SUB 64    /* sub-block for reverb/whirl: one sample per lane of a wave64 */
+/* the smallest whirl write-ahead (WhirlTables::minAhead) the whirl kernels render exactly:
+ * one sub-block plus what float rounding can take off a lead; derived at its check,
+ * buildShared (csrc/tbf_engine.cpp), which refuses a whirl chain below it */
+#define TBF_WH_MIN_LEAD ((float)TBF_SUB + 1.0f / 1024.0f)
 #define TBF_NW 256    /* NOF_WHEELS, src/tonegen.h:79 */
 #define TBF_VRING 256
 #define TBF_WH_TSTRIDE 16388 /* device stride of the whirl displacement tables (16-byte aligned rows) */

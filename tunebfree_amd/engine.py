@@ -143,13 +143,20 @@ class Engine:
 
     def layout(self):
         """The cfg-derived layout (tbf_debug_layout): compact whirl ring window, the
-        geometry's largest write-ahead, reverb slab length."""
+        geometry's largest write-ahead, reverb slab length; and (tbf_debug_whirl_lead) its
+        smallest write-ahead with the bound under which a whirl chain is refused."""
         f = self._lib.tbf_debug_layout
         f.restype = C.c_int
         f.argtypes = [C.c_void_p, _u32p, _fp, _u32p]
         w, a, s = C.c_uint32(), C.c_float(), C.c_uint32()
         _check(f(self._h, C.byref(w), C.byref(a), C.byref(s)))
-        return {"wring_len": w.value, "max_ahead": a.value, "slab_len": s.value}
+        g = self._lib.tbf_debug_whirl_lead
+        g.restype = C.c_int
+        g.argtypes = [C.c_void_p, _fp, _fp]
+        m, b = C.c_float(), C.c_float()
+        _check(g(self._h, C.byref(m), C.byref(b)))
+        return {"wring_len": w.value, "max_ahead": a.value, "slab_len": s.value, "min_ahead": m.value,
+                "min_ahead_bound": b.value}
 
     def front_chunks(self):
         """tbf_debug_front_chunks: chunks with events stepped by (the device's, the host's) front end"""
