@@ -74,6 +74,20 @@ typedef struct tbf_engine tbf_engine;
                                    * stage takes its exact serial replay (parity tests of the
                                    * fallbacks; slow) */
 
+/* tbf_engine_config.whirl_out: which of the reference's whirl entry points the engine's L / R
+ * are.  The LV2 and CLAP shells call whirlProc3, the JACK host's plain build whirlProc
+ * (src/main.cpp:265-281); the two differ in their bits even at the default microphone width
+ * (DESIGN.md section 1).  Every call that yields L / R delivers the chosen pair in the same two
+ * buffers: tbf_render*, tbf_synth_sound and its FIFO, tbf_process*.  The mode is the engine's,
+ * not an instance's: the DSP state is the same in either, so clone, save, load and remove are
+ * untouched and a blob saved on an engine of one mode loads into an engine of the other.
+ * tbf_engine_create returns -22 for any other value, and for TBF_WHIRL_OUT_DIRECT on a chain
+ * that does not run the whirl (TBF_CHAIN_TONEGEN and the tap chains). */
+#define TBF_WHIRL_OUT_MIC 0    /* whirlProc3 (src/whirl.cpp:1653-1681): the four rotor signals through the
+                                * microphone mix */
+#define TBF_WHIRL_OUT_DIRECT 1 /* whirlProc (src/whirl.cpp:1640-1650): whirlProc2's outL / outR, the direct sum
+                                * y + hornLevel * H + leak per channel (1592-1606); under bypass the input */
+
 typedef struct tbf_engine_config {
 	double   sample_rate; /* Hz, 8000 .. 192000; a chain that runs the whirl (TBF_CHAIN_FULL, TBF_CHAIN_FX)
 	                       * needs every rotor write-ahead >= 64 samples: from about 35.5 kHz with the
@@ -83,7 +97,9 @@ typedef struct tbf_engine_config {
 	int32_t  device;      /* HIP device ordinal */
 	uint32_t chain_mode;  /* TBF_CHAIN_* */
 	uint32_t debug_flags; /* TBF_DEBUG_*, 0 in production */
-	uint32_t reserved[3];
+	uint32_t whirl_out;   /* TBF_WHIRL_OUT_*: what outL / outR of every call carry (the size and layout of the
+	                       * struct are those of the three reserved words this field was the first of) */
+	uint32_t reserved[2];
 } tbf_engine_config;
 
 int         tbf_abi_version (void);
@@ -326,6 +342,47 @@ int tbf_process_device (tbf_engine* e, uint32_t nblocks, const float* d_in, uint
 int tbf_process_events (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, const float* d_in,
                         uint64_t in_stride, float* d_outL, float* d_outR, uint64_t stride, void* stream);
 
+/* ---- rotor outputs: whirlProc2's horn and drum pairs out of one render ----
+ * The reference's JACK host in its cabinet-convolution build calls whirlProc2 (w, in, NULL,
+ * NULL, hornL, hornR, drumL, drumR, n), sends the horn pair through its convolver and mixes the
+ * drum pair in afterwards (src/main.cpp:265-281).  These calls deliver the four signals of one
+ * render: hornL / hornR = hornLevel * H + leak and drumL / drumR = the drum shelves' outputs,
+ * exactly whirlProc2's outHL / outHR / outDL / outDR (src/whirl.cpp:1592-1606); under bypass
+ * the horn pair is the input and the drum pair 0 (1197-1215).  Instance i writes plane[i *
+ * rotors->stride + 0 .. nblocks*128) of each of the four planes; all four pointers are required,
+ * rotors->stride >= nblocks*128, and for device memory the tbf_render_device contract holds
+ * (float alignment, odd strides, nothing outside [0, nblocks*128) of a row is written).  outL /
+ * outR carry what the engine's whirl_out says, at their own stride, or are both NULL.  The
+ * output ranges must not overlap one another.
+ * -22 on a chain that does not run the whirl, on a missing pointer (rotors, one of its four,
+ * one of outL / outR without the other), on a short stride and on an effects-only input range
+ * that overlaps any of the six outputs; -19 on a host-only engine.  Validation comes first: a
+ * refused call renders nothing and steps no control.  tbf_debug_launches counts these renders'
+ * whirl launches as TBF_LAUNCH_WHIRL / TBF_LAUNCH_WHIRL_SPLIT.  There is no frame-granular FIFO
+ * for the rotor planes: a host that serves odd frame counts keeps its own (as for
+ * tbf_process*). */
+typedef struct tbf_rotor_out {
+	float*   hornL; /* hornLevel * H + leak, left and right (outHL, outHR) */
+	float*   hornR;
+	float*   drumL; /* the drum shelves' outputs (outDL, outDR) */
+	float*   drumR;
+	uint64_t stride; /* floats between instances, the same for the four planes */
+} tbf_rotor_out;
+/* TBF_CHAIN_FULL; host buffers, synchronous (as tbf_render) */
+int tbf_render_rotors (tbf_engine* e, uint32_t nblocks, float* outL, float* outR, uint64_t stride,
+                       const tbf_rotor_out* rotors);
+/* TBF_CHAIN_FULL; device memory on `stream` with events, as tbf_render_events (ev == NULL with
+ * nev == 0: no events, as tbf_render_device) */
+int tbf_render_rotors_device (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, float* d_outL,
+                              float* d_outR, uint64_t stride, const tbf_rotor_out* rotors, void* stream);
+/* TBF_CHAIN_FX; host buffers, synchronous (as tbf_process) */
+int tbf_process_rotors (tbf_engine* e, uint32_t nblocks, const float* in, uint64_t in_stride, float* outL,
+                        float* outR, uint64_t stride, const tbf_rotor_out* rotors);
+/* TBF_CHAIN_FX; device memory on `stream` with events, as tbf_process_events */
+int tbf_process_rotors_device (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, const float* d_in,
+                               uint64_t in_stride, float* d_outL, float* d_outR, uint64_t stride,
+                               const tbf_rotor_out* rotors, void* stream);
+
 int tbf_synchronize (tbf_engine* e);
 /* Which exact-but-slow paths the kernels took since the engine's first render (cumulative,
  * informational; the results are bit-identical either way).  Waits for the engine's
@@ -378,8 +435,8 @@ enum {
 	TBF_LAUNCH_TONEGEN_RANGES = 1, /* k_tonegen, an instance's blocks split over several waves */
 	TBF_LAUNCH_RV_CORE        = 2, /* k_rv_core, the streaming reverb network */
 	TBF_LAUNCH_RV_CORE_LDS    = 3, /* k_rv_core_lds */
-	TBF_LAUNCH_WHIRL          = 4, /* k_whirl */
-	TBF_LAUNCH_WHIRL_SPLIT    = 5, /* k_whirl_split */
+	TBF_LAUNCH_WHIRL          = 4, /* k_whirl, in any output mode (whirl_out, rotor rows) */
+	TBF_LAUNCH_WHIRL_SPLIT    = 5, /* k_whirl_split, likewise */
 	TBF_LAUNCH_KINDS          = 6
 };
 int tbf_debug_launches (const tbf_engine* e, uint64_t* counts, uint32_t cap);

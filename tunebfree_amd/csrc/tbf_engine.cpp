@@ -40,6 +40,8 @@ extern "C" uint32_t tbf_chain_kernels (uint32_t chain);
 static bool chainFx (uint32_t chain) { return tbf_chain_first_stage (chain) > 0; }
 /* whether the chain runs the reverb stages (and so holds their stage buffers) */
 static bool chainReverb (uint32_t chain) { return tbf_chain_stages (chain) > 2; }
+/* the chain ends in the whirl (TBF_CHAIN_FULL, TBF_CHAIN_FX) */
+static bool chainWhirl (uint32_t chain) { return tbf_chain_stages (chain) == TBF_NSTAGES; }
 extern "C" int tbf_launch_tgctl (const tbf_launch* P, hipStream_t stream);
 extern "C" int tbf_launch_front (const tbf_launch* P, hipStream_t stream);
 extern "C" int tbf_launch_calibrate (int op, void* buf, uint64_t n, hipStream_t s);
@@ -362,6 +364,10 @@ int tbf_engine_create (const tbf_engine_config* cfg, tbf_engine** out)
 		return fail (-22, "null argument");
 	if (!(cfg->sample_rate >= 8000.0 && cfg->sample_rate <= 192000.0))
 		return fail (-22, "sample_rate out of range");
+	if (cfg->whirl_out != TBF_WHIRL_OUT_MIC && cfg->whirl_out != TBF_WHIRL_OUT_DIRECT)
+		return fail (-22, "whirl_out: not a TBF_WHIRL_OUT_* value");
+	if (cfg->whirl_out != TBF_WHIRL_OUT_MIC && !chainWhirl (cfg->chain_mode))
+		return fail (-22, "whirl_out: TBF_WHIRL_OUT_DIRECT needs a chain that runs the whirl (TBF_CHAIN_FULL, TBF_CHAIN_FX)");
 	/* device -1: host-only engine (table builders and control plane; render refuses) */
 	if (cfg->device != -1) {
 		int ndev = 0;
@@ -1388,6 +1394,10 @@ static int fillLaunch (tbf_engine* e, tbf_launch& P, uint32_t n, float* dL, floa
 	P.chain     = tbf_chain_kernels (e->cfg.chain_mode);
 	P.ext       = e->extIn;
 	P.extStride = e->extStride;
+	for (int k = 0; k < 4; k++)
+		P.rot[k] = e->rotOut[k];
+	P.rotStride = e->rotStride;
+	P.whOut     = e->cfg.whirl_out;
 	P.slabLen   = e->slabLen;
 	P.errFlags  = e->err.p;
 	P.dbg       = e->cfg.debug_flags;
@@ -1897,6 +1907,100 @@ static int processImpl (tbf_engine* e, uint32_t nblocks, const float* dIn, uint6
 	return rc;
 }
 
+static int eventsSorted (const tbf_event* ev, uint32_t nev);
+
+/* The checks of the tbf_*_rotors* calls, all before anything renders or steps (in: the
+ * effects-only calls' input rows, NULL for the tbf_render_rotors* calls); pointers are compared
+ * on the host only. */
+static int rotorArgs (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, bool fx, const float* in,
+                      uint64_t inStride, const float* outL, const float* outR, uint64_t stride, const tbf_rotor_out* rot)
+{
+	if (!e || !rot || !rot->hornL || !rot->hornR || !rot->drumL || !rot->drumR || (fx && !in) || (nev && !ev))
+		return fail (-22, "null argument");
+	if (!outL != !outR)
+		return fail (-22, "outL and outR: both or neither");
+	if (!chainWhirl (e->cfg.chain_mode))
+		return fail (-22, "rotor outputs need a chain that runs the whirl (TBF_CHAIN_FULL, TBF_CHAIN_FX)");
+	if (fx != chainFx (e->cfg.chain_mode))
+		return fail (-22, fx ? "tbf_process_rotors* needs an effects-only engine (TBF_CHAIN_FX)"
+		                     : "effects-only engine (TBF_CHAIN_FX) has no tone generator to render: use tbf_process_rotors*");
+	const uint64_t per = (uint64_t)nblocks * TBF_BLK;
+	if (rot->stride < per)
+		return fail (-22, "rotors->stride smaller than nblocks*128");
+	if (outL && stride < per)
+		return fail (-22, "stride smaller than nblocks*128");
+	if (fx && inStride < per)
+		return fail (-22, "in_stride smaller than nblocks*128");
+	const uint64_t n = e->inst.size ();
+	if (fx && n && per) { /* [first float, one past the last float) of each range */
+		const uintptr_t i0 = (uintptr_t)in, i1 = (uintptr_t)(in + (n - 1) * inStride + per);
+		const float*    o[6]  = {outL, outR, rot->hornL, rot->hornR, rot->drumL, rot->drumR};
+		for (int k = outL ? 0 : 2; k < 6; k++) {
+			const uintptr_t o0 = (uintptr_t)o[k], o1 = (uintptr_t)(o[k] + (n - 1) * (k < 2 ? stride : rot->stride) + per);
+			if (i0 < o1 && o0 < i1)
+				return fail (-22, "input and output ranges overlap");
+		}
+	}
+	if (int rc = eventsSorted (ev, nev))
+		return rc;
+	if (e->cfg.device < 0)
+		return fail (-19, "host-only engine (device -1) cannot render");
+	return 0;
+}
+
+/* renderImpl / processImpl with the call's rotor planes (tbf_engine.rotOut: set for this call
+ * only).  Without L / R the kernels' L / R stores go to the horn rows, where each lane's horn
+ * stores follow them to the same address (wh_flush, tbf_render.hip): no branch around a store
+ * and no buffer to throw away. */
+static int rotorImpl (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, const float* dIn, uint64_t inStride,
+                      float* dL, float* dR, uint64_t stride, const tbf_rotor_out& rot, hipStream_t s)
+{
+	float* const planes[4] = {rot.hornL, rot.hornR, rot.drumL, rot.drumR};
+	std::copy (planes, planes + 4, e->rotOut);
+	e->rotStride = rot.stride;
+	if (!dL) {
+		dL     = rot.hornL;
+		dR     = rot.hornR;
+		stride = rot.stride;
+	}
+	const int rc = dIn ? processImpl (e, nblocks, dIn, inStride, dL, dR, stride, s, ev, nev)
+	                   : renderImpl (e, nblocks, dL, dR, stride, s, ev, nev);
+	std::fill (e->rotOut, e->rotOut + 4, nullptr);
+	return rc;
+}
+
+/* the host-buffer rotor calls: stage the planes (and L / R, the input) on the device, render,
+ * copy back, as tbf_render and tbf_process do */
+static int rotorHost (tbf_engine* e, uint32_t nblocks, const float* in, uint64_t inStride, float* outL, float* outR,
+                      uint64_t stride, const tbf_rotor_out* rot)
+{
+	HIPCHK (hipSetDevice (e->cfg.device));
+	const uint32_t n   = (uint32_t)e->inst.size ();
+	const size_t   per = (size_t)nblocks * TBF_BLK;
+	if (n == 0 || per == 0)
+		return 0;
+	if (e->rotBuf.ensure (4 * (size_t)n * per) || (in && e->extBuf.ensure ((size_t)n * per)) ||
+	    (outL && (e->outL.ensure ((size_t)n * per) || e->outR.ensure ((size_t)n * per))))
+		return fail (-12, "out of device memory (rotor outputs)");
+	if (in)
+		HIPCHK (hipMemcpy2DAsync (e->extBuf.p, per * 4, in, inStride * 4, per * 4, n, hipMemcpyHostToDevice, e->stream));
+	const size_t        plane = (size_t)n * per;
+	const tbf_rotor_out dev   = {e->rotBuf.p, e->rotBuf.p + plane, e->rotBuf.p + 2 * plane, e->rotBuf.p + 3 * plane, per};
+	if (int rc = rotorImpl (e, nblocks, nullptr, 0, in ? e->extBuf.p : nullptr, per, outL ? e->outL.p : nullptr,
+	                        outL ? e->outR.p : nullptr, per, dev, e->stream))
+		return rc;
+	float* const host[4] = {rot->hornL, rot->hornR, rot->drumL, rot->drumR};
+	for (int k = 0; k < 4; k++)
+		HIPCHK (hipMemcpy2DAsync (host[k], rot->stride * 4, e->rotBuf.p + k * plane, per * 4, per * 4, n, hipMemcpyDeviceToHost,
+		                          e->stream));
+	if (outL) {
+		HIPCHK (hipMemcpy2DAsync (outL, stride * 4, e->outL.p, per * 4, per * 4, n, hipMemcpyDeviceToHost, e->stream));
+		HIPCHK (hipMemcpy2DAsync (outR, stride * 4, e->outR.p, per * 4, per * 4, n, hipMemcpyDeviceToHost, e->stream));
+	}
+	HIPCHK (hipStreamSynchronize (e->stream));
+	return 0;
+}
+
 /* events sorted by block (in parallel: large event lists) */
 static int eventsSorted (const tbf_event* ev, uint32_t nev)
 {
@@ -1960,6 +2064,39 @@ int tbf_process (tbf_engine* e, uint32_t nblocks, const float* in, uint64_t inSt
 	HIPCHK (hipMemcpy2DAsync (outR, stride * 4, e->outR.p, per * 4, per * 4, n, hipMemcpyDeviceToHost, e->stream));
 	HIPCHK (hipStreamSynchronize (e->stream));
 	return 0;
+}
+
+int tbf_render_rotors (tbf_engine* e, uint32_t nblocks, float* outL, float* outR, uint64_t stride, const tbf_rotor_out* rot)
+{
+	if (int rc = rotorArgs (e, nblocks, nullptr, 0, false, nullptr, 0, outL, outR, stride, rot))
+		return rc;
+	return rotorHost (e, nblocks, nullptr, 0, outL, outR, stride, rot);
+}
+
+int tbf_render_rotors_device (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, float* dL, float* dR,
+                              uint64_t stride, const tbf_rotor_out* rot, void* stream)
+{
+	if (int rc = rotorArgs (e, nblocks, ev, nev, false, nullptr, 0, dL, dR, stride, rot))
+		return rc;
+	HIPCHK (hipSetDevice (e->cfg.device));
+	return rotorImpl (e, nblocks, ev, nev, nullptr, 0, dL, dR, stride, *rot, stream ? (hipStream_t)stream : e->stream);
+}
+
+int tbf_process_rotors (tbf_engine* e, uint32_t nblocks, const float* in, uint64_t inStride, float* outL, float* outR,
+                        uint64_t stride, const tbf_rotor_out* rot)
+{
+	if (int rc = rotorArgs (e, nblocks, nullptr, 0, true, in, inStride, outL, outR, stride, rot))
+		return rc;
+	return rotorHost (e, nblocks, in, inStride, outL, outR, stride, rot);
+}
+
+int tbf_process_rotors_device (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, const float* dIn,
+                               uint64_t inStride, float* dL, float* dR, uint64_t stride, const tbf_rotor_out* rot, void* stream)
+{
+	if (int rc = rotorArgs (e, nblocks, ev, nev, true, dIn, inStride, dL, dR, stride, rot))
+		return rc;
+	HIPCHK (hipSetDevice (e->cfg.device));
+	return rotorImpl (e, nblocks, ev, nev, dIn, inStride, dL, dR, stride, *rot, stream ? (hipStream_t)stream : e->stream);
 }
 
 int tbf_render_device (tbf_engine* e, uint32_t nblocks, float* dL, float* dR, uint64_t stride, void* stream)

@@ -429,6 +429,11 @@ struct tbf_engine {
 	 * reads the caller's buffer waits on every call (the input-side analogue of outWait) */
 	const float*                            extIn      = nullptr;
 	uint64_t                                extStride  = 0;
+	/* the current call's rotor planes hornL, hornR, drumL, drumR (tbf_*_rotors*; NULL in every
+	 * other call), and the host-buffer variants' staging of the four (plane k at rotBuf + k * n * per) */
+	float*                                  rotOut[4]  = {nullptr, nullptr, nullptr, nullptr};
+	uint64_t                                rotStride  = 0;
+	DevBuf<float>                           rotBuf;
 	bool                                    inWait     = false;
 	uint64_t                                aheadCount = 0;       /* k_rv_pre launches that ran ahead (tbf_debug_pre_ahead) */
 	bool                                    rvLdsOn  = true;  /* k_rv_core_lds when the rings fit (TBF_RV_LDS=0: k_rv_core) */

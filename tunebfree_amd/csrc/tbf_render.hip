@@ -46,6 +46,12 @@
 #ifndef WH_WAVES
 #define WH_WAVES 4
 #endif
+/* k_whirl<512> in an output mode other than the mic mix (WH_OM_*): 3 waves per SIMD.  At 4 the
+ * mic mix already spills 11 VGPRs (48 B of scratch per lane); the direct sum would spill 10 and
+ * the rotor rows 14, and these modes run without scratch (142 / 147 VGPRs) */
+#ifndef WH_WAVES_OUT
+#define WH_WAVES_OUT 3
+#endif
 #ifndef WH_RG
 #define WH_RG 2 /* k_whirl rings per motion group (4 or 2) */
 #endif
@@ -2755,23 +2761,162 @@ __device__ __forceinline__ float wh_output (float t, float z0, float z1, const f
 	return (t * c[2]) + (c[3] * t1) + (c[4] * t2);
 }
 
-/* A sub-block's two output stores, held back until the next sub-block has issued its
+/* What a whirl kernel writes, a compile-time mode: bit 0, what outL / outR carry (0:
+ * whirlProc3's mic mix, src/whirl.cpp:1653-1681; 1: whirlProc's direct sum outL / outR,
+ * 1592-1606: tbf_launch.whOut); bit 1, whirlProc2's outHL / outHR / outDL / outDR as four
+ * more rows (tbf_launch.rot).  The mic-mix kernels (mode 0) are the kernels as they were. */
+#define WH_OM_DIRECT 1
+#define WH_OM_ROTORS 2
+
+/* A sub-block's output stores, held back until the next sub-block has issued its
  * motion-table loads: vmcnt retires in issue order, so a store issued before a load is
  * waited for with it, and every sub-block waits for its table loads (and every block for
  * its input) -- with the stores issued first, each of those waits also waited out the
  * previous stores' write latency. */
-struct WhOut {
+template <bool ROT>
+struct WhOutT {
 	float* l;
 	float* r;
 	float  vl, vr;
 };
+/* with the rotor rows: six values and one sample index into the instance's six rows of this
+ * chunk (WhRows), which are wave-uniform -- one held VGPR instead of six held pointers (k_whirl
+ * <512> has 128 VGPRs) */
+template <>
+struct WhOutT<true> {
+	uint32_t off;
+	float    vl, vr, h[4]; /* h: hornL, hornR, drumL, drumR */
+};
+template <bool ROT>
+struct WhRowsT {
+};
+template <>
+struct WhRowsT<true> {
+	float* p[6]; /* L, R, hornL, hornR, drumL, drumR: the instance's rows at the chunk's first sample */
+};
+template <int OM>
+using WhOut = WhOutT<(OM & WH_OM_ROTORS) != 0>;
+template <int OM>
+using WhRows = WhRowsT<(OM & WH_OM_ROTORS) != 0>;
+
+template <int OM>
+__device__ __forceinline__ WhRows<OM> wh_rows (const tbf_launch& P, const uint32_t inst)
+{
+	WhRows<OM> rows;
+	if constexpr ((OM & WH_OM_ROTORS) != 0) {
+		rows.p[0] = P.outL + (size_t)inst * P.outStride + P.outOffset;
+		rows.p[1] = P.outR + (size_t)inst * P.outStride + P.outOffset;
+#pragma unroll
+		for (int k = 0; k < 4; k++)
+			rows.p[2 + k] = P.rot[k] + (size_t)inst * P.rotStride + P.outOffset;
+	}
+	return rows;
+}
 
 /* the held stores; unconditional (a store under a branch makes the wait counts after it
- * unknown, and the compiler then waits for everything) */
-__device__ __forceinline__ void wh_flush (const WhOut& o)
+ * unknown, and the compiler then waits for everything).  L and R go first: a rotor render
+ * without L / R has them point at the horn rows (tbf_engine.cpp), where the horn stores,
+ * later in the same lane's order, land on top */
+template <int OM>
+__device__ __forceinline__ void wh_flush (const WhOut<OM>& o, const WhRows<OM>& rows)
 {
-	*o.l = o.vl;
-	*o.r = o.vr;
+	if constexpr ((OM & WH_OM_ROTORS) != 0) {
+		rows.p[0][o.off] = o.vl;
+		rows.p[1][o.off] = o.vr;
+#pragma unroll
+		for (int k = 0; k < 4; k++)
+			rows.p[2 + k][o.off] = o.h[k];
+	} else {
+		*o.l = o.vl;
+		*o.r = o.vr;
+	}
+}
+
+/* where the held stores of sample i of the block at oL / oR (bo samples into the chunk) go */
+template <int OM>
+__device__ __forceinline__ void wh_hold_at (WhOut<OM>& o, float* oL, float* oR, const uint32_t bo, const int i)
+{
+	if constexpr ((OM & WH_OM_ROTORS) != 0)
+		o.off = bo + (uint32_t)i;
+	else {
+		o.l = oL + i;
+		o.r = oR + i;
+	}
+}
+
+/* the held stores of sample i: its outputs (whirlProc2 outL/outR or whirlProc3's mix;
+ * outHL/outHR/outDL/outDR) from the horn rings' hlv / hrv, the leak and the drum shelves'
+ * dL / dR */
+template <int OM>
+__device__ __forceinline__ void wh_hold (WhOut<OM>& o, float* oL, float* oR, const uint32_t bo, const int i, const tbf_inst_const& K,
+                                         const float hlv, const float hrv, const float leak, const float dL, const float dR)
+{
+	const float hL = K.hornLevel * hlv + leak;
+	const float hR = K.hornLevel * hrv + leak;
+	wh_hold_at<OM> (o, oL, oR, bo, i);
+	if constexpr ((OM & WH_OM_DIRECT) != 0) {
+		o.vl = (dL + K.hornLevel * hlv) + leak; /* y + hornLevel * HLbuf[outpos] + leak, src/whirl.cpp:1594 */
+		o.vr = (dR + K.hornLevel * hrv) + leak;
+	} else {
+		o.vl = hL * K.mic[0] + hR * K.mic[1] + dL * K.mic[2] + dR * K.mic[3];
+		o.vr = hL * K.mic[4] + hR * K.mic[5] + dL * K.mic[6] + dR * K.mic[7];
+	}
+	if constexpr ((OM & WH_OM_ROTORS) != 0) {
+		o.h[0] = hL;
+		o.h[1] = hR;
+		o.h[2] = dL;
+		o.h[3] = dR;
+	}
+}
+
+/* the same under bypass (src/whirl.cpp:1197-1215): every output but the drum pair is the
+ * input, the drum pair 0; whirlProc3 mixes those */
+template <int OM>
+__device__ __forceinline__ void wh_hold_bypass (WhOut<OM>& o, const tbf_inst_const& K, const float in)
+{
+	if constexpr ((OM & WH_OM_DIRECT) != 0)
+		o.vl = o.vr = in;
+	else {
+		o.vl = in * K.mic[0] + in * K.mic[1] + 0.f * K.mic[2] + 0.f * K.mic[3];
+		o.vr = in * K.mic[4] + in * K.mic[5] + 0.f * K.mic[6] + 0.f * K.mic[7];
+	}
+	if constexpr ((OM & WH_OM_ROTORS) != 0) {
+		o.h[0] = o.h[1] = in;
+		o.h[2] = o.h[3] = 0.f;
+	}
+}
+
+/* a bypassed block's outputs: the first sub-block's at once, the second sub-block's become
+ * the held stores, so that the held stores always carry the latest output of their lane (a
+ * later flush of an older one would overwrite a newer value) */
+template <int OM>
+__device__ __forceinline__ void wh_bypass_out (WhOut<OM>& pend, const WhRows<OM>& rows, float* oL, float* oR, const uint32_t bo,
+                                               const int lane, const tbf_inst_const& K, const float in0, const float in1)
+{
+	wh_flush<OM> (pend, rows);
+	WhOut<OM> first;
+	wh_hold_at<OM> (first, oL, oR, bo, lane);
+	wh_hold_bypass<OM> (first, K, in0);
+	wh_flush<OM> (first, rows);
+	wh_hold_at<OM> (pend, oL, oR, bo, NL + lane);
+	wh_hold_bypass<OM> (pend, K, in1);
+}
+
+/* before the first sub-block's outputs exist, the held stores write 0 to the first output
+ * sample of the lane, which the real output overwrites later (same lane, same address: in
+ * order) */
+template <int OM>
+__device__ __forceinline__ void wh_hold_init (WhOut<OM>& pend, const tbf_launch& P, const uint32_t inst, const unsigned lane)
+{
+	if constexpr ((OM & WH_OM_ROTORS) != 0)
+		pend.off = lane;
+	else {
+		pend.l = P.outL + (size_t)inst * P.outStride + P.outOffset + lane;
+		pend.r = P.outR + (size_t)inst * P.outStride + P.outOffset + lane;
+	}
+	pend.vl = pend.vr = 0.f;
+	if constexpr ((OM & WH_OM_ROTORS) != 0)
+		pend.h[0] = pend.h[1] = pend.h[2] = pend.h[3] = 0.f;
 }
 
 /* k_whirl's wave-uniform state, in registers (scalar ones, through readfirstlane /
@@ -2877,10 +3022,11 @@ __device__ __forceinline__ void wh_reg_store (WhLds<W>& sm, const WhReg& R)
  * block's input (samples lane, lane + 64); the next block's is loaded from inNext into
  * nx0 / nx1 during the first sub-block (inNext may be this block's own input when there
  * is no next block: a harmless re-read) */
-template <int W>
+template <int W, int OM>
 __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypass, const int revOpt, const tbf_inst_const& K,
                              const float in0, const float in1, const float* __restrict__ inNext, float& nx0, float& nx1,
-                             const bool hasNext, float* __restrict__ oL, float* __restrict__ oR, WhOut& pend, WhReg& R)
+                             const bool hasNext, float* __restrict__ oL, float* __restrict__ oR, const uint32_t bo,
+                             const WhRows<OM>& rows, WhOut<OM>& pend, WhReg& R)
 {
 	const int     lane  = threadIdx.x;
 	tbf_wh_state& st    = sm.st;
@@ -2895,16 +3041,7 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 		/* whirlProc2 bypass (src/whirl.cpp:1197-1215) + whirlProc3 mix */
 		nx0 = inNext[lane];
 		nx1 = inNext[lane + NL];
-		wh_flush (pend);
-		oL[lane] = in0 * K.mic[0] + in0 * K.mic[1] + 0.f * K.mic[2] + 0.f * K.mic[3];
-		oR[lane] = in0 * K.mic[4] + in0 * K.mic[5] + 0.f * K.mic[6] + 0.f * K.mic[7];
-		/* the second sub-block's outputs become the held stores, so that the held
-		 * stores always carry the latest output of their lane (a later flush of an older
-		 * one would overwrite a newer value) */
-		pend.l  = oL + NL + lane;
-		pend.r  = oR + NL + lane;
-		pend.vl = in1 * K.mic[0] + in1 * K.mic[1] + 0.f * K.mic[2] + 0.f * K.mic[3];
-		pend.vr = in1 * K.mic[4] + in1 * K.mic[5] + 0.f * K.mic[6] + 0.f * K.mic[7];
+		wh_bypass_out<OM> (pend, rows, oL, oR, bo, lane, K, in0, in1);
 		return;
 	}
 	/* whirl_speed changes nothing while no rotary selection arrives, neither rotor is
@@ -3127,7 +3264,7 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 			if (r0 == 0) {
 				nx0 = inNext[lane];
 				nx1 = inNext[lane + NL];
-				wh_flush (pend);
+				wh_flush<OM> (pend, rows);
 			}
 #pragma unroll
 			for (int gi = 0; gi < WH_RG; gi++) {
@@ -3233,12 +3370,17 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 		/* ---- outputs (whirlProc2 outHL/outHR/outDL/outDR + whirlProc3 mix) ---- */
 		{
 			const float leak = xf * K.leakage;
-			const float hL   = K.hornLevel * hlv + leak;
-			const float hR   = K.hornLevel * hrv + leak;
-			pend.l           = oL + sb * TBF_SUB + n;
-			pend.r           = oR + sb * TBF_SUB + n;
-			pend.vl          = hL * K.mic[0] + hR * K.mic[1] + dL * K.mic[2] + dR * K.mic[3];
-			pend.vr          = hL * K.mic[4] + hR * K.mic[5] + dL * K.mic[6] + dR * K.mic[7];
+			if constexpr (OM == 0) {
+				/* the mic mix keeps its statements here: the same expressions routed through
+				 * wh_hold compile to other register counts (k_whirl<1024> 150 VGPRs for 152) */
+				const float hL = K.hornLevel * hlv + leak;
+				const float hR = K.hornLevel * hrv + leak;
+				pend.l         = oL + sb * TBF_SUB + n;
+				pend.r         = oR + sb * TBF_SUB + n;
+				pend.vl        = hL * K.mic[0] + hR * K.mic[1] + dL * K.mic[2] + dR * K.mic[3];
+				pend.vr        = hL * K.mic[4] + hR * K.mic[5] + dL * K.mic[6] + dR * K.mic[7];
+			} else
+				wh_hold<OM> (pend, oL, oR, bo, sb * TBF_SUB + n, K, hlv, hrv, leak, dL, dR);
 		}
 		/* ---- carry filter taps and histories ---- */
 		R.z[0] = rlf (xf, NL - 1);
@@ -3271,8 +3413,9 @@ __device__ void stage_whirl (const tbf_launch& P, WhLds<W>& sm, const bool bypas
 
 static_assert (sizeof (tbf_wh_params) % 4 == 0 && sizeof (tbf_wh_params) <= 4 * NL, "one dword per lane");
 
-template <int W>
-__global__ void __attribute__ ((amdgpu_flat_work_group_size (NL, NL), amdgpu_waves_per_eu (W <= 512 ? WH_WAVES : (W <= 1024 ? 2 : 1))))
+template <int W, int OM>
+__global__ void __attribute__ ((amdgpu_flat_work_group_size (NL, NL),
+                                amdgpu_waves_per_eu (W <= 512 ? (OM ? WH_WAVES_OUT : WH_WAVES) : (W <= 1024 ? 2 : 1))))
 k_whirl (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf_seg_ctl* __restrict__ ctl)
 {
 	__shared__ WhLds<W> sm;
@@ -3306,13 +3449,9 @@ k_whirl (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf_s
 		c0 = inBase[threadIdx.x];
 		c1 = inBase[threadIdx.x + NL];
 	}
-	/* before the first sub-block's outputs exist, the held store writes 0 to the first
-	 * output sample of the lane, which the real output overwrites later (same lane, same
-	 * address: in order) */
-	WhOut pend;
-	pend.l  = P.outL + (size_t)inst * P.outStride + P.outOffset + threadIdx.x;
-	pend.r  = P.outR + (size_t)inst * P.outStride + P.outOffset + threadIdx.x;
-	pend.vl = pend.vr = 0.f;
+	const WhRows<OM> rows = wh_rows<OM> (P, inst);
+	WhOut<OM>        pend;
+	wh_hold_init<OM> (pend, P, inst, threadIdx.x);
 	for (uint32_t blk = 0; blk < P.nBlocks; blk++) {
 		float*     oL = P.outL + (size_t)inst * P.outStride + P.outOffset + (size_t)blk * TBF_BLK;
 		float*     oR = P.outR + (size_t)inst * P.outStride + P.outOffset + (size_t)blk * TBF_BLK;
@@ -3331,13 +3470,13 @@ k_whirl (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf_s
 		 * changes its coefficients */
 		const int  nx      = blk_lane ((int)blk + 1);
 		const bool hasNext = more && !rl (byv, nx) && !rl (wsv, nx);
-		stage_whirl<W> (P, sm, rl (byv, blk_lane ((int)blk)) != 0, rl (rvv, blk_lane ((int)blk)), K, c0, c1,
-		                inBase + (size_t)(more ? blk + 1 : blk) * TBF_BLK, n0, n1, hasNext, oL, oR, pend, R);
+		stage_whirl<W, OM> (P, sm, rl (byv, blk_lane ((int)blk)) != 0, rl (rvv, blk_lane ((int)blk)), K, c0, c1,
+		                    inBase + (size_t)(more ? blk + 1 : blk) * TBF_BLK, n0, n1, hasNext, oL, oR, blk * TBF_BLK, rows, pend, R);
 		c0 = n0;
 		c1 = n1;
 	}
 	if (P.nBlocks > 0)
-		wh_flush (pend);
+		wh_flush<OM> (pend, rows);
 	wh_reg_store (sm, R);
 	copy_words (S, &sm.st);
 	for (uint32_t i = threadIdx.x; i < 4u * W; i += NL)
@@ -3580,10 +3719,11 @@ __device__ __forceinline__ void wh_ring (const tbf_launch& P, WhLds<W>& sm, cons
 }
 
 /* the horn wave's block (whirlProc2's horn half + whirlProc3 mix): outputs via the held stores */
-template <int W>
+template <int W, int OM>
 __device__ void whirl_horn (const tbf_launch& P, WhLds<W>& sm, const bool bypass, const int revOpt, const tbf_inst_const& K,
                             const float in0, const float in1, const float* __restrict__ inNext, float& nx0, float& nx1,
-                            const bool hasNext, float* __restrict__ oL, float* __restrict__ oR, WhOut& pend, uint32_t& opos)
+                            const bool hasNext, float* __restrict__ oL, float* __restrict__ oR, const uint32_t bo,
+                            const WhRows<OM>& rows, WhOut<OM>& pend, uint32_t& opos)
 {
 	const int     lane = threadIdx.x & (NL - 1), n = lane;
 	tbf_wh_state& st   = sm.st;
@@ -3591,13 +3731,7 @@ __device__ void whirl_horn (const tbf_launch& P, WhLds<W>& sm, const bool bypass
 		/* whirlProc2 bypass (src/whirl.cpp:1197-1215) + whirlProc3 mix (see stage_whirl) */
 		nx0 = inNext[lane];
 		nx1 = inNext[lane + NL];
-		wh_flush (pend);
-		oL[lane] = in0 * K.mic[0] + in0 * K.mic[1] + 0.f * K.mic[2] + 0.f * K.mic[3];
-		oR[lane] = in0 * K.mic[4] + in0 * K.mic[5] + 0.f * K.mic[6] + 0.f * K.mic[7];
-		pend.l   = oL + NL + lane;
-		pend.r   = oR + NL + lane;
-		pend.vl  = in1 * K.mic[0] + in1 * K.mic[1] + 0.f * K.mic[2] + 0.f * K.mic[3];
-		pend.vr  = in1 * K.mic[4] + in1 * K.mic[5] + 0.f * K.mic[6] + 0.f * K.mic[7];
+		wh_bypass_out<OM> (pend, rows, oL, oR, bo, lane, K, in0, in1);
 		return;
 	}
 	int brake = 0;
@@ -3681,7 +3815,7 @@ __device__ void whirl_horn (const tbf_launch& P, WhLds<W>& sm, const bool bypass
 		/* behind this sub-block's loads: the next block's input and the held output stores */
 		nx0 = inNext[lane];
 		nx1 = inNext[lane + NL];
-		wh_flush (pend);
+		wh_flush<OM> (pend, rows);
 		wh_ring<W, true> (P, sm, K, ang + K.fwAng, 0, outpos, unwrap, xin, 0.f, 0.f);
 		wh_ring<W, true> (P, sm, K, ang + K.bwAng, 1, outpos, unwrap, xin, 0.f, 0.f);
 		/* the drum wave's dL / dR of this sub-block, left in its ring slots at outpos */
@@ -3689,12 +3823,17 @@ __device__ void whirl_horn (const tbf_launch& P, WhLds<W>& sm, const bool bypass
 		const float dL = sm.wring[2][o], dR = sm.wring[3][o];
 		{
 			const float leak = xf * K.leakage;
-			const float hL   = K.hornLevel * hlv + leak;
-			const float hR   = K.hornLevel * hrv + leak;
-			pend.l           = oL + sb * TBF_SUB + n;
-			pend.r           = oR + sb * TBF_SUB + n;
-			pend.vl          = hL * K.mic[0] + hR * K.mic[1] + dL * K.mic[2] + dR * K.mic[3];
-			pend.vr          = hL * K.mic[4] + hR * K.mic[5] + dL * K.mic[6] + dR * K.mic[7];
+			if constexpr (OM == 0) {
+				/* the mic mix keeps its statements here: the same expressions routed through
+				 * wh_hold compile to other register counts (k_whirl<1024> 150 VGPRs for 152) */
+				const float hL = K.hornLevel * hlv + leak;
+				const float hR = K.hornLevel * hrv + leak;
+				pend.l         = oL + sb * TBF_SUB + n;
+				pend.r         = oR + sb * TBF_SUB + n;
+				pend.vl        = hL * K.mic[0] + hR * K.mic[1] + dL * K.mic[2] + dR * K.mic[3];
+				pend.vr        = hL * K.mic[4] + hR * K.mic[5] + dL * K.mic[6] + dR * K.mic[7];
+			} else
+				wh_hold<OM> (pend, oL, oR, bo, sb * TBF_SUB + n, K, hlv, hrv, leak, dL, dR);
 		}
 		if (lane == NL - 1) {
 			st.z[0] = xf;
@@ -3802,7 +3941,7 @@ __device__ void whirl_drum (const tbf_launch& P, WhLds<W>& sm, const bool bypass
 	wave_sync ();
 }
 
-template <int W>
+template <int W, int OM>
 __global__ void __attribute__ ((amdgpu_flat_work_group_size (2 * NL, 2 * NL),
                                 amdgpu_waves_per_eu (W <= 512 ? WHS_WAVES : (W <= 1024 ? 4 : 2))))
 k_whirl_split (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf_seg_ctl* __restrict__ ctl)
@@ -3839,10 +3978,9 @@ k_whirl_split (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const
 		c0 = inBase[lane];
 		c1 = inBase[lane + NL];
 	}
-	WhOut pend;
-	pend.l  = P.outL + (size_t)inst * P.outStride + P.outOffset + lane;
-	pend.r  = P.outR + (size_t)inst * P.outStride + P.outOffset + lane;
-	pend.vl = pend.vr = 0.f;
+	const WhRows<OM> rows = wh_rows<OM> (P, inst);
+	WhOut<OM>        pend;
+	wh_hold_init<OM> (pend, P, inst, (unsigned)lane);
 	int clr = -1; /* drum wave: the window whose dL / dR slots await clearing */
 	for (uint32_t blk = 0; blk < P.nBlocks; blk++) {
 		float*     oL = P.outL + (size_t)inst * P.outStride + P.outOffset + (size_t)blk * TBF_BLK;
@@ -3864,14 +4002,14 @@ k_whirl_split (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const
 		const int   rev     = rl (rvv, blk_lane ((int)blk));
 		const float* inNext = inBase + (size_t)(more ? blk + 1 : blk) * TBF_BLK;
 		if (horn)
-			whirl_horn<W> (P, sm, byp, rev, K, c0, c1, inNext, n0, n1, hasNext, oL, oR, pend, opos);
+			whirl_horn<W, OM> (P, sm, byp, rev, K, c0, c1, inNext, n0, n1, hasNext, oL, oR, blk * TBF_BLK, rows, pend, opos);
 		else
 			whirl_drum<W> (P, sm, byp, rev, K, c0, c1, inNext, n0, n1, opos, clr);
 		c0 = n0;
 		c1 = n1;
 	}
 	if (horn && P.nBlocks > 0)
-		wh_flush (pend);
+		wh_flush<OM> (pend, rows);
 	__syncthreads (); /* the horn wave has read the last window's dL / dR */
 	if (!horn && clr >= 0) {
 		sm.wring[2][((uint32_t)clr + (uint32_t)lane) & (uint32_t)(W - 1)] = 0.f;
@@ -3887,6 +4025,28 @@ k_whirl_split (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const
 }
 
 /* ------------------------------------------------------------------ launch */
+/* stage 5 in output mode OM: k_whirl or k_whirl_split for the ring window */
+template <int OM>
+static int launch_whirl (const tbf_launch* P, hipStream_t stream)
+{
+	const dim3 grid (P->nInst), block (NL), sblock (2 * NL);
+	if (P->whSplit)
+		switch (P->wringLen) {
+			case 512: hipLaunchKernelGGL ((k_whirl_split<512, OM>), grid, sblock, 0, stream, *P, P->cst, P->ctl); break;
+			case 1024: hipLaunchKernelGGL ((k_whirl_split<1024, OM>), grid, sblock, 0, stream, *P, P->cst, P->ctl); break;
+			case 2048: hipLaunchKernelGGL ((k_whirl_split<2048, OM>), grid, sblock, 0, stream, *P, P->cst, P->ctl); break;
+			default: return -22;
+		}
+	else
+		switch (P->wringLen) {
+			case 512: hipLaunchKernelGGL ((k_whirl<512, OM>), grid, block, 0, stream, *P, P->cst, P->ctl); break;
+			case 1024: hipLaunchKernelGGL ((k_whirl<1024, OM>), grid, block, 0, stream, *P, P->cst, P->ctl); break;
+			case 2048: hipLaunchKernelGGL ((k_whirl<2048, OM>), grid, block, 0, stream, *P, P->cst, P->ctl); break;
+			default: return -22;
+		}
+	return 0;
+}
+
 /* stage k (0 k_tonegen, 1 k_mixpre, 2 k_rv_pre, 3 k_rv_core, 4 k_rv_post, 5 k_whirl) of one
  * launch chunk; the chain mode decides which stages run (tbf_chain_stages) */
 extern "C" int tbf_launch_stage (const tbf_launch* P, int k, hipStream_t stream)
@@ -3939,21 +4099,20 @@ extern "C" int tbf_launch_stage (const tbf_launch* P, int k, hipStream_t stream)
 	else if (k == 4)
 		hipLaunchKernelGGL (k_rv_post, dim3 ((P->nInst + RVP_CB - 1) / RVP_CB), dim3 (RVP_THREADS), 0, stream, *P, P->cst, P->ctl);
 	else if (k == 5) {
-		if (P->whSplit) {
-			const dim3 sblock (2 * NL);
-			switch (P->wringLen) {
-				case 512: hipLaunchKernelGGL (k_whirl_split<512>, grid, sblock, 0, stream, *P, P->cst, P->ctl); break;
-				case 1024: hipLaunchKernelGGL (k_whirl_split<1024>, grid, sblock, 0, stream, *P, P->cst, P->ctl); break;
-				case 2048: hipLaunchKernelGGL (k_whirl_split<2048>, grid, sblock, 0, stream, *P, P->cst, P->ctl); break;
-				default: return -22;
-			}
-		} else
-		switch (P->wringLen) {
-			case 512: hipLaunchKernelGGL (k_whirl<512>, grid, block, 0, stream, *P, P->cst, P->ctl); break;
-			case 1024: hipLaunchKernelGGL (k_whirl<1024>, grid, block, 0, stream, *P, P->cst, P->ctl); break;
-			case 2048: hipLaunchKernelGGL (k_whirl<2048>, grid, block, 0, stream, *P, P->cst, P->ctl); break;
-			default: return -22;
+		/* the output mode (WH_OM_*): all four rotor rows or none, with L / R never NULL */
+		const bool rot = P->rot[0] != nullptr;
+		if (!P->outL || !P->outR || P->whOut > 1u || (rot && (!P->rot[1] || !P->rot[2] || !P->rot[3])) ||
+		    (rot && P->rotStride < (uint64_t)P->nBlocks * TBF_BLK))
+			return -22;
+		int rc;
+		switch ((P->whOut ? WH_OM_DIRECT : 0) | (rot ? WH_OM_ROTORS : 0)) {
+			case 0: rc = launch_whirl<0> (P, stream); break;
+			case WH_OM_DIRECT: rc = launch_whirl<WH_OM_DIRECT> (P, stream); break;
+			case WH_OM_ROTORS: rc = launch_whirl<WH_OM_ROTORS> (P, stream); break;
+			default: rc = launch_whirl<WH_OM_DIRECT | WH_OM_ROTORS> (P, stream); break;
 		}
+		if (rc)
+			return rc;
 	} else
 		return -22;
 	return hipGetLastError () == hipSuccess ? 0 : -5;

@@ -358,6 +358,13 @@ typedef struct tbf_launch {
 	const float*          ext;
 	uint64_t              extStride; /* floats between instances */
 	uint64_t              extOffset; /* first sample index of this chunk */
+	/* whirl outputs beyond the mic mix (the reference's JACK host, src/main.cpp:265-281); at the
+	 * end, so that the mic-mix kernels read every older field where it was */
+	float*                rot[4];    /* a rotor render's hornL, hornR, drumL, drumR rows (whirlProc2's outHL / outHR /
+	                                  * outDL / outDR, at outOffset like outL / outR); all NULL otherwise */
+	uint64_t              rotStride; /* floats between instances */
+	uint32_t              whOut;     /* TBF_WHIRL_OUT_*: what outL / outR carry */
+	uint32_t              pad2;
 } tbf_launch;
 
 #endif

@@ -25,11 +25,19 @@ class TbfError(RuntimeError):
 
 class _Config(C.Structure):
     _fields_ = [("sample_rate", C.c_double), ("device", C.c_int32), ("chain_mode", C.c_uint32),
-                ("debug_flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+                ("debug_flags", C.c_uint32), ("whirl_out", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class RotorOut(C.Structure):
+    """tbf_rotor_out: the four planes of a rotor render and their common stride (in floats)"""
+    _fields_ = [("hornL", C.c_void_p), ("hornR", C.c_void_p), ("drumL", C.c_void_p), ("drumR", C.c_void_p),
+                ("stride", C.c_uint64)]
 
 
 # tbf_engine_config.debug_flags / tbf_error_flags bits (include/tbf.h)
 DEBUG_FORCE_SERIAL = 1
+# tbf_engine_config.whirl_out (include/tbf.h TBF_WHIRL_OUT_*): whirlProc3's mic mix, whirlProc's direct sum
+WHIRL_OUT_MIC, WHIRL_OUT_DIRECT = 0, 1
 PATH_VIB_SERIAL, PATH_WH_ANGLE, PATH_WH_MOTION, PATH_RV_PHASE, PATH_RV_WINDOW = 1, 2, 4, 8, 16
 
 
@@ -71,6 +79,13 @@ SIGNATURES = {
                                      C.c_uint64, C.c_void_p]),
     "tbf_process_events": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
                                      C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "tbf_render_rotors": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RotorOut)]),
+    "tbf_render_rotors_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                           C.c_uint64, C.POINTER(RotorOut), C.c_void_p]),
+    "tbf_process_rotors": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                     C.c_uint64, C.POINTER(RotorOut)]),
+    "tbf_process_rotors_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
+                                            C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RotorOut), C.c_void_p]),
 }
 
 # tbf_engine_config.chain_mode of the effects-only chains (include/tbf.h TBF_CHAIN_FX*)
@@ -109,9 +124,9 @@ def _check(rc):
 class Engine:
     """A batch of organ instances on one GPU (one engine per device / rank)."""
 
-    def __init__(self, sample_rate=48000.0, device=0, chain=0, debug_flags=0):
+    def __init__(self, sample_rate=48000.0, device=0, chain=0, debug_flags=0, whirl_out=WHIRL_OUT_MIC):
         lib = load_library()
-        cfg = _Config(float(sample_rate), int(device), int(chain), int(debug_flags))
+        cfg = _Config(float(sample_rate), int(device), int(chain), int(debug_flags), int(whirl_out))
         h = C.c_void_p()
         _check(lib.tbf_engine_create(C.byref(cfg), C.byref(h)))
         self._lib, self._h = lib, h
@@ -382,6 +397,63 @@ class Engine:
                                             C.c_void_p(int(in_ptr)), int(in_stride), C.c_void_p(int(outL_ptr)),
                                             C.c_void_p(int(outR_ptr)), int(stride),
                                             None if stream is None else C.c_void_p(int(stream))))
+
+    def _rotor_host(self, nblocks, lr, call):
+        """four zeroed host planes (and L / R when lr), handed to call (L ptr, R ptr, RotorOut)"""
+        shape = (self.n_instances, nblocks * 128)
+        planes = [np.zeros(shape, np.float32) for _ in range(4)]
+        L, R = (np.zeros(shape, np.float32), np.zeros(shape, np.float32)) if lr else (None, None)
+        ro = RotorOut(*[p.ctypes.data for p in planes], nblocks * 128)
+        _check(call(None if L is None else L.ctypes.data, None if R is None else R.ctypes.data, C.byref(ro)))
+        return (L, R, *planes)
+
+    def render_rotors(self, nblocks, lr=True):
+        """tbf_render_rotors: one synchronous render with whirlProc2's horn and drum pairs;
+        returns (L, R, hornL, hornR, drumL, drumR), each [n_instances, nblocks*128] (L and R
+        None with lr=False: the call's NULL outL / outR)."""
+        return self._rotor_host(nblocks, lr, lambda l, r, ro: self._lib.tbf_render_rotors(
+            self._h, int(nblocks), l, r, nblocks * 128, ro))
+
+    def process_rotors(self, x, lr=True):
+        """tbf_process_rotors: Engine.process with the rotor planes; returns (L, R, hornL, hornR,
+        drumL, drumR)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n = self.n_instances
+        if x.ndim != 2 or x.shape[0] != n or x.shape[1] % 128:
+            raise ValueError(f"input shape {x.shape}: want ({n}, nblocks*128)")
+        nb = x.shape[1] // 128
+        return self._rotor_host(nb, lr, lambda l, r, ro: self._lib.tbf_process_rotors(
+            self._h, nb, x.ctypes.data, x.shape[1], l, r, x.shape[1], ro))
+
+    @staticmethod
+    def _rotor_out(rotor_ptrs, rotor_stride):
+        hl, hr, dl, dr = (None if p is None else int(p) for p in rotor_ptrs)
+        return RotorOut(hl, hr, dl, dr, int(rotor_stride))
+
+    def render_rotors_device(self, nblocks, outL_ptr, outR_ptr, stride, rotor_ptrs, rotor_stride, events=(),
+                             stream=None):
+        """tbf_render_rotors_device: enqueue a render into device memory; rotor_ptrs = (hornL,
+        hornR, drumL, drumR) raw pointers of rotor_stride floats per instance, outL_ptr /
+        outR_ptr raw pointers or both None, events as Engine.events."""
+        ev = np.ascontiguousarray(events, dtype=EVENT_DTYPE) if len(events) else np.zeros(0, EVENT_DTYPE)
+        ro = self._rotor_out(rotor_ptrs, rotor_stride)
+        _check(self._lib.tbf_render_rotors_device(
+            self._h, int(nblocks), ev.ctypes.data if len(ev) else None, len(ev),
+            None if outL_ptr is None else C.c_void_p(int(outL_ptr)),
+            None if outR_ptr is None else C.c_void_p(int(outR_ptr)), int(stride), C.byref(ro),
+            None if stream is None else C.c_void_p(int(stream))))
+
+    def process_rotors_device(self, nblocks, in_ptr, in_stride, outL_ptr, outR_ptr, stride, rotor_ptrs,
+                              rotor_stride, events=(), stream=None):
+        """tbf_process_rotors_device: render_rotors_device for an effects-only engine's
+        device-resident input rows."""
+        ev = np.ascontiguousarray(events, dtype=EVENT_DTYPE) if len(events) else np.zeros(0, EVENT_DTYPE)
+        ro = self._rotor_out(rotor_ptrs, rotor_stride)
+        _check(self._lib.tbf_process_rotors_device(
+            self._h, int(nblocks), ev.ctypes.data if len(ev) else None, len(ev), C.c_void_p(int(in_ptr)),
+            int(in_stride), None if outL_ptr is None else C.c_void_p(int(outL_ptr)),
+            None if outR_ptr is None else C.c_void_p(int(outR_ptr)), int(stride), C.byref(ro),
+            None if stream is None else C.c_void_p(int(stream))))
 
     def synchronize(self):
         _check(self._lib.tbf_synchronize(self._h))

@@ -21,7 +21,7 @@ struct B3S {
 
 static int tbf_instantiate_engine (B3S* b3s, double rate, const double* mts128)
 {
-	tbf_engine_config cfg = { rate, /*device*/ 0, TBF_CHAIN_FULL, /*debug_flags*/ 0, {0, 0, 0} };
+	tbf_engine_config cfg = { rate, /*device*/ 0, TBF_CHAIN_FULL, /*debug_flags*/ 0, TBF_WHIRL_OUT_MIC, {0, 0} };
 	uint32_t tpl, first, seed = (uint32_t)time (NULL);   /* srand(time(NULL)), lv2.cpp:949 */
 	b3s->tbf = NULL;
 	if (tbf_engine_create (&cfg, &b3s->tbf)) return -1;

@@ -12,3 +12,7 @@ CHAIN_FULL, CHAIN_TONEGEN = 0, 1
 CHAIN_TAP_PREAMP, CHAIN_TAP_REVERB = 2, 3
 # effects-only chains: the caller's audio through overdrive -> reverb -> whirl (Engine.process*)
 CHAIN_FX, CHAIN_FX_TAP_PREAMP, CHAIN_FX_TAP_REVERB = 4, 5, 6
+
+# tbf_engine_config.whirl_out: what L / R carry -- whirlProc3's microphone mix (the LV2 and CLAP
+# shells) or whirlProc's direct sum (the JACK host's plain build); Engine(..., whirl_out=)
+WHIRL_OUT_MIC, WHIRL_OUT_DIRECT = 0, 1
