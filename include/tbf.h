@@ -277,7 +277,8 @@ int tbf_synth_sound (tbf_engine* e, uint32_t nframes, float* outL, float* outR, 
  * reverb.mix, rotary.speed-preset|speed-select|speed-toggle, and the whirl's
  * whirl.horn.filter.a|b.type|hz|q|gain, whirl.horn|drum.brakepos,
  * whirl.horn|drum.acceleration|deceleration (src/whirl.cpp:699-889, registered 966-981;
- * from the next block).  value 0..127 (clamped).  Returns 0 when applied, 1 for any
+ * from the next block), and convolution.mix (src/midi.cpp:168; the cabinet calls' mix,
+ * below).  value 0..127 (clamped).  Returns 0 when applied, 1 for any
  * other name (ignored, as the reference ignores names without a registered function). */
 int tbf_midi_control (tbf_engine* e, uint32_t inst, const char* fn, int32_t value);
 /* programme definitions in the .pgm syntax (src/pgmParser.cpp:65-73, properties of
@@ -383,6 +384,71 @@ int tbf_process_rotors_device (tbf_engine* e, uint32_t nblocks, const tbf_event*
                                uint64_t in_stride, float* d_outL, float* d_outR, uint64_t stride,
                                const tbf_rotor_out* rotors, void* stream);
 
+/* ---- cabinet convolver: the horn pair through an impulse response, on the device ----
+ * The last stage of the reference's JACK host in its convolver build (src/main.cpp:265-281):
+ * whirlProc2, then the horn pair through the convolver, then the drum pair mixed in.  The
+ * reference tree holds the call site and the control name but not the convolver, so the
+ * arithmetic and the mix law below are this project's own definition.
+ * Cabinet: one engine-wide stereo impulse response at the engine's sample rate, irL[taps] and
+ * irR[taps]; hornL is convolved with irL and hornR with irR, no cross terms.  Per instance,
+ * channel and sample
+ *     wet_n = sum_k ir[k] * horn[n-k]      (horn before the instance's first cabinet block = 0;
+ *                                           no added latency)
+ *     out_n = (dry * horn_n + mix * wet_n) + drum_n,   dry = 1.0f - mix
+ * where every operation of the second line is one float32 operation in that association, and
+ * horn / drum are what the tbf_*_rotors* calls deliver (under whirl.bypass: the input and 0).
+ * The convolution is a partitioned FFT convolution in float32 (csrc/tbf_cabinet.hip); against a
+ * float64 direct sum its error stays within a few 2^-24 of max|horn| * sum|ir|.
+ * mix is per instance, 1.0f unless set: by the cfg key convolution.mix (0..1, for instances
+ * added afterwards), by tbf_midi_control (inst, "convolution.mix", v): mix = (float)(v / 127.0),
+ * or by a TBF_EV_CONTROL event with that name's id; like every control it takes effect at the
+ * next block boundary.  It is stored (and returns 0) on every engine, with or without a cabinet,
+ * and is part of the host control state that clone, save, load and remove carry.
+ * State: per instance and channel the spectra of the last horn blocks, zero at
+ * tbf_instances_add.  It advances only through the cabinet calls: a tbf_render*, tbf_process* or
+ * tbf_*_rotors* call in between renders blocks the convolver never hears, so a host uses one
+ * family of calls.  It is instance state: clone, save, load and remove copy it; a blob's header
+ * carries the response's length and a fingerprint of its taps, and a load into an engine with
+ * another cabinet, or none, returns -22 ("cabinet ..."); tbf_debug_device_bytes counts it.
+ * Like every render, the cabinet planes of a block are bit-identical however the render is cut
+ * into calls and chunks and whether controls come by call or by event. */
+#define TBF_CAB_MAX_TAPS 8192
+/* engine-wide; shapes per-instance state, so before the first tbf_instances_add (-16 after).  -22: NULL ir with
+ * taps > 0, taps > TBF_CAB_MAX_TAPS, a non-finite tap, a chain that does not run the whirl.  taps == 0: no cabinet. */
+int tbf_cabinet_set (tbf_engine* e, const float* irL, const float* irR, uint32_t taps);
+typedef struct tbf_cabinet_out {
+	float*   L;    /* required: (dry * horn + mix * wet) + drum */
+	float*   R;
+	float*   wetL; /* both or neither: the convolver's own output */
+	float*   wetR;
+	uint64_t stride; /* floats between instances, the same for the planes given */
+} tbf_cabinet_out;
+/* tbf_render_cabinet* for TBF_CHAIN_FULL, tbf_process_cabinet* for TBF_CHAIN_FX; host buffers and
+ * synchronous, or device memory on `stream` with events, as the tbf_*_rotors* calls.  rotors may
+ * be NULL; otherwise all four of its planes are required and receive the call's rotor signals.
+ * Without rotors the engine renders them into scratch of its own, at most 16 B per instance and
+ * sample of 256 blocks (a longer call is cut into pieces), -12 when the device cannot hold it.
+ * -22 without a cabinet, on the wrong chain, on a missing pointer or half a pair, on a short
+ * stride, and when any two of the ranges (input, cabinet planes, rotor planes) overlap; -19 on a
+ * host-only engine.  Validation comes first: a refused call renders nothing, steps no control
+ * and moves no history.  Device memory follows tbf_render_device's contract (float alignment,
+ * odd strides, nothing outside [0, nblocks*128) of a row written).  No frame-granular FIFO. */
+int tbf_render_cabinet (tbf_engine* e, uint32_t nblocks, const tbf_cabinet_out* cab, const tbf_rotor_out* rotors);
+int tbf_render_cabinet_device (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev,
+                               const tbf_cabinet_out* cab, const tbf_rotor_out* rotors, void* stream);
+int tbf_process_cabinet (tbf_engine* e, uint32_t nblocks, const float* in, uint64_t in_stride, const tbf_cabinet_out* cab,
+                         const tbf_rotor_out* rotors);
+int tbf_process_cabinet_device (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, const float* d_in,
+                                uint64_t in_stride, const tbf_cabinet_out* cab, const tbf_rotor_out* rotors, void* stream);
+/* test hook: taps, partitions K, history bytes per instance, k_cabinet launches so far, and one instance's mix
+ * (any pointer may be NULL; inst is checked only with wet) */
+int tbf_debug_cabinet (const tbf_engine* e, uint32_t inst, uint32_t* taps, uint32_t* parts, uint64_t* inst_bytes,
+                       uint64_t* launches, float* wet);
+
+/* k_cabinet's own time, with HIP events around each launch on its stream: enable 1 / -1 turns recording on / off;
+ * 0 returns the summed milliseconds and the launches since the last query (it waits for them) */
+int tbf_debug_cabinet_time (tbf_engine* e, int32_t enable, double* ms, uint64_t* launches);
+
 int tbf_synchronize (tbf_engine* e);
 /* Which exact-but-slow paths the kernels took since the engine's first render (cumulative,
  * informational; the results are bit-identical either way).  Waits for the engine's
@@ -446,7 +512,7 @@ int tbf_debug_pre_ahead (const tbf_engine* e, uint64_t* launches);
 /* test hook: device memory the engine holds now.  instance_bytes: the bytes allocated for
  * the arrays whose size is a function of the instance count alone (st, wring, rslab, tgc,
  * cst, the persistent slots of the program pool, the control pool ctl and its index table
- * ctlIdx).  The delta part of the program pool is left out: under device control it grows
+ * ctlIdx, and the cabinet convolver's history when a cabinet is set).  The delta part of the program pool is left out: under device control it grows
  * with the deltas of a call, and it grows by a quarter more than asked for.  stage_bytes:
  * the stage buffers mid0 / mid1 / mid2 / rvA / rvB.  Either pointer may be NULL; a host-only
  * engine reports zeros. */

@@ -169,6 +169,8 @@ int configSet (Config& c, const char* k, const char* v, int* scope)
 		{"scanner.modulation.v3", 'r', 0.0, 12.0, CFG_SHARED, [] (Config& c, double d, int) { c.vib3OffAmp = d; }},
 		/* reverb.mix */
 		{"reverb.mix", 'r', 0, 1.0, CFG_INSTANCE, [] (Config& c, double d, int) { c.reverbMix = (float)d; }},
+		/* convolution.mix (src/cfgParser.cpp:76 hands the line to the convolver) */
+		{"convolution.mix", 'r', 0, 1.0, CFG_INSTANCE, [] (Config& c, double d, int) { c.cabMix = (float)d; }},
 		/* osc.*: templates ... */
 		{"osc.x-precision", 'd', 0, 0, CFG_TEMPLATE, [] (Config& c, double d, int) { if (0.0 < d) c.tgPrecision = d; }},
 		{"osc.attack.click.level", 'r', 0.0, 1.0, CFG_TEMPLATE, [] (Config& c, double d, int) { c.envAttackClickLevel = (float)d; }},

@@ -95,6 +95,10 @@ bool controlFunction (Instance& in, const char* fn, unsigned char u)
 					return true;
 				}
 	}
+	if (!strcmp (fn, "convolution.mix")) { /* src/midi.cpp:168; the mix law is this project's */
+		in.cabWet = cabinetWet (u);           /* read by the cabinet calls alone: nothing of the chain changes */
+		return true;
+	}
 	if (!strcmp (fn, "percussion.enable")) /* src/tonegen.cpp:2850-2880 */
 		in.tg.setPercEnabled (u < 64 ? 0 : 1);
 	else if (!strcmp (fn, "percussion.decay"))
@@ -153,7 +157,9 @@ const char* const kControlNames[] = {
     "whirl.horn.filter.a.type", "whirl.horn.filter.a.hz", "whirl.horn.filter.a.q", "whirl.horn.filter.a.gain",
     "whirl.horn.filter.b.type", "whirl.horn.filter.b.hz", "whirl.horn.filter.b.q", "whirl.horn.filter.b.gain",
     "whirl.horn.brakepos", "whirl.drum.brakepos", "whirl.horn.acceleration", "whirl.horn.deceleration",
-    "whirl.drum.acceleration", "whirl.drum.deceleration"};
+    "whirl.drum.acceleration", "whirl.drum.deceleration",
+    /* appended, so the ids above stay: the cabinet convolver's mix (csrc/tbf_cabinet.cpp) */
+    "convolution.mix"};
 const int kNControls = (int)(sizeof (kControlNames) / sizeof (kControlNames[0]));
 
 /* ---------------------------------------------------------------- .pgm parser */

@@ -786,6 +786,7 @@ int tbf_instances_add (tbf_engine* e, uint32_t n, const uint32_t* tpl_ids, const
 		in.whr.init (e->wt.sr, e->conf); /* the runtime whirl parameters, as the cfg left them */
 		in.s0.wh.prm = in.whr.cur;
 		in.rvG      = e->conf.reverbMix;  /* reverbConfig: setReverbMix */
+		in.cabWet   = e->conf.cabMix;     /* convolution.mix */
 		in.whBypass = e->conf.bypass;     /* whirlConfig: whirl.bypass */
 		/* initWhirl -> computeRotationSpeeds -> setRevSelect(revSelect) ->
 		 * useRevOption(revselects[revSelect]), revselects = {4, 0, 8} (src/whirl.cpp:226-293) */
@@ -1166,6 +1167,8 @@ static int ensureDevice (tbf_engine* e)
 			e->tgc = std::move (ng);
 		}
 		e->persistStale = true;
+		if (int rc = cabinetGrow (e, old, n))
+			return rc;
 		HIPCHK (hipMemcpy (e->cst.p, k.data (), n * sizeof (tbf_inst_const), hipMemcpyHostToDevice));
 		e->hCtl.resize (n);
 		e->hProg.resize (PERSIST (n));
@@ -1968,6 +1971,14 @@ static int rotorImpl (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint
 	std::fill (e->rotOut, e->rotOut + 4, nullptr);
 	return rc;
 }
+
+int tbf::rotorRender (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, const float* dIn, uint64_t inStride,
+                      const tbf_rotor_out& rot, hipStream_t s)
+{
+	return rotorImpl (e, nblocks, ev, nev, dIn, inStride, nullptr, nullptr, 0, rot, s);
+}
+
+int tbf::eventsInOrder (const tbf_event* ev, uint32_t nev) { return eventsSorted (ev, nev); }
 
 /* the host-buffer rotor calls: stage the planes (and L / R, the input) on the device, render,
  * copy back, as tbf_render and tbf_process do */

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/tbf.h"
+#include "tbf_cabinet.h"
 #include "tbf_host.h"
 #include "tbf_types.h"
 
@@ -72,6 +73,7 @@ struct Instance {
 	} odc;
 	/* reverb mix */
 	float          rvG = 0.1f;
+	float          cabWet = 1.0f; /* convolution.mix: the cabinet convolver's wet share (csrc/tbf_cabinet.cpp) */
 	int            whBypass = 0;
 	int            revOpt = -1;   /* useRevOption (n) pending for the next block */
 	int            revSelect = 0; /* whirl revSelect: WHIRL_SLOW after initWhirl (src/whirl.cpp:1131) */
@@ -436,6 +438,22 @@ struct tbf_engine {
 	DevBuf<float>                           rotBuf;
 	bool                                    inWait     = false;
 	uint64_t                                aheadCount = 0;       /* k_rv_pre launches that ran ahead (tbf_debug_pre_ahead) */
+	/* the cabinet convolver (tbf_cabinet_set, csrc/tbf_cabinet.cpp): the engine-wide response and
+	 * its tables, the per-instance history st (a k_state_move segment like st / wring / rslab:
+	 * 2 * TBF_CAB_CH_FLOATS (K) floats per instance), the mix as the device holds it */
+	struct Cabinet {
+		uint32_t           taps = 0, K = 0; /* taps 0: no cabinet */
+		uint64_t           fp   = 0;        /* fingerprint of the taps (blob header) */
+		std::vector<float> ir[2];
+		bool               tablesUp = false; /* H and tw are on the device */
+		DevBuf<float>      H[2], tw, st, wet0, wetBlk;
+		DevBuf<float>      hostOut;          /* the host-buffer calls' staging: wet pair and rotor planes */
+		std::vector<float> wetDev;           /* wet0 as uploaded */
+		uint64_t           launches = 0;     /* k_cabinet launches (tbf_debug_cabinet) */
+		bool               timeOn = false;   /* tbf_debug_cabinet_time: an event pair around every launch */
+		std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
+		uint64_t           instFloats () const { return K ? 2 * TBF_CAB_CH_FLOATS (K) : 0; }
+	} cab;
 	bool                                    rvLdsOn  = true;  /* k_rv_core_lds when the rings fit (TBF_RV_LDS=0: k_rv_core) */
 	bool                                    rvLdsFit = false; /* the instances' rings fit k_rv_core_lds */
 	uint32_t                                rvGrid   = 0;     /* k_rv_core_lds persistent workgroups (TBF_RV_PERSIST=0: one per pair) */
@@ -481,6 +499,15 @@ extern thread_local std::vector<uint32_t>* tlAct;
  * (ensureDevice), and the wait for the engine's stream and the pipelined stage streams */
 int engineDevice (tbf_engine* e);
 int engineDrain (tbf_engine* e);
+/* for csrc/tbf_cabinet.cpp: one render (dIn NULL) or effects-only pass into the four rotor
+ * planes alone, on stream s (rotorImpl without L / R); the events' order check */
+int rotorRender (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, const float* dIn, uint64_t inStride,
+                 const tbf_rotor_out& rot, hipStream_t s);
+int eventsInOrder (const tbf_event* ev, uint32_t nev);
+/* csrc/tbf_cabinet.cpp: the history array regrown for n instances (ensureDevice: the first
+ * `old` keep theirs, the new ones start from zeros); convolution.mix's value of a control value */
+int cabinetGrow (tbf_engine* e, uint32_t old, uint32_t n);
+inline float cabinetWet (int u) { return (float)((double)(u > 127 ? 127 : u) / 127.0); }
 inline void markActive (tbf_engine* e, uint32_t i)
 {
 	if (i < e->inAct.size () && !e->inAct[i]) {

@@ -257,6 +257,7 @@ void ioInstance (A& a, Instance& in)
 	a.pod (in.odD);
 	a.pod (in.odc);
 	a.pod (in.rvG);
+	a.pod (in.cabWet);
 	a.pod (in.whBypass);
 	a.pod (in.revOpt);
 	a.pod (in.revSelect);
@@ -397,6 +398,9 @@ uint32_t deviceSegments (const tbf_engine* e, DevSeg* s)
 	if (e->devCtl)
 		s[n++] = {(unsigned char*)e->tgc.p, sizeof (tbf_tgc_state)};
 	s[n++] = {(unsigned char*)e->prog.p, PSLOTS * SLOT * sizeof (tbf_prog_entry)};
+	if (e->cab.K) /* the cabinet convolver's history (csrc/tbf_cabinet.h) */
+		s[n++] = {(unsigned char*)e->cab.st.p, e->cab.instFloats () * sizeof (float)};
+	static_assert (6 <= TBF_MOVE_SEGS, "deviceSegments lists up to six arrays");
 	return n;
 }
 
@@ -473,6 +477,8 @@ struct BlobHdr {
 	double   sampleRate;
 	uint32_t chain, device, devCtl, wringLen, slabLen, progSlots;
 	uint64_t engineFp;
+	uint32_t cabTaps, cabPad;  /* the cabinet response: its length (0: none) and the fingerprint of its taps */
+	uint64_t cabFp;
 	uint64_t devStride;        /* bytes of one device record (0 on a host-only engine) */
 	uint64_t hostOff, devOff;  /* the host records, the device records */
 	uint64_t bodyHash;         /* checksum of everything behind the header */
@@ -511,6 +517,8 @@ void fillHeader (tbf_engine* e, uint32_t n, BlobHdr& h)
 	h.slabLen     = e->slabLen;
 	h.progSlots   = (uint32_t)(PSLOTS * SLOT);
 	h.engineFp    = engineFingerprint (e);
+	h.cabTaps     = e->cab.taps;
+	h.cabFp       = e->cab.fp;
 	h.devStride   = h.device ? deviceRecordBytes (e) : 0;
 	h.hostOff     = sizeof (BlobHdr) + (uint64_t)n * sizeof (BlobInst);
 }
@@ -543,6 +551,9 @@ const char* headerMismatch (const BlobHdr& b, const BlobHdr& h)
 	FIELD (slabLen, "reverb slab length (slabLen)")
 	FIELD (progSlots, "program slots per instance")
 	FIELD (engineFp, "engine fingerprint (whirl / scanner tables)")
+	FIELD (cabTaps, "cabinet response length (tbf_cabinet_set)")
+	FIELD (cabPad, "cabinet header word")
+	FIELD (cabFp, "cabinet response taps (tbf_cabinet_set)")
 	FIELD (count, "instance count")
 	FIELD (devStride, "device record size")
 	FIELD (hostOff, "host record offset")
@@ -905,12 +916,14 @@ int tbf_instances_remove (tbf_engine* e, uint32_t n, const uint32_t* inst, uint3
 		DevBuf<tbf_inst_const> ncs;
 		DevBuf<tbf_seg_ctl>    nct;
 		DevBuf<uint32_t>       nix;
+		DevBuf<float>          ncb;
 		if (m) {
 			/* the sizes ensureDevice gives an engine that gets m instances at once */
 			const size_t pool = PROG_POOL (m, e->devCtl);
 			if (nst.ensure (m) || nwr.ensure ((size_t)m * 4 * e->wringLen) || nsl.ensure ((size_t)m * e->slabLen) ||
 			    (e->devCtl && ntg.ensure (m)) || npr.ensure (pool + pool / 4) || ncs.ensure (m) ||
-			    nct.ensure (2 * CTL_REGION (m)) || nix.ensure (2 * (size_t)m * TBF_CHUNK)) {
+			    nct.ensure (2 * CTL_REGION (m)) || nix.ensure (2 * (size_t)m * TBF_CHUNK) ||
+		    (e->cab.K && ncb.ensure ((size_t)m * e->cab.instFloats ()))) {
 				(void)hipGetLastError ();
 				return fail (-12, "out of device memory (compacted instances)");
 			}
@@ -922,6 +935,8 @@ int tbf_instances_remove (tbf_engine* e, uint32_t n, const uint32_t* inst, uint3
 			if (e->devCtl)
 				into[g++] = {(unsigned char*)ntg.p, sizeof (tbf_tgc_state)};
 			into[g++] = {(unsigned char*)npr.p, PSLOTS * SLOT * sizeof (tbf_prog_entry)};
+			if (e->cab.K)
+				into[g++] = {(unsigned char*)ncb.p, e->cab.instFloats () * sizeof (float)};
 			std::vector<uint32_t>       dst (m);
 			std::vector<tbf_inst_const> k (m);
 			for (uint32_t j = 0; j < m; j++) {
@@ -944,6 +959,8 @@ int tbf_instances_remove (tbf_engine* e, uint32_t n, const uint32_t* inst, uint3
 		e->cst   = std::move (ncs);
 		e->ctl   = std::move (nct);
 		e->ctlIdx = std::move (nix);
+		e->cab.st = std::move (ncb);
+		e->cab.wetDev.clear (); /* the mix per instance goes up again at the next cabinet call */
 		e->mid0.release (), e->mid1.release (), e->mid2.release (), e->rvA.release (), e->rvB.release ();
 		e->stageBlocks = e->stageN = 0;
 		e->devInst     = m;
@@ -1012,7 +1029,7 @@ int tbf_debug_device_bytes (const tbf_engine* e, uint64_t* instance_bytes, uint6
 	if (e->cfg.device >= 0) {
 		ib = e->st.cap * sizeof (tbf_inst_state) + e->wring.cap * sizeof (float) + e->rslab.cap * sizeof (double) +
 		     e->tgc.cap * sizeof (tbf_tgc_state) + e->cst.cap * sizeof (tbf_inst_const) + e->ctl.cap * sizeof (tbf_seg_ctl) +
-		     e->ctlIdx.cap * sizeof (uint32_t);
+		     e->ctlIdx.cap * sizeof (uint32_t) + e->cab.st.cap * sizeof (float);
 		if (e->prog.p) /* the persistent slots of the pool (its delta part grows with a call's deltas) */
 			ib += std::min<uint64_t> (PERSIST (e->devInst), e->prog.cap) * sizeof (tbf_prog_entry);
 		sb = (e->mid0.cap + e->mid1.cap + e->mid2.cap) * sizeof (float) + (e->rvA.cap + e->rvB.cap) * sizeof (double);

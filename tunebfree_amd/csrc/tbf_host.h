@@ -66,6 +66,8 @@ struct Config {
 	double vibFqHertz = 7.25, vib1OffAmp = 3.0, vib2OffAmp = 6.0, vib3OffAmp = 9.0;
 	/* reverb.mix */
 	float  reverbMix = 0.1f;
+	/* convolution.mix: the cabinet convolver's wet share of instances added from now on */
+	float  cabMix = 1.0f;
 	/* osc.* (scalar keys) */
 	double tgPrecision = 0.001, percFastDecaySeconds = 1.0, percSlowDecaySeconds = 4.0;
 	float  percEnvGainResetNorm = 1.0f, percEnvGainResetSoft = 0.5012f, percEnvScaling = 11.0f;

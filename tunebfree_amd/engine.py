@@ -34,6 +34,12 @@ class RotorOut(C.Structure):
                 ("stride", C.c_uint64)]
 
 
+class CabinetOut(C.Structure):
+    """tbf_cabinet_out: the mixed pair, the optional wet pair and their common stride (in floats)"""
+    _fields_ = [("L", C.c_void_p), ("R", C.c_void_p), ("wetL", C.c_void_p), ("wetR", C.c_void_p),
+                ("stride", C.c_uint64)]
+
+
 # tbf_engine_config.debug_flags / tbf_error_flags bits (include/tbf.h)
 DEBUG_FORCE_SERIAL = 1
 # tbf_engine_config.whirl_out (include/tbf.h TBF_WHIRL_OUT_*): whirlProc3's mic mix, whirlProc's direct sum
@@ -86,6 +92,14 @@ SIGNATURES = {
                                      C.c_uint64, C.POINTER(RotorOut)]),
     "tbf_process_rotors_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
                                             C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RotorOut), C.c_void_p]),
+    "tbf_cabinet_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "tbf_render_cabinet": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(CabinetOut), C.POINTER(RotorOut)]),
+    "tbf_render_cabinet_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(CabinetOut),
+                                            C.POINTER(RotorOut), C.c_void_p]),
+    "tbf_process_cabinet": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(CabinetOut),
+                                      C.POINTER(RotorOut)]),
+    "tbf_process_cabinet_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
+                                             C.POINTER(CabinetOut), C.POINTER(RotorOut), C.c_void_p]),
 }
 
 # tbf_engine_config.chain_mode of the effects-only chains (include/tbf.h TBF_CHAIN_FX*)
@@ -453,6 +467,97 @@ class Engine:
             self._h, int(nblocks), ev.ctypes.data if len(ev) else None, len(ev), C.c_void_p(int(in_ptr)),
             int(in_stride), None if outL_ptr is None else C.c_void_p(int(outL_ptr)),
             None if outR_ptr is None else C.c_void_p(int(outR_ptr)), int(stride), C.byref(ro),
+            None if stream is None else C.c_void_p(int(stream))))
+
+    def set_cabinet(self, irL, irR=None):
+        """tbf_cabinet_set: the engine-wide cabinet response (irR None: irL for both channels;
+        an empty irL: no cabinet).  Before the first add_instances."""
+        l = np.ascontiguousarray(irL, dtype=np.float32).ravel()
+        r = l if irR is None else np.ascontiguousarray(irR, dtype=np.float32).ravel()
+        if len(l) != len(r):
+            raise ValueError(f"irL has {len(l)} taps, irR {len(r)}")
+        _check(self._lib.tbf_cabinet_set(self._h, l.ctypes.data if len(l) else None, r.ctypes.data if len(r) else None,
+                                         len(l)))
+
+    def cabinet_info(self, inst=0):
+        """tbf_debug_cabinet: dict of taps, partitions, the history bytes per instance, the
+        k_cabinet launches so far and instance inst's mix (None when it does not exist)"""
+        f = self._lib.tbf_debug_cabinet
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_uint32, _u32p, _u32p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _fp]
+        taps, parts, nb, nl, wet = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_float()
+        has = inst < self.n_instances
+        _check(f(self._h, int(inst), C.byref(taps), C.byref(parts), C.byref(nb), C.byref(nl), C.byref(wet) if has else None))
+        return {"taps": taps.value, "partitions": parts.value, "instance_bytes": nb.value, "launches": nl.value,
+                "wet": wet.value if has else None}
+
+    def cabinet_time(self, enable=None):
+        """tbf_debug_cabinet_time: enable True / False switches the event pair around every
+        k_cabinet launch on / off; None returns (milliseconds, launches) since the last query."""
+        f = self._lib.tbf_debug_cabinet_time
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_uint64)]
+        if enable is not None:
+            _check(f(self._h, 1 if enable else -1, None, None))
+            return None
+        ms, n = C.c_double(), C.c_uint64()
+        _check(f(self._h, 0, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def _cabinet_host(self, nblocks, wet, rotors, call):
+        shape = (self.n_instances, nblocks * 128)
+        planes = [np.zeros(shape, np.float32) for _ in range(2 + (2 if wet else 0) + (4 if rotors else 0))]
+        co = CabinetOut(planes[0].ctypes.data, planes[1].ctypes.data, planes[2].ctypes.data if wet else None,
+                        planes[3].ctypes.data if wet else None, nblocks * 128)
+        ro = RotorOut(*[p.ctypes.data for p in planes[-4:]], nblocks * 128) if rotors else None
+        _check(call(C.byref(co), None if ro is None else C.byref(ro)))
+        return tuple(planes)
+
+    def render_cabinet(self, nblocks, wet=False, rotors=False):
+        """tbf_render_cabinet: one synchronous render through the cabinet convolver; returns (L, R),
+        then (wetL, wetR) with wet, then (hornL, hornR, drumL, drumR) with rotors, each
+        [n_instances, nblocks*128]."""
+        return self._cabinet_host(nblocks, wet, rotors, lambda co, ro: self._lib.tbf_render_cabinet(
+            self._h, int(nblocks), co, ro))
+
+    def process_cabinet(self, x, wet=False, rotors=False):
+        """tbf_process_cabinet: render_cabinet for an effects-only engine's input x
+        [n_instances, nblocks*128]."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n = self.n_instances
+        if x.ndim != 2 or x.shape[0] != n or x.shape[1] % 128:
+            raise ValueError(f"input shape {x.shape}: want ({n}, nblocks*128)")
+        nb = x.shape[1] // 128
+        return self._cabinet_host(nb, wet, rotors, lambda co, ro: self._lib.tbf_process_cabinet(
+            self._h, nb, x.ctypes.data, x.shape[1], co, ro))
+
+    @staticmethod
+    def _cabinet_out(cab_ptrs, cab_stride):
+        ptrs = [None if p is None else int(p) for p in cab_ptrs]
+        ptrs += [None] * (4 - len(ptrs))
+        return CabinetOut(*ptrs, int(cab_stride))
+
+    def render_cabinet_device(self, nblocks, cab_ptrs, cab_stride, rotor_ptrs=None, rotor_stride=0, events=(),
+                              stream=None):
+        """tbf_render_cabinet_device: enqueue a render through the cabinet convolver into device
+        memory; cab_ptrs = (L, R) or (L, R, wetL, wetR) raw pointers of cab_stride floats per
+        instance, rotor_ptrs None or (hornL, hornR, drumL, drumR), events as Engine.events."""
+        ev = np.ascontiguousarray(events, dtype=EVENT_DTYPE) if len(events) else np.zeros(0, EVENT_DTYPE)
+        co = self._cabinet_out(cab_ptrs, cab_stride)
+        ro = None if rotor_ptrs is None else self._rotor_out(rotor_ptrs, rotor_stride)
+        _check(self._lib.tbf_render_cabinet_device(
+            self._h, int(nblocks), ev.ctypes.data if len(ev) else None, len(ev), C.byref(co),
+            None if ro is None else C.byref(ro), None if stream is None else C.c_void_p(int(stream))))
+
+    def process_cabinet_device(self, nblocks, in_ptr, in_stride, cab_ptrs, cab_stride, rotor_ptrs=None, rotor_stride=0,
+                               events=(), stream=None):
+        """tbf_process_cabinet_device: render_cabinet_device for an effects-only engine's
+        device-resident input rows."""
+        ev = np.ascontiguousarray(events, dtype=EVENT_DTYPE) if len(events) else np.zeros(0, EVENT_DTYPE)
+        co = self._cabinet_out(cab_ptrs, cab_stride)
+        ro = None if rotor_ptrs is None else self._rotor_out(rotor_ptrs, rotor_stride)
+        _check(self._lib.tbf_process_cabinet_device(
+            self._h, int(nblocks), ev.ctypes.data if len(ev) else None, len(ev), C.c_void_p(int(in_ptr)),
+            int(in_stride), C.byref(co), None if ro is None else C.byref(ro),
             None if stream is None else C.c_void_p(int(stream))))
 
     def synchronize(self):

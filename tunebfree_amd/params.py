@@ -16,3 +16,6 @@ CHAIN_FX, CHAIN_FX_TAP_PREAMP, CHAIN_FX_TAP_REVERB = 4, 5, 6
 # tbf_engine_config.whirl_out: what L / R carry -- whirlProc3's microphone mix (the LV2 and CLAP
 # shells) or whirlProc's direct sum (the JACK host's plain build); Engine(..., whirl_out=)
 WHIRL_OUT_MIC, WHIRL_OUT_DIRECT = 0, 1
+
+# the cabinet convolver (Engine.set_cabinet): the longest impulse response, in taps (TBF_CAB_MAX_TAPS)
+CAB_MAX_TAPS = 8192
