@@ -449,6 +449,88 @@ int tbf_debug_cabinet (const tbf_engine* e, uint32_t inst, uint32_t* taps, uint3
  * 0 returns the summed milliseconds and the launches since the last query (it waits for them) */
 int tbf_debug_cabinet_time (tbf_engine* e, int32_t enable, double* ms, uint64_t* launches);
 
+/* ---- output rate conversion: L / R at another sample rate, on the device ----
+ * A streaming polyphase rate converter behind whatever L / R the chain and whirl_out deliver, on
+ * every chain mode.  Like the cabinet it is specified here, not restated from the reference
+ * (DESIGN.md section 7): the reference renders at its host's rate only, and at another rate it
+ * renders other audio (its whirl geometry is in samples).
+ * The engine rate Fi must be an integer number of Hz; the output rate Fo is an integer number of
+ * Hz and differs from Fi.  L / M = Fo / Fi in lowest terms.
+ * Prototype filter, built once on the host in double and rounded to float32:
+ *     s = max (L, M);  Z = 32 zero crossings a side;
+ *     T = ceil (2 Z s / L), rounded up to even: the taps per phase;  N = L T;  c = (N - 1) / 2;
+ *     fc = 0.45 / s  (0.9 of the narrower Nyquist);
+ *     g[k] = L * 2 fc * sinc (2 fc (k - c)) * kaiser (k; N, beta = 10),   k = 0 .. N - 1,
+ *     sinc (x) = sin (pi x) / (pi x), the Kaiser window with a double-precision I0 series.
+ * Position: per instance, P (uint64) counts the engine-rate samples the converter has consumed
+ * since tbf_instances_add; x[j] is the instance's L (or R) sample number j, x[j < 0] = 0.
+ * Output count: output sample n exists once n M < P L, so C (P) = ceil (P L / M) outputs exist
+ * after P inputs.  A call that feeds nblocks * 128 samples delivers exactly the outputs
+ * n in [C (P), C (P + nblocks * 128)) of each instance; each has P <= floor (n M / L) < P + nblocks * 128.
+ * Arithmetic, per output n:  p = n M in 64 bits, i = p div L, phi = p mod L,  acc = 0.0f,
+ *     for t = 0 .. T - 1 ascending:  acc = fmaf (g[phi + t L], x[i - t], acc);     y[n] = acc,
+ * each step one float32 fmaf, denormals kept.  Nothing depends on call or chunk length, so the
+ * output is bit-identical at every cut into calls, chunks and scratch pieces, and whether
+ * controls come by call or by event.
+ * The latency is (N - 1) / (2 L) engine-rate samples; it is reported, not compensated.  Counts
+ * differ between instances whenever their P differ (an instance added later, a blob loaded from
+ * another time).  The cap: L <= 1024 and L T <= 2^18.
+ * State: on the device the last T - 1 inputs per instance and channel, zero at
+ * tbf_instances_add; on the host P per instance.  It advances only through the calls below: a
+ * tbf_render*, tbf_process*, rotor or cabinet call in between renders blocks the converter never
+ * hears, so a host uses one family of calls.  It is instance state: clone copies it (P
+ * included), save / load copy it (the blob header carries Fo, L, M, T and a fingerprint of the
+ * table; a load into an engine with another converter, or none, returns -22 "resampler ..."),
+ * remove compacts it; tbf_debug_device_bytes counts it when a converter is set. */
+/* engine-wide; shapes per-instance state, so before the first tbf_instances_add (-16 after).  0: no converter.
+ * -22: a non-integer engine rate, out_rate_hz equal to the engine's rate, a ratio beyond the cap. */
+int tbf_resampler_set (tbf_engine* e, uint32_t out_rate_hz);
+/* ceil (nblocks * 128 * L / M): the bound on any instance's count for such a call, and the least output stride accepted */
+int tbf_resampled_frames (const tbf_engine* e, uint32_t nblocks, uint64_t* max_frames);
+typedef struct tbf_resampled_out {
+	float*    L;    /* required: the converted pair; instance i gets [0, counts[i]) of its rows */
+	float*    R;
+	float*    rawL; /* both or neither: the engine-rate pair, bit-identical to tbf_render_device's */
+	float*    rawR;
+	uint64_t  stride;     /* floats between instances of L / R: at least tbf_resampled_frames (nblocks) */
+	uint64_t  raw_stride; /* floats between instances of rawL / rawR: at least nblocks * 128 */
+	uint32_t* counts;     /* required, host memory, one per instance: filled before the call returns */
+} tbf_resampled_out;
+/* tbf_render_resampled* for TBF_CHAIN_FULL, TBF_CHAIN_TONEGEN and the tap chains, tbf_process_resampled*
+ * for the TBF_CHAIN_FX* chains; host buffers and synchronous, or device memory on `stream` with
+ * events, as the cabinet calls.  counts is host memory in both forms: the host owns P, so the
+ * counts are known without waiting for the device.  Without the raw planes the engine renders
+ * L / R into scratch of its own, at most 8 B per instance and sample of 256 blocks (a longer call is
+ * cut into pieces, each with its own events), -12 before anything renders when the device cannot
+ * hold it.  -22 without a converter, with the wrong family for the chain, on a missing pointer or
+ * half a pair, on a short stride, when any two of the ranges (input, converted rows over
+ * tbf_resampled_frames, raw rows) overlap, and for a call whose counts would pass 32 bits; -19
+ * on a host-only engine.  Validation comes first: a refused call renders nothing, steps no
+ * control and moves no state.  Device memory follows tbf_render_device's contract (float
+ * alignment, odd strides); nothing outside [0, counts[i]) of a converted row and
+ * [0, nblocks*128) of a raw row is written. */
+int tbf_render_resampled (tbf_engine* e, uint32_t nblocks, const tbf_resampled_out* out);
+int tbf_render_resampled_device (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev,
+                                 const tbf_resampled_out* out, void* stream);
+int tbf_process_resampled (tbf_engine* e, uint32_t nblocks, const float* in, uint64_t in_stride,
+                           const tbf_resampled_out* out);
+int tbf_process_resampled_device (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, const float* d_in,
+                                  uint64_t in_stride, const tbf_resampled_out* out, void* stream);
+/* test hook: L, M, T, the float32 table g[k] in k order (table may be NULL; -22 when cap < L T) and the latency in
+ * engine-rate samples; works on a host-only engine; zeros without a converter */
+int tbf_debug_resampler (const tbf_engine* e, uint32_t* L, uint32_t* M, uint32_t* T, float* table, uint64_t cap,
+                         double* latency);
+/* test hook: the host restatement of the definition on one row, from the header the kernel is built from
+ * (csrc/tbf_resample.h) with libm's fmaf.  x holds the n_in samples pos0 .., hist the T - 1 samples before them (NULL:
+ * zeros); y receives the outputs [C (pos0), C (pos0 + n_in)), *n_out their number (-22 when cap is smaller).  Works on
+ * a host-only engine. */
+int tbf_debug_resample_ref (const tbf_engine* e, const float* x, uint64_t n_in, const float* hist, uint64_t pos0, float* y,
+                            uint64_t cap, uint64_t* n_out);
+/* test hook: sets an instance's P and leaves its history alone (tests place n M across 2^32 with it) */
+int tbf_debug_resampler_pos (tbf_engine* e, uint32_t inst, uint64_t pos);
+/* k_resample's own time, as tbf_debug_cabinet_time */
+int tbf_debug_resample_time (tbf_engine* e, int32_t enable, double* ms, uint64_t* launches);
+
 int tbf_synchronize (tbf_engine* e);
 /* Which exact-but-slow paths the kernels took since the engine's first render (cumulative,
  * informational; the results are bit-identical either way).  Waits for the engine's
@@ -512,7 +594,7 @@ int tbf_debug_pre_ahead (const tbf_engine* e, uint64_t* launches);
 /* test hook: device memory the engine holds now.  instance_bytes: the bytes allocated for
  * the arrays whose size is a function of the instance count alone (st, wring, rslab, tgc,
  * cst, the persistent slots of the program pool, the control pool ctl and its index table
- * ctlIdx, and the cabinet convolver's history when a cabinet is set).  The delta part of the program pool is left out: under device control it grows
+ * ctlIdx, the cabinet convolver's history when a cabinet is set and the rate converter's when one is set).  The delta part of the program pool is left out: under device control it grows
  * with the deltas of a call, and it grows by a quarter more than asked for.  stage_bytes:
  * the stage buffers mid0 / mid1 / mid2 / rvA / rvB.  Either pointer may be NULL; a host-only
  * engine reports zeros. */

@@ -1169,6 +1169,8 @@ static int ensureDevice (tbf_engine* e)
 		e->persistStale = true;
 		if (int rc = cabinetGrow (e, old, n))
 			return rc;
+		if (int rc = resampleGrow (e, old, n))
+			return rc;
 		HIPCHK (hipMemcpy (e->cst.p, k.data (), n * sizeof (tbf_inst_const), hipMemcpyHostToDevice));
 		e->hCtl.resize (n);
 		e->hProg.resize (PERSIST (n));
@@ -1979,6 +1981,13 @@ int tbf::rotorRender (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint
 }
 
 int tbf::eventsInOrder (const tbf_event* ev, uint32_t nev) { return eventsSorted (ev, nev); }
+
+int tbf::plainRender (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, const float* dIn, uint64_t inStride,
+                      float* dL, float* dR, uint64_t stride, hipStream_t s)
+{
+	return dIn ? processImpl (e, nblocks, dIn, inStride, dL, dR, stride, s, ev, nev)
+	           : renderImpl (e, nblocks, dL, dR, stride, s, ev, nev);
+}
 
 /* the host-buffer rotor calls: stage the planes (and L / R, the input) on the device, render,
  * copy back, as tbf_render and tbf_process do */

@@ -26,6 +26,7 @@
 #include "../../include/tbf.h"
 #include "tbf_cabinet.h"
 #include "tbf_host.h"
+#include "tbf_resample.h"
 #include "tbf_types.h"
 
 namespace tbf {
@@ -74,6 +75,7 @@ struct Instance {
 	/* reverb mix */
 	float          rvG = 0.1f;
 	float          cabWet = 1.0f; /* convolution.mix: the cabinet convolver's wet share (csrc/tbf_cabinet.cpp) */
+	uint64_t       rsPos = 0;     /* the rate converter's P: engine-rate samples it has consumed (csrc/tbf_resample.cpp) */
 	int            whBypass = 0;
 	int            revOpt = -1;   /* useRevOption (n) pending for the next block */
 	int            revSelect = 0; /* whirl revSelect: WHIRL_SLOW after initWhirl (src/whirl.cpp:1131) */
@@ -454,6 +456,25 @@ struct tbf_engine {
 		std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
 		uint64_t           instFloats () const { return K ? 2 * TBF_CAB_CH_FLOATS (K) : 0; }
 	} cab;
+	/* the output rate converter (tbf_resampler_set, csrc/tbf_resample.cpp): the engine-wide
+	 * prototype and its phase-major table, the per-instance history st (a k_state_move segment
+	 * like the cabinet's: 2 * TBF_RS_HIST (T) floats per instance).  The positions are the
+	 * instances' (Instance::rsPos) */
+	struct Resampler {
+		uint32_t           Fo = 0, L = 0, M = 0, T = 0; /* L 0: no converter */
+		uint32_t           TO = 0, TS = 0;              /* k_resample's tile: outputs, taps per segment, */
+		uint32_t           winFloats = 0, ldsRow = 0;   /* its LDS window and the table's row stride in LDS (0: not there) */
+		uint64_t           fp = 0;                      /* fingerprint of the table (blob header) */
+		std::vector<float> g, pm;                       /* g[k] as defined; the same phase-major, rows of TBF_RS_ROW (T) */
+		bool               tabUp = false;               /* pm is on the device */
+		DevBuf<float>      tab, st, hostOut;            /* hostOut: the host-buffer calls' staging of the converted pair */
+		DevBuf<uint64_t>   pos;                         /* positions per instance, when they differ */
+		uint64_t           launches = 0;
+		bool               timeOn = false;              /* tbf_debug_resample_time: an event pair around every launch */
+		std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
+		uint32_t           histFloats () const { return L ? TBF_RS_HIST (T) : 0; }
+		uint64_t           instFloats () const { return 2 * (uint64_t)histFloats (); }
+	} rs;
 	bool                                    rvLdsOn  = true;  /* k_rv_core_lds when the rings fit (TBF_RV_LDS=0: k_rv_core) */
 	bool                                    rvLdsFit = false; /* the instances' rings fit k_rv_core_lds */
 	uint32_t                                rvGrid   = 0;     /* k_rv_core_lds persistent workgroups (TBF_RV_PERSIST=0: one per pair) */
@@ -507,6 +528,11 @@ int eventsInOrder (const tbf_event* ev, uint32_t nev);
 /* csrc/tbf_cabinet.cpp: the history array regrown for n instances (ensureDevice: the first
  * `old` keep theirs, the new ones start from zeros); convolution.mix's value of a control value */
 int cabinetGrow (tbf_engine* e, uint32_t old, uint32_t n);
+/* for csrc/tbf_resample.cpp: one render (dIn NULL) or effects-only pass into L / R on stream s
+ * (renderImpl / processImpl); the converter's history array regrown as cabinetGrow's */
+int plainRender (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, const float* dIn, uint64_t inStride,
+                 float* dL, float* dR, uint64_t stride, hipStream_t s);
+int resampleGrow (tbf_engine* e, uint32_t old, uint32_t n);
 inline float cabinetWet (int u) { return (float)((double)(u > 127 ? 127 : u) / 127.0); }
 inline void markActive (tbf_engine* e, uint32_t i)
 {

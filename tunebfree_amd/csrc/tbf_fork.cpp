@@ -258,6 +258,7 @@ void ioInstance (A& a, Instance& in)
 	a.pod (in.odc);
 	a.pod (in.rvG);
 	a.pod (in.cabWet);
+	a.pod (in.rsPos);
 	a.pod (in.whBypass);
 	a.pod (in.revOpt);
 	a.pod (in.revSelect);
@@ -400,7 +401,9 @@ uint32_t deviceSegments (const tbf_engine* e, DevSeg* s)
 	s[n++] = {(unsigned char*)e->prog.p, PSLOTS * SLOT * sizeof (tbf_prog_entry)};
 	if (e->cab.K) /* the cabinet convolver's history (csrc/tbf_cabinet.h) */
 		s[n++] = {(unsigned char*)e->cab.st.p, e->cab.instFloats () * sizeof (float)};
-	static_assert (6 <= TBF_MOVE_SEGS, "deviceSegments lists up to six arrays");
+	if (e->rs.L) /* the rate converter's history (csrc/tbf_resample.h) */
+		s[n++] = {(unsigned char*)e->rs.st.p, e->rs.instFloats () * sizeof (float)};
+	static_assert (7 <= TBF_MOVE_SEGS, "deviceSegments lists up to seven arrays");
 	return n;
 }
 
@@ -479,6 +482,8 @@ struct BlobHdr {
 	uint64_t engineFp;
 	uint32_t cabTaps, cabPad;  /* the cabinet response: its length (0: none) and the fingerprint of its taps */
 	uint64_t cabFp;
+	uint32_t rsFo, rsL, rsM, rsT; /* the rate converter: output rate (0: none), ratio, taps per phase, and the */
+	uint64_t rsFp;                /* fingerprint of its table */
 	uint64_t devStride;        /* bytes of one device record (0 on a host-only engine) */
 	uint64_t hostOff, devOff;  /* the host records, the device records */
 	uint64_t bodyHash;         /* checksum of everything behind the header */
@@ -519,6 +524,11 @@ void fillHeader (tbf_engine* e, uint32_t n, BlobHdr& h)
 	h.engineFp    = engineFingerprint (e);
 	h.cabTaps     = e->cab.taps;
 	h.cabFp       = e->cab.fp;
+	h.rsFo        = e->rs.Fo;
+	h.rsL         = e->rs.L;
+	h.rsM         = e->rs.M;
+	h.rsT         = e->rs.T;
+	h.rsFp        = e->rs.fp;
 	h.devStride   = h.device ? deviceRecordBytes (e) : 0;
 	h.hostOff     = sizeof (BlobHdr) + (uint64_t)n * sizeof (BlobInst);
 }
@@ -554,6 +564,11 @@ const char* headerMismatch (const BlobHdr& b, const BlobHdr& h)
 	FIELD (cabTaps, "cabinet response length (tbf_cabinet_set)")
 	FIELD (cabPad, "cabinet header word")
 	FIELD (cabFp, "cabinet response taps (tbf_cabinet_set)")
+	FIELD (rsFo, "resampler output rate (tbf_resampler_set)")
+	FIELD (rsL, "resampler ratio L (tbf_resampler_set)")
+	FIELD (rsM, "resampler ratio M (tbf_resampler_set)")
+	FIELD (rsT, "resampler taps per phase (tbf_resampler_set)")
+	FIELD (rsFp, "resampler table (tbf_resampler_set)")
 	FIELD (count, "instance count")
 	FIELD (devStride, "device record size")
 	FIELD (hostOff, "host record offset")
@@ -916,14 +931,15 @@ int tbf_instances_remove (tbf_engine* e, uint32_t n, const uint32_t* inst, uint3
 		DevBuf<tbf_inst_const> ncs;
 		DevBuf<tbf_seg_ctl>    nct;
 		DevBuf<uint32_t>       nix;
-		DevBuf<float>          ncb;
+		DevBuf<float>          ncb, nrs;
 		if (m) {
 			/* the sizes ensureDevice gives an engine that gets m instances at once */
 			const size_t pool = PROG_POOL (m, e->devCtl);
 			if (nst.ensure (m) || nwr.ensure ((size_t)m * 4 * e->wringLen) || nsl.ensure ((size_t)m * e->slabLen) ||
 			    (e->devCtl && ntg.ensure (m)) || npr.ensure (pool + pool / 4) || ncs.ensure (m) ||
 			    nct.ensure (2 * CTL_REGION (m)) || nix.ensure (2 * (size_t)m * TBF_CHUNK) ||
-		    (e->cab.K && ncb.ensure ((size_t)m * e->cab.instFloats ()))) {
+			    (e->cab.K && ncb.ensure ((size_t)m * e->cab.instFloats ())) ||
+			    (e->rs.L && nrs.ensure ((size_t)m * e->rs.instFloats ()))) {
 				(void)hipGetLastError ();
 				return fail (-12, "out of device memory (compacted instances)");
 			}
@@ -937,6 +953,8 @@ int tbf_instances_remove (tbf_engine* e, uint32_t n, const uint32_t* inst, uint3
 			into[g++] = {(unsigned char*)npr.p, PSLOTS * SLOT * sizeof (tbf_prog_entry)};
 			if (e->cab.K)
 				into[g++] = {(unsigned char*)ncb.p, e->cab.instFloats () * sizeof (float)};
+			if (e->rs.L)
+				into[g++] = {(unsigned char*)nrs.p, e->rs.instFloats () * sizeof (float)};
 			std::vector<uint32_t>       dst (m);
 			std::vector<tbf_inst_const> k (m);
 			for (uint32_t j = 0; j < m; j++) {
@@ -960,6 +978,7 @@ int tbf_instances_remove (tbf_engine* e, uint32_t n, const uint32_t* inst, uint3
 		e->ctl   = std::move (nct);
 		e->ctlIdx = std::move (nix);
 		e->cab.st = std::move (ncb);
+		e->rs.st  = std::move (nrs);
 		e->cab.wetDev.clear (); /* the mix per instance goes up again at the next cabinet call */
 		e->mid0.release (), e->mid1.release (), e->mid2.release (), e->rvA.release (), e->rvB.release ();
 		e->stageBlocks = e->stageN = 0;
@@ -1029,7 +1048,8 @@ int tbf_debug_device_bytes (const tbf_engine* e, uint64_t* instance_bytes, uint6
 	if (e->cfg.device >= 0) {
 		ib = e->st.cap * sizeof (tbf_inst_state) + e->wring.cap * sizeof (float) + e->rslab.cap * sizeof (double) +
 		     e->tgc.cap * sizeof (tbf_tgc_state) + e->cst.cap * sizeof (tbf_inst_const) + e->ctl.cap * sizeof (tbf_seg_ctl) +
-		     e->ctlIdx.cap * sizeof (uint32_t) + e->cab.st.cap * sizeof (float);
+		     e->ctlIdx.cap * sizeof (uint32_t) + e->cab.st.cap * sizeof (float) +
+		     e->rs.st.cap * sizeof (float);
 		if (e->prog.p) /* the persistent slots of the pool (its delta part grows with a call's deltas) */
 			ib += std::min<uint64_t> (PERSIST (e->devInst), e->prog.cap) * sizeof (tbf_prog_entry);
 		sb = (e->mid0.cap + e->mid1.cap + e->mid2.cap) * sizeof (float) + (e->rvA.cap + e->rvB.cap) * sizeof (double);

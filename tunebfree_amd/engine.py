@@ -40,6 +40,13 @@ class CabinetOut(C.Structure):
                 ("stride", C.c_uint64)]
 
 
+class ResampledOut(C.Structure):
+    """tbf_resampled_out: the converted pair, the optional engine-rate pair, their strides (in
+    floats) and the host array of counts"""
+    _fields_ = [("L", C.c_void_p), ("R", C.c_void_p), ("rawL", C.c_void_p), ("rawR", C.c_void_p),
+                ("stride", C.c_uint64), ("raw_stride", C.c_uint64), ("counts", C.c_void_p)]
+
+
 # tbf_engine_config.debug_flags / tbf_error_flags bits (include/tbf.h)
 DEBUG_FORCE_SERIAL = 1
 # tbf_engine_config.whirl_out (include/tbf.h TBF_WHIRL_OUT_*): whirlProc3's mic mix, whirlProc's direct sum
@@ -100,6 +107,14 @@ SIGNATURES = {
                                       C.POINTER(RotorOut)]),
     "tbf_process_cabinet_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
                                              C.POINTER(CabinetOut), C.POINTER(RotorOut), C.c_void_p]),
+    "tbf_resampler_set": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "tbf_resampled_frames": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "tbf_render_resampled": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(ResampledOut)]),
+    "tbf_render_resampled_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(ResampledOut),
+                                              C.c_void_p]),
+    "tbf_process_resampled": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(ResampledOut)]),
+    "tbf_process_resampled_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
+                                               C.POINTER(ResampledOut), C.c_void_p]),
 }
 
 # tbf_engine_config.chain_mode of the effects-only chains (include/tbf.h TBF_CHAIN_FX*)
@@ -559,6 +574,122 @@ class Engine:
             self._h, int(nblocks), ev.ctypes.data if len(ev) else None, len(ev), C.c_void_p(int(in_ptr)),
             int(in_stride), C.byref(co), None if ro is None else C.byref(ro),
             None if stream is None else C.c_void_p(int(stream))))
+
+    def set_output_rate(self, hz):
+        """tbf_resampler_set: the engine-wide output rate of the *_resampled calls (0: none).
+        Before the first add_instances."""
+        _check(self._lib.tbf_resampler_set(self._h, int(hz)))
+
+    def resampler_info(self, table=True):
+        """tbf_debug_resampler: dict of L, M, T, the latency in engine-rate samples and (with
+        table) the float32 prototype g[k] in k order"""
+        f = self._lib.tbf_debug_resampler
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, _u32p, _u32p, _u32p, C.c_void_p, C.c_uint64, _dp]
+        L, M, T, lat = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_double()
+        _check(f(self._h, C.byref(L), C.byref(M), C.byref(T), None, 0, C.byref(lat)))
+        info = {"L": L.value, "M": M.value, "T": T.value, "latency": lat.value}
+        if table:
+            g = np.zeros(L.value * T.value, np.float32)
+            _check(f(self._h, None, None, None, g.ctypes.data, len(g), None))
+            info["table"] = g
+        return info
+
+    def resampled_frames(self, nblocks):
+        """tbf_resampled_frames: the bound on any instance's count for a call of nblocks, and the
+        least output stride"""
+        m = C.c_uint64()
+        _check(self._lib.tbf_resampled_frames(self._h, int(nblocks), C.byref(m)))
+        return m.value
+
+    def resample_ref(self, x, hist=None, pos0=0):
+        """tbf_debug_resample_ref: the host restatement on one row: x the samples pos0 .., hist
+        the T - 1 samples before them (None: zeros); returns the outputs the row gains"""
+        f = self._lib.tbf_debug_resample_ref
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                      C.POINTER(C.c_uint64)]
+        x = np.ascontiguousarray(x, dtype=np.float32).ravel()
+        h = None if hist is None else np.ascontiguousarray(hist, dtype=np.float32).ravel()
+        n = C.c_uint64()
+        y = np.zeros(self.resampled_frames((len(x) + 127) // 128) + 1, np.float32)
+        _check(f(self._h, x.ctypes.data if len(x) else None, len(x), None if h is None else h.ctypes.data, int(pos0),
+                 y.ctypes.data, len(y), C.byref(n)))
+        return y[:n.value].copy()
+
+    def resampler_pos(self, inst, pos):
+        """tbf_debug_resampler_pos: set instance inst's position P; the history stays"""
+        f = self._lib.tbf_debug_resampler_pos
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64]
+        _check(f(self._h, int(inst), int(pos)))
+
+    def resample_time(self, enable=None):
+        """tbf_debug_resample_time: enable True / False switches the event pair around every
+        k_resample launch on / off; None returns (milliseconds, launches) since the last query."""
+        f = self._lib.tbf_debug_resample_time
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_uint64)]
+        if enable is not None:
+            _check(f(self._h, 1 if enable else -1, None, None))
+            return None
+        ms, n = C.c_double(), C.c_uint64()
+        _check(f(self._h, 0, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def _resampled_host(self, nblocks, raw, call):
+        n, frames = self.n_instances, self.resampled_frames(nblocks)
+        planes = [np.zeros((n, frames), np.float32) for _ in range(2)]
+        planes += [np.zeros((n, nblocks * 128), np.float32) for _ in range(2 if raw else 0)]
+        counts = np.zeros(n, np.uint32)
+        ro = ResampledOut(planes[0].ctypes.data, planes[1].ctypes.data, planes[2].ctypes.data if raw else None,
+                          planes[3].ctypes.data if raw else None, frames, nblocks * 128, counts.ctypes.data)
+        _check(call(C.byref(ro)))
+        return tuple(planes) + (counts,)
+
+    def render_resampled(self, nblocks, raw=False):
+        """tbf_render_resampled: one synchronous render at the output rate; returns (L, R), then
+        (rawL, rawR) with raw, then counts: L / R are [n_instances, resampled_frames(nblocks)] of
+        which instance i's first counts[i] are its samples (the rest zeros)."""
+        return self._resampled_host(nblocks, raw, lambda ro: self._lib.tbf_render_resampled(self._h, int(nblocks), ro))
+
+    def process_resampled(self, x, raw=False):
+        """tbf_process_resampled: render_resampled for an effects-only engine's input x
+        [n_instances, nblocks*128]."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n = self.n_instances
+        if x.ndim != 2 or x.shape[0] != n or x.shape[1] % 128:
+            raise ValueError(f"input shape {x.shape}: want ({n}, nblocks*128)")
+        nb = x.shape[1] // 128
+        return self._resampled_host(nb, raw, lambda ro: self._lib.tbf_process_resampled(
+            self._h, nb, x.ctypes.data, x.shape[1], ro))
+
+    def _resampled_out(self, out_ptrs, stride, raw_ptrs, raw_stride):
+        counts = np.zeros(self.n_instances, np.uint32)
+        raw = (None, None) if raw_ptrs is None else raw_ptrs
+        ptrs = [None if p is None else int(p) for p in tuple(out_ptrs) + tuple(raw)]
+        return ResampledOut(*ptrs, int(stride), int(raw_stride), counts.ctypes.data), counts
+
+    def render_resampled_device(self, nblocks, out_ptrs, stride, raw_ptrs=None, raw_stride=0, events=(), stream=None):
+        """tbf_render_resampled_device: enqueue a render at the output rate into device memory;
+        out_ptrs = (L, R) raw pointers of stride floats per instance, raw_ptrs None or (rawL,
+        rawR) of raw_stride floats, events as Engine.events.  Returns the counts (host)."""
+        ev = np.ascontiguousarray(events, dtype=EVENT_DTYPE) if len(events) else np.zeros(0, EVENT_DTYPE)
+        ro, counts = self._resampled_out(out_ptrs, stride, raw_ptrs, raw_stride)
+        _check(self._lib.tbf_render_resampled_device(
+            self._h, int(nblocks), ev.ctypes.data if len(ev) else None, len(ev), C.byref(ro),
+            None if stream is None else C.c_void_p(int(stream))))
+        return counts
+
+    def process_resampled_device(self, nblocks, in_ptr, in_stride, out_ptrs, stride, raw_ptrs=None, raw_stride=0,
+                                 events=(), stream=None):
+        """tbf_process_resampled_device: render_resampled_device for an effects-only engine's
+        device-resident input rows."""
+        ev = np.ascontiguousarray(events, dtype=EVENT_DTYPE) if len(events) else np.zeros(0, EVENT_DTYPE)
+        ro, counts = self._resampled_out(out_ptrs, stride, raw_ptrs, raw_stride)
+        _check(self._lib.tbf_process_resampled_device(
+            self._h, int(nblocks), ev.ctypes.data if len(ev) else None, len(ev),
+            None if in_ptr is None else C.c_void_p(int(in_ptr)), int(in_stride), C.byref(ro),
+            None if stream is None else C.c_void_p(int(stream))))
+        return counts
 
     def synchronize(self):
         _check(self._lib.tbf_synchronize(self._h))
