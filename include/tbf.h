@@ -531,6 +531,95 @@ int tbf_debug_resampler_pos (tbf_engine* e, uint32_t inst, uint64_t pos);
 /* k_resample's own time, as tbf_debug_cabinet_time */
 int tbf_debug_resample_time (tbf_engine* e, int32_t enable, double* ms, uint64_t* launches);
 
+/* ---- PCM output: interleaved integer frames with meters, on the device ----
+ * A last stage behind any two float32 planes: whatever L / R the chain and whirl_out deliver, or
+ * (tbf_pcm_convert_device) any pair of device planes, the converted rows of the resampled calls
+ * and the cabinet and rotor planes included.  It turns them into the interleaved frames a WAV
+ * writer, a dataset shard or an audio sink takes, and meters them on the way.  Like the cabinet
+ * and the rate converter it is specified here, not restated from the reference (DESIGN.md section
+ * 7).  It has no instance state: clone, save, load and remove do not know it.
+ * A frame is L then R, little-endian, frames back to back; row r holds its frames from byte
+ * r * out_stride_bytes of `out`.
+ * Quantisation, per float32 sample x, with S = 32768.0f (S16) or 8388608.0f (S24), denormals kept:
+ *     v = x * S                         one float32 multiply
+ *     t = v, or with dither t = v + d   one float32 add
+ *     q = rintf (t)                     ties to even
+ *     NaN: q = 0;   q > max: q = max;   q < min: q = min;   each counted as a clip
+ *     max = 32767 / 8388607,  min = -32768 / -8388608.
+ * So x = 1.0f clips to max (and is counted): full scale is [-1, 1 - 1 / S].  TBF_PCM_F32 copies
+ * the sample's bits unchanged (-0.f, subnormals and NaN payloads included) and counts a clip where
+ * !(fabsf (x) <= 1.0f).
+ * Dither (TBF_PCM_DITHER, S16 only: -22 with another format) is TPDF of +-1 LSB, counter-based and
+ * stateless.  With h (a) the 32-bit mixer
+ *     a ^= a >> 16;  a *= 0x7feb352d;  a ^= a >> 15;  a *= 0x846ca68b;  a ^= a >> 16
+ * the sample of row r, channel c (0: L, 1: R) and 64-bit frame index f = frame0 (r) + j, j the
+ * frame's place in the call's row, gets
+ *     k = h (h (h (seed ^ (2 r + c)) ^ lo32 (f)) ^ hi32 (f))
+ *     d = ((float)(k & 0xffff) - (float)(k >> 16)) * 0x1p-16f.
+ * seed and frame0 are the caller's; dither is no instance state.  A caller who passes the frames
+ * delivered so far as frame0 gets the same bytes at every cut into calls.  The row number is the
+ * instance's index, so tbf_instances_remove, which renumbers the survivors, changes their dither
+ * stream from then on (a caller who minds keeps its own numbering in seed and row_frame0).
+ * Meters, optional, one per row: peak = the largest fabsf (x) of the row's frames in this call
+ * (NaN skipped; 0 for an empty row), clip = the count above.  Each call overwrites them; they do
+ * not accumulate across calls.  Both are independent of order, so they are exact. */
+#define TBF_PCM_S16 0u     /* int16 L, int16 R: 4 B per frame */
+#define TBF_PCM_S24_3LE 1u /* packed 3-byte little-endian L, R: 6 B per frame */
+#define TBF_PCM_F32 2u     /* float32 L, R: 8 B per frame */
+#define TBF_PCM_DITHER 1u  /* tbf_pcm_out.flags */
+typedef struct tbf_pcm_meter {
+	float    peakL, peakR;
+	uint32_t clipL, clipR;
+} tbf_pcm_meter;
+typedef struct tbf_pcm_out {
+	void*           out;              /* required; 4-byte aligned in the *_device calls */
+	uint64_t        out_stride_bytes; /* bytes between rows: a multiple of 4, at least frames * frame bytes */
+	tbf_pcm_meter*  meters;           /* optional, one per row: device memory in the *_device calls, host memory in the host calls */
+	uint32_t        format;           /* TBF_PCM_S16 / _S24_3LE / _F32 */
+	uint32_t        flags;            /* 0 or TBF_PCM_DITHER */
+	uint32_t        seed;             /* dither */
+	uint64_t        frame0;           /* dither: the frame index of every row's first frame ... */
+	const uint64_t* row_frame0;       /* ... or, optional, host memory, one per row: each row's own */
+} tbf_pcm_out;
+/* The stage alone: n_rows rows of d_L / d_R (device memory, row r at r * in_stride floats; any
+ * 4-byte-aligned pointers and odd strides, as tbf_render_device delivers them; d_L == d_R is
+ * allowed) into out->out on `stream` (NULL: the engine's own), ordered as tbf_render_device: the
+ * planes must be complete where `stream` reaches the call, the frames and meters are complete
+ * when it has passed it.  Row r converts counts[r] frames (counts: host memory, each <= frames),
+ * or `frames` when counts is NULL; n_rows need not be the instance count.  Nothing outside
+ * [0, count * frame bytes) of a row is written.  With counts or row_frame0 the call waits for
+ * their upload before it returns.  An engine's PCM calls share staging: calls on different
+ * streams are the caller's to order. */
+int tbf_pcm_convert_device (tbf_engine* e, uint32_t n_rows, const float* d_L, const float* d_R, uint64_t in_stride,
+                            uint32_t frames, const uint32_t* counts, const tbf_pcm_out* out, void* stream);
+/* One render (tbf_render_pcm* for TBF_CHAIN_FULL, TBF_CHAIN_TONEGEN and the tap chains) or
+ * effects-only pass (tbf_process_pcm* for the TBF_CHAIN_FX* chains) delivered as nblocks * 128
+ * frames per instance, row = instance: host buffers and synchronous, or device memory on `stream`
+ * with events, as the cabinet and resampled calls.  The L / R behind them are tbf_render_device's,
+ * bit for bit.  The engine renders them into scratch of its own, at most 8 B per instance and
+ * sample of 256 blocks; a longer call is cut into pieces, each with its own events, and delivers
+ * the bytes and meters of one call.  The host forms convert into device staging and copy the
+ * packed rows out once per piece.  -12 before anything renders when the device cannot hold the
+ * scratch.
+ * -22: a format or flag that does not exist, dither with another format than S16, a missing
+ * pointer, out_stride_bytes no multiple of 4 or smaller than the row, a misaligned device
+ * pointer, a count above frames, ranges that overlap (input, frames, meters), the wrong family
+ * for the chain, events out of order; -19 on a host-only engine.  Validation comes first: a
+ * refused call renders nothing and steps no control. */
+int tbf_render_pcm (tbf_engine* e, uint32_t nblocks, const tbf_pcm_out* out);
+int tbf_render_pcm_device (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, const tbf_pcm_out* out,
+                           void* stream);
+int tbf_process_pcm (tbf_engine* e, uint32_t nblocks, const float* in, uint64_t in_stride, const tbf_pcm_out* out);
+int tbf_process_pcm_device (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, const float* d_in,
+                            uint64_t in_stride, const tbf_pcm_out* out, void* stream);
+/* test hook: the host restatement of the definition on one row, from the header the kernel is
+ * built from (csrc/tbf_pcm.h): n frames of L / R as row `row` from dither frame frame0 into
+ * n * frame bytes of out and (optional) one meter.  Needs no engine and no device.  -22 as above. */
+int tbf_debug_pcm_ref (uint32_t format, uint32_t flags, uint32_t seed, uint32_t row, uint64_t frame0, const float* L,
+                       const float* R, uint64_t n, void* out, tbf_pcm_meter* meter);
+/* k_pcm's own time, as tbf_debug_cabinet_time */
+int tbf_debug_pcm_time (tbf_engine* e, int32_t enable, double* ms, uint64_t* launches);
+
 int tbf_synchronize (tbf_engine* e);
 /* Which exact-but-slow paths the kernels took since the engine's first render (cumulative,
  * informational; the results are bit-identical either way).  Waits for the engine's

@@ -26,6 +26,7 @@
 #include "../../include/tbf.h"
 #include "tbf_cabinet.h"
 #include "tbf_host.h"
+#include "tbf_pcm.h"
 #include "tbf_resample.h"
 #include "tbf_types.h"
 
@@ -475,6 +476,16 @@ struct tbf_engine {
 		uint32_t           histFloats () const { return L ? TBF_RS_HIST (T) : 0; }
 		uint64_t           instFloats () const { return 2 * (uint64_t)histFloats (); }
 	} rs;
+	/* the PCM output stage (csrc/tbf_pcm.cpp): no instance state, only the calls' staging -- the
+	 * rows' counts and dither frames when they differ, the host-buffer calls' packed rows and meters */
+	struct Pcm {
+		DevBuf<tbf_pcm_row>   rows;
+		DevBuf<unsigned char> hostOut;
+		DevBuf<tbf_pcm_meter> hostMeters;
+		uint64_t              launches = 0;
+		bool                  timeOn = false; /* tbf_debug_pcm_time: an event pair around every launch */
+		std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
+	} pcm;
 	bool                                    rvLdsOn  = true;  /* k_rv_core_lds when the rings fit (TBF_RV_LDS=0: k_rv_core) */
 	bool                                    rvLdsFit = false; /* the instances' rings fit k_rv_core_lds */
 	uint32_t                                rvGrid   = 0;     /* k_rv_core_lds persistent workgroups (TBF_RV_PERSIST=0: one per pair) */

@@ -47,6 +47,20 @@ class ResampledOut(C.Structure):
                 ("stride", C.c_uint64), ("raw_stride", C.c_uint64), ("counts", C.c_void_p)]
 
 
+class PcmOut(C.Structure):
+    """tbf_pcm_out: the frames and their row stride in bytes, the optional meters, the format and
+    flags, and the dither's seed and frame numbering"""
+    _fields_ = [("out", C.c_void_p), ("out_stride_bytes", C.c_uint64), ("meters", C.c_void_p), ("format", C.c_uint32),
+                ("flags", C.c_uint32), ("seed", C.c_uint32), ("frame0", C.c_uint64), ("row_frame0", C.c_void_p)]
+
+
+# tbf_pcm_out.format / .flags (include/tbf.h TBF_PCM_*), bytes per frame by format, and tbf_pcm_meter
+PCM_S16, PCM_S24_3LE, PCM_F32 = 0, 1, 2
+PCM_DITHER = 1
+PCM_FRAME_BYTES = (4, 6, 8)
+METER_DTYPE = np.dtype([("peakL", "<f4"), ("peakR", "<f4"), ("clipL", "<u4"), ("clipR", "<u4")])
+
+
 # tbf_engine_config.debug_flags / tbf_error_flags bits (include/tbf.h)
 DEBUG_FORCE_SERIAL = 1
 # tbf_engine_config.whirl_out (include/tbf.h TBF_WHIRL_OUT_*): whirlProc3's mic mix, whirlProc's direct sum
@@ -115,6 +129,13 @@ SIGNATURES = {
     "tbf_process_resampled": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(ResampledOut)]),
     "tbf_process_resampled_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
                                                C.POINTER(ResampledOut), C.c_void_p]),
+    "tbf_pcm_convert_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                                         C.c_void_p, C.POINTER(PcmOut), C.c_void_p]),
+    "tbf_render_pcm": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(PcmOut)]),
+    "tbf_render_pcm_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(PcmOut), C.c_void_p]),
+    "tbf_process_pcm": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(PcmOut)]),
+    "tbf_process_pcm_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
+                                         C.POINTER(PcmOut), C.c_void_p]),
 }
 
 # tbf_engine_config.chain_mode of the effects-only chains (include/tbf.h TBF_CHAIN_FX*)
@@ -690,6 +711,111 @@ class Engine:
             None if in_ptr is None else C.c_void_p(int(in_ptr)), int(in_stride), C.byref(ro),
             None if stream is None else C.c_void_p(int(stream))))
         return counts
+
+    @staticmethod
+    def _pcm_array(fmt, n, frames):
+        """the host array of n rows of frames frames: int16 [n, frames, 2], uint8 [n, frames * 6]
+        or float32 [n, frames, 2]"""
+        if fmt == PCM_S24_3LE:
+            return np.zeros((n, frames * 6), np.uint8)
+        return np.zeros((n, frames, 2), np.int16 if fmt == PCM_S16 else np.float32)
+
+    @staticmethod
+    def pcm_ref(fmt, L, R, flags=0, seed=0, row=0, frame0=0):
+        """tbf_debug_pcm_ref: the host restatement of the PCM stage on one row (no device
+        needed): returns (frames, meter): int16 [n, 2], uint8 [n * 6] or float32 [n, 2], and a
+        METER_DTYPE scalar."""
+        f = load_library().tbf_debug_pcm_ref
+        f.restype = C.c_int
+        f.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                      C.c_void_p, C.c_void_p]
+        L = np.ascontiguousarray(L, dtype=np.float32).ravel()
+        R = np.ascontiguousarray(R, dtype=np.float32).ravel()
+        if len(L) != len(R):
+            raise ValueError("L and R differ in length")
+        out = Engine._pcm_array(int(fmt), 1, len(L))[0]
+        meter = np.zeros(1, METER_DTYPE)
+        _check(f(int(fmt), int(flags), int(seed), int(row), int(frame0), L.ctypes.data, R.ctypes.data, len(L),
+                 out.ctypes.data, meter.ctypes.data))
+        return out, meter[0]
+
+    def pcm_time(self, enable=None):
+        """tbf_debug_pcm_time: enable True / False switches the event pair around every k_pcm
+        launch on / off; None returns (milliseconds, launches) since the last query."""
+        f = self._lib.tbf_debug_pcm_time
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_uint64)]
+        if enable is not None:
+            _check(f(self._h, 1 if enable else -1, None, None))
+            return None
+        ms, n = C.c_double(), C.c_uint64()
+        _check(f(self._h, 0, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    @staticmethod
+    def _pcm_out(out_ptr, out_stride_bytes, fmt, flags, seed, frame0, row_frame0, meters_ptr):
+        """a PcmOut and the row_frame0 array it points to (keep it alive over the call)"""
+        rf = None if row_frame0 is None else np.ascontiguousarray(row_frame0, dtype=np.uint64)
+        po = PcmOut(None if out_ptr is None else int(out_ptr), int(out_stride_bytes),
+                    None if meters_ptr is None else int(meters_ptr), int(fmt), int(flags), int(seed), int(frame0),
+                    None if rf is None else rf.ctypes.data)
+        return po, rf
+
+    def _pcm_host(self, nblocks, fmt, flags, seed, frame0, row_frame0, meters, call):
+        n, frames = self.n_instances, nblocks * 128
+        out = self._pcm_array(int(fmt), n, frames)
+        m = np.zeros(n, METER_DTYPE)
+        po, _rf = self._pcm_out(out.ctypes.data, frames * PCM_FRAME_BYTES[int(fmt)], fmt, flags, seed, frame0, row_frame0,
+                                m.ctypes.data if meters else None)
+        _check(call(C.byref(po)))
+        return (out, m) if meters else out
+
+    def render_pcm(self, nblocks, fmt=PCM_S16, flags=0, seed=0, frame0=0, row_frame0=None, meters=False):
+        """tbf_render_pcm: one synchronous render delivered as interleaved frames: int16
+        [n_instances, frames, 2], uint8 [n_instances, frames * 6] (packed 24-bit) or float32
+        [n_instances, frames, 2], frames = nblocks * 128; with meters, (frames, METER_DTYPE [n])."""
+        return self._pcm_host(nblocks, fmt, flags, seed, frame0, row_frame0, meters,
+                              lambda po: self._lib.tbf_render_pcm(self._h, int(nblocks), po))
+
+    def process_pcm(self, x, fmt=PCM_S16, flags=0, seed=0, frame0=0, row_frame0=None, meters=False):
+        """tbf_process_pcm: render_pcm for an effects-only engine's input x [n_instances, nblocks*128]."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n = self.n_instances
+        if x.ndim != 2 or x.shape[0] != n or x.shape[1] % 128:
+            raise ValueError(f"input shape {x.shape}: want ({n}, nblocks*128)")
+        nb = x.shape[1] // 128
+        return self._pcm_host(nb, fmt, flags, seed, frame0, row_frame0, meters,
+                              lambda po: self._lib.tbf_process_pcm(self._h, nb, x.ctypes.data, x.shape[1], po))
+
+    def render_pcm_device(self, nblocks, out_ptr, out_stride_bytes, fmt=PCM_S16, flags=0, seed=0, frame0=0, row_frame0=None,
+                          meters_ptr=None, events=(), stream=None):
+        """tbf_render_pcm_device: enqueue a render delivered as interleaved frames into device
+        memory: row i from out_ptr + i * out_stride_bytes, meters_ptr None or device memory of one
+        tbf_pcm_meter (16 B) per instance, events as Engine.events."""
+        ev = np.ascontiguousarray(events, dtype=EVENT_DTYPE) if len(events) else np.zeros(0, EVENT_DTYPE)
+        po, _rf = self._pcm_out(out_ptr, out_stride_bytes, fmt, flags, seed, frame0, row_frame0, meters_ptr)
+        _check(self._lib.tbf_render_pcm_device(self._h, int(nblocks), ev.ctypes.data if len(ev) else None, len(ev),
+                                               C.byref(po), None if stream is None else C.c_void_p(int(stream))))
+
+    def process_pcm_device(self, nblocks, in_ptr, in_stride, out_ptr, out_stride_bytes, fmt=PCM_S16, flags=0, seed=0,
+                           frame0=0, row_frame0=None, meters_ptr=None, events=(), stream=None):
+        """tbf_process_pcm_device: render_pcm_device for an effects-only engine's device-resident
+        input rows."""
+        ev = np.ascontiguousarray(events, dtype=EVENT_DTYPE) if len(events) else np.zeros(0, EVENT_DTYPE)
+        po, _rf = self._pcm_out(out_ptr, out_stride_bytes, fmt, flags, seed, frame0, row_frame0, meters_ptr)
+        _check(self._lib.tbf_process_pcm_device(
+            self._h, int(nblocks), ev.ctypes.data if len(ev) else None, len(ev),
+            None if in_ptr is None else C.c_void_p(int(in_ptr)), int(in_stride), C.byref(po),
+            None if stream is None else C.c_void_p(int(stream))))
+
+    def pcm_convert_device(self, n_rows, L_ptr, R_ptr, in_stride, frames, out_ptr, out_stride_bytes, fmt=PCM_S16, counts=None,
+                           flags=0, seed=0, frame0=0, row_frame0=None, meters_ptr=None, stream=None):
+        """tbf_pcm_convert_device: the PCM stage alone over any two device planes of n_rows rows
+        (row r at r * in_stride floats): `frames` frames per row, or counts[r] (host array) of them."""
+        c = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+        po, _rf = self._pcm_out(out_ptr, out_stride_bytes, fmt, flags, seed, frame0, row_frame0, meters_ptr)
+        _check(self._lib.tbf_pcm_convert_device(
+            self._h, int(n_rows), C.c_void_p(int(L_ptr)), C.c_void_p(int(R_ptr)), int(in_stride), int(frames),
+            None if c is None else c.ctypes.data, C.byref(po), None if stream is None else C.c_void_p(int(stream))))
 
     def synchronize(self):
         _check(self._lib.tbf_synchronize(self._h))

@@ -19,3 +19,10 @@ WHIRL_OUT_MIC, WHIRL_OUT_DIRECT = 0, 1
 
 # the cabinet convolver (Engine.set_cabinet): the longest impulse response, in taps (TBF_CAB_MAX_TAPS)
 CAB_MAX_TAPS = 8192
+
+# the PCM output stage (Engine.render_pcm, .process_pcm, .pcm_convert_device): tbf_pcm_out.format
+# (TBF_PCM_*: int16, packed 3-byte little-endian int24, float32 frames of L then R), the bytes per
+# frame of each, and tbf_pcm_out.flags (TPDF dither, int16 only)
+PCM_S16, PCM_S24_3LE, PCM_F32 = 0, 1, 2
+PCM_FRAME_BYTES = (4, 6, 8)
+PCM_DITHER = 1
