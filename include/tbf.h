@@ -620,6 +620,89 @@ int tbf_debug_pcm_ref (uint32_t format, uint32_t flags, uint32_t seed, uint32_t 
 /* k_pcm's own time, as tbf_debug_cabinet_time */
 int tbf_debug_pcm_time (tbf_engine* e, int32_t enable, double* ms, uint64_t* launches);
 
+/* ---- Mixdown: groups of rows summed to stereo buses, on the device ----
+ * A stage behind any two float32 planes, stateless: whatever L / R the chain and whirl_out
+ * deliver, or (tbf_mix_device) any pair of device planes, the converted rows of the resampled
+ * calls and the cabinet and rotor planes included.  It sums groups of rows into stereo buses in a
+ * defined order, so a mix is as reproducible as the planes behind it, and it writes planes that
+ * tbf_pcm_convert_device takes as they come.  Like the cabinet, the rate converter and the PCM
+ * stage it is specified here, not restated from the reference.  It has no
+ * instance state: clone, save, load and remove do not know it.
+ * Input: n_rows rows of d_L / d_R.  Row r starts at r * in_stride floats.  Row r holds
+ * counts[r] <= frames valid frames, or `frames` when counts is NULL.
+ * Per row, a tbf_mix_row { uint32_t bus; float ll, lr, rl, rr; }.  bus == TBF_MIX_NONE
+ * (UINT32_MAX) means the row is in no bus: not one byte of it is read.  Otherwise bus < n_buses.
+ * Output: n_buses rows of outL / outR, each of exactly `frames` frames.
+ * For bus b and frame j, visit the rows r in ascending r with bus[r] == b and j < count[r].  Each
+ * line is one float32 fmaf, in this order:
+ *     accL = accR = +0.0f
+ *     for each such row r:
+ *         accL = fmaf (ll_r, L_r[j], accL);  accL = fmaf (lr_r, R_r[j], accL);
+ *         accR = fmaf (rl_r, L_r[j], accR);  accR = fmaf (rr_r, R_r[j], accR);
+ *     outL[b][j] = accL;  outR[b][j] = accR
+ * Denormals are kept.  NaN and Inf propagate literally.  No term is skipped because a coefficient
+ * is zero: only TBF_MIX_NONE and j >= count[r] remove a term.  A bus with no member, and the
+ * frames of a bus that none of its members reaches, are +0.0f.  d_L == d_R is allowed (mono
+ * planes).  Nothing here depends on call or chunk length, so a bus's bits are the same however a
+ * render is cut.  The order is part of the definition: the kernel parallelises over buses and
+ * frames, never over one bus's rows, and uses no float atomics. */
+#define TBF_MIX_NONE 0xFFFFFFFFu /* tbf_mix_row.bus: the row is in no bus */
+typedef struct tbf_mix_row {
+	uint32_t bus;            /* TBF_MIX_NONE, or < n_buses */
+	float    ll, lr, rl, rr; /* finite: L -> busL, R -> busL, L -> busR, R -> busR */
+} tbf_mix_row;
+typedef struct tbf_mix_out {
+	float*   L;      /* n_buses rows, bus b from b * stride floats: device memory in the *_device calls and */
+	float*   R;      /* tbf_mix_device (4-byte aligned), host memory in the host calls */
+	uint64_t stride; /* floats between rows, >= frames */
+} tbf_mix_out;
+/* The stage alone: n_rows rows of d_L / d_R (device memory; any 4-byte-aligned pointers and odd
+ * strides, as tbf_render_device delivers them) into out->L / out->R on `stream` (NULL: the
+ * engine's own), ordered as tbf_render_device: the planes must be complete where `stream` reaches
+ * the call, the buses are complete when it has passed it.  Nothing outside [0, frames) of an
+ * output row is written.  n_rows need not be the instance count.  rows and counts are host
+ * memory: the call turns them into a bus-sorted list and waits for its upload before it returns.
+ * n_buses has no cap beyond memory.  An engine's mix calls share staging: calls on different
+ * streams are the caller's to order. */
+int tbf_mix_device (tbf_engine* e, uint32_t n_rows, const float* d_L, const float* d_R, uint64_t in_stride, uint32_t frames,
+                    const uint32_t* counts, const tbf_mix_row* rows, uint32_t n_buses, const tbf_mix_out* out, void* stream);
+/* One render (tbf_render_mix* for TBF_CHAIN_FULL, TBF_CHAIN_TONEGEN and the tap chains) or
+ * effects-only pass (tbf_process_mix* for the TBF_CHAIN_FX* chains) delivered as n_buses rows of
+ * nblocks * 128 frames, row r of `rows` = instance r: host buffers and synchronous, or device
+ * memory on `stream` with events, as the PCM calls.  The L / R behind them are
+ * tbf_render_device's, bit for bit.  The engine renders them into scratch of its own, at most
+ * 8 B per instance and sample of 256 blocks; a longer call is cut into pieces, each with its own
+ * events, each mixed at its frame offset, and delivers the bits of one call.  The host forms mix
+ * into device staging and copy the buses out once per piece; their rows and out are host memory.
+ * -12 before anything renders when the device cannot hold the scratch.
+ * -22, with a tbf_last_error that names the argument: a NULL pointer, n_buses == 0 while a row
+ * names a bus, a bus index >= n_buses, a non-finite coefficient of a row in a bus, a stride
+ * smaller than the row, a misaligned device pointer, counts[r] > frames, any overlap among the
+ * input rows, the two output planes and the effects-only input (each taken as one range from its
+ * first row's first frame to its last row's last), the wrong family for the chain, events out of
+ * order; -19 on a host-only engine.  Validation comes first: a refused call renders nothing,
+ * steps no control and writes nothing. */
+int tbf_render_mix (tbf_engine* e, uint32_t nblocks, const tbf_mix_row* rows, uint32_t n_buses, const tbf_mix_out* out);
+int tbf_render_mix_device (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, const tbf_mix_row* rows,
+                           uint32_t n_buses, const tbf_mix_out* out, void* stream);
+int tbf_process_mix (tbf_engine* e, uint32_t nblocks, const float* in, uint64_t in_stride, const tbf_mix_row* rows,
+                     uint32_t n_buses, const tbf_mix_out* out);
+int tbf_process_mix_device (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, const float* d_in,
+                            uint64_t in_stride, const tbf_mix_row* rows, uint32_t n_buses, const tbf_mix_out* out, void* stream);
+/* test hook: the host restatement of the whole definition on host arrays, from the header the
+ * kernel is built from (csrc/tbf_mix.h) with libm's fmaf: the arguments of tbf_mix_device, all
+ * host memory.  Needs no engine and no device.  -22 as above (no alignment is asked for). */
+int tbf_debug_mix_ref (uint32_t n_rows, const float* L, const float* R, uint64_t in_stride, uint32_t frames,
+                       const uint32_t* counts, const tbf_mix_row* rows, uint32_t n_buses, const tbf_mix_out* out);
+/* test hook: how k_mix lays a call of `frames` frames and n_buses buses out: the frames a lane
+ * carries (4, 2 or 1: fewer when the call would otherwise fill too few waves), the frames of a
+ * workgroup's tile, and the most buses of one launch (a call with more is launched in slices).
+ * No layout changes a bit.  Any pointer may be NULL. */
+int tbf_debug_mix_grid (uint32_t frames, uint32_t n_buses, uint32_t* frames_per_lane, uint32_t* tile_frames,
+                        uint32_t* slice_buses);
+/* k_mix's own time, as tbf_debug_cabinet_time */
+int tbf_debug_mix_time (tbf_engine* e, int32_t enable, double* ms, uint64_t* launches);
+
 int tbf_synchronize (tbf_engine* e);
 /* Which exact-but-slow paths the kernels took since the engine's first render (cumulative,
  * informational; the results are bit-identical either way).  Waits for the engine's

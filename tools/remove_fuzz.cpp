@@ -11,6 +11,10 @@
  * array left uncompacted, or a removed instance's state left behind, shows as a difference,
  * an index past an array as a sanitizer report.  Both engines are rebuilt every few hundred
  * calls so that the shadow stays small.
+ * Every few dozen calls the mixdown stage's host code runs too (mix): the host restatement
+ * tbf_debug_mix_ref over random rows, buses and counts in heap arrays of the exact size, so that a
+ * frame or a list entry past its end is a sanitizer report, and tbf_render_mix on A's instances,
+ * which checks its rows and builds its list before it answers -19.
  *
  * Build and run: `make -C tunebfree_amd remove_fuzz` (the host sources compiled with
  * -fsanitize=address,undefined, linked with the kernels' objects as built), then
@@ -77,6 +81,56 @@ static void step (Pair& p, uint32_t i)
 	CHECK (memcmp (pa.data (), pb.data (), (size_t)na * 9 * sizeof (float)) == 0);
 }
 
+/* the mixdown stage's host code over exact-sized arrays; every sample against a plain loop */
+static void mix (tbf_engine* e, std::mt19937& rng)
+{
+	auto           pick = [&] (uint32_t n) { return (uint32_t)(rng () % n); };
+	const uint32_t n = pick (12), nb = pick (5), frames = 1 + pick (40), stride = frames + pick (3);
+	const size_t   len = n ? (size_t)(n - 1) * stride + frames : 0; /* to the last row's last frame, no further */
+	std::vector<float>       L (len), R (len);
+	std::vector<uint32_t>    cnt (n);
+	std::vector<tbf_mix_row> rows (n);
+	for (float& v : L)
+		v = (float)pick (2001) * 1e-3f - 1.0f;
+	for (float& v : R)
+		v = (float)pick (2001) * 1e-3f - 1.0f;
+	for (uint32_t r = 0; r < n; r++) {
+		rows[r] = {nb && pick (4) ? pick (nb) : TBF_MIX_NONE, (float)pick (5) * 0.5f - 1.0f, (float)pick (3) * 0.25f,
+		           -(float)pick (3) * 0.25f, (float)pick (5) * 0.5f - 1.0f};
+		cnt[r]  = pick (frames + 1);
+	}
+	const uint32_t     ostride = frames + pick (2);
+	std::vector<float> oL ((size_t)nb * ostride + 1, 9.0f), oR ((size_t)nb * ostride + 1, 9.0f);
+	const tbf_mix_out  out = {oL.data (), oR.data (), ostride};
+	const bool         full = pick (3) == 0;
+	CHECK (tbf_debug_mix_ref (n, L.data (), R.data (), stride, frames, full ? nullptr : cnt.data (), rows.data (), nb, &out) == 0);
+	for (uint32_t b = 0; b < nb; b++)
+		for (uint32_t j = 0; j < ostride; j++) {
+			float al = 0.0f, ar = 0.0f;
+			for (uint32_t r = 0; r < n && j < frames; r++)
+				if (rows[r].bus == b && j < (full ? frames : cnt[r])) {
+					const float xl = L[(size_t)r * stride + j], xr = R[(size_t)r * stride + j];
+					al = __builtin_fmaf (rows[r].lr, xr, __builtin_fmaf (rows[r].ll, xl, al));
+					ar = __builtin_fmaf (rows[r].rr, xr, __builtin_fmaf (rows[r].rl, xl, ar));
+				}
+			const float wl = j < frames ? al : 9.0f, wr = j < frames ? ar : 9.0f;
+			CHECK (memcmp (&oL[(size_t)b * ostride + j], &wl, 4) == 0 && memcmp (&oR[(size_t)b * ostride + j], &wr, 4) == 0);
+		}
+	CHECK (oL.back () == 9.0f && oR.back () == 9.0f);
+	/* on the engine's instances: the rows' checks and the list, then -19 (a host-only engine) */
+	const uint32_t           ni = tbf_instance_count (e), buses = 1 + pick (3);
+	std::vector<tbf_mix_row> ir (ni);
+	for (uint32_t r = 0; r < ni; r++)
+		ir[r] = {pick (3) ? pick (buses) : TBF_MIX_NONE, 1.0f, 0.0f, 0.0f, 1.0f};
+	std::vector<float> hl ((size_t)buses * 128), hr ((size_t)buses * 128);
+	const tbf_mix_out  ho = {hl.data (), hr.data (), 128};
+	CHECK (tbf_render_mix (e, 1, ir.data (), buses, &ho) == -19);
+	if (ni) {
+		ir[pick (ni)].bus = buses;
+		CHECK (tbf_render_mix (e, 1, ir.data (), buses, &ho) == -22);
+	}
+}
+
 int main (int argc, char** argv)
 {
 	const int      calls = argc > 1 ? atoi (argv[1]) : 4000;
@@ -99,6 +153,8 @@ int main (int argc, char** argv)
 			p.twin.clear ();
 			blobs.clear ();
 		}
+		if (g_call % 37 == 0)
+			mix (p.a, rng);
 		const uint32_t n  = tbf_instance_count (p.a);
 		uint32_t       op = pick (100);
 		CHECK (n == p.twin.size ());

@@ -26,6 +26,7 @@
 #include "../../include/tbf.h"
 #include "tbf_cabinet.h"
 #include "tbf_host.h"
+#include "tbf_mix.h"
 #include "tbf_pcm.h"
 #include "tbf_resample.h"
 #include "tbf_types.h"
@@ -486,6 +487,16 @@ struct tbf_engine {
 		bool                  timeOn = false; /* tbf_debug_pcm_time: an event pair around every launch */
 		std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
 	} pcm;
+	/* the mixdown stage (csrc/tbf_mix.cpp): no instance state, only the calls' staging -- the
+	 * bus-sorted member list and the host-buffer calls' bus planes */
+	struct Mix {
+		DevBuf<uint32_t>       busOff;
+		DevBuf<tbf_mix_member> members;
+		DevBuf<float>          hostOut;
+		uint64_t               launches = 0;
+		bool                   timeOn = false; /* tbf_debug_mix_time: an event pair around every launch */
+		std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
+	} mix;
 	bool                                    rvLdsOn  = true;  /* k_rv_core_lds when the rings fit (TBF_RV_LDS=0: k_rv_core) */
 	bool                                    rvLdsFit = false; /* the instances' rings fit k_rv_core_lds */
 	uint32_t                                rvGrid   = 0;     /* k_rv_core_lds persistent workgroups (TBF_RV_PERSIST=0: one per pair) */

@@ -7,6 +7,8 @@ from pathlib import Path
 
 import numpy as np
 
+from .params import MIX_ROW_DTYPE
+
 # TBF_LIB overrides the library path (build variants for A/B measurements)
 LIB_PATH = Path(os.environ.get("TBF_LIB", Path(__file__).resolve().parent / "libtbf.so"))
 
@@ -59,6 +61,21 @@ PCM_S16, PCM_S24_3LE, PCM_F32 = 0, 1, 2
 PCM_DITHER = 1
 PCM_FRAME_BYTES = (4, 6, 8)
 METER_DTYPE = np.dtype([("peakL", "<f4"), ("peakR", "<f4"), ("clipL", "<u4"), ("clipR", "<u4")])
+
+
+class MixRow(C.Structure):
+    """tbf_mix_row: the row's bus (MIX_NONE: none) and its four coefficients L -> busL, R -> busL,
+    L -> busR, R -> busR; arrays of them are MIX_ROW_DTYPE records (params.mix_rows builds them)"""
+    _fields_ = [("bus", C.c_uint32), ("ll", C.c_float), ("lr", C.c_float), ("rl", C.c_float), ("rr", C.c_float)]
+
+
+class MixOut(C.Structure):
+    """tbf_mix_out: the two bus planes and their common stride (in floats)"""
+    _fields_ = [("L", C.c_void_p), ("R", C.c_void_p), ("stride", C.c_uint64)]
+
+
+# tbf_mix_row.bus of a row in no bus (include/tbf.h TBF_MIX_NONE)
+MIX_NONE = 0xFFFFFFFF
 
 
 # tbf_engine_config.debug_flags / tbf_error_flags bits (include/tbf.h)
@@ -136,6 +153,15 @@ SIGNATURES = {
     "tbf_process_pcm": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(PcmOut)]),
     "tbf_process_pcm_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
                                          C.POINTER(PcmOut), C.c_void_p]),
+    "tbf_mix_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                                 C.c_void_p, C.c_uint32, C.POINTER(MixOut), C.c_void_p]),
+    "tbf_render_mix": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(MixOut)]),
+    "tbf_render_mix_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                        C.POINTER(MixOut), C.c_void_p]),
+    "tbf_process_mix": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                                  C.POINTER(MixOut)]),
+    "tbf_process_mix_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
+                                         C.c_void_p, C.c_uint32, C.POINTER(MixOut), C.c_void_p]),
 }
 
 # tbf_engine_config.chain_mode of the effects-only chains (include/tbf.h TBF_CHAIN_FX*)
@@ -816,6 +842,119 @@ class Engine:
         _check(self._lib.tbf_pcm_convert_device(
             self._h, int(n_rows), C.c_void_p(int(L_ptr)), C.c_void_p(int(R_ptr)), int(in_stride), int(frames),
             None if c is None else c.ctypes.data, C.byref(po), None if stream is None else C.c_void_p(int(stream))))
+
+    @staticmethod
+    def _mix_rows(rows, n=None):
+        """the rows as a contiguous MIX_ROW_DTYPE array (keep it alive over the call)"""
+        r = np.ascontiguousarray(rows, dtype=MIX_ROW_DTYPE).reshape(-1)
+        if n is not None and len(r) != n:
+            raise ValueError(f"{len(r)} mix rows for {n} rows")
+        return r
+
+    @staticmethod
+    def mix_ref(L, R, rows, n_buses, counts=None):
+        """tbf_debug_mix_ref: the host restatement of the mixdown stage on host arrays (no device
+        needed): L, R [n_rows, frames] float32 (the same array twice: mono planes), rows
+        MIX_ROW_DTYPE [n_rows], counts None or [n_rows]; returns (busL, busR) [n_buses, frames]."""
+        f = load_library().tbf_debug_mix_ref
+        f.restype = C.c_int
+        f.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                      C.POINTER(MixOut)]
+        mono = L is R
+        L = np.ascontiguousarray(L, dtype=np.float32)
+        R = L if mono else np.ascontiguousarray(R, dtype=np.float32)
+        if L.ndim != 2 or L.shape != R.shape:
+            raise ValueError(f"planes of shape {L.shape} and {R.shape}: want two of [n_rows, frames]")
+        n, frames = L.shape
+        r = Engine._mix_rows(rows, n)
+        c = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+        oL, oR = np.full((int(n_buses), frames), np.nan, np.float32), np.full((int(n_buses), frames), np.nan, np.float32)
+        mo = MixOut(oL.ctypes.data, oR.ctypes.data, frames)
+        _check(f(n, L.ctypes.data, R.ctypes.data, frames, frames, None if c is None else c.ctypes.data,
+                 r.ctypes.data if n else None, int(n_buses), C.byref(mo)))
+        return oL, oR
+
+    @staticmethod
+    def mix_grid(frames, n_buses):
+        """tbf_debug_mix_grid: (frames per lane, frames per workgroup tile, buses per launch) of a
+        k_mix call of `frames` frames and n_buses buses"""
+        f = load_library().tbf_debug_mix_grid
+        f.restype, f.argtypes = C.c_int, [C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p]
+        g, t, sl = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(f(int(frames), int(n_buses), C.byref(g), C.byref(t), C.byref(sl)))
+        return g.value, t.value, sl.value
+
+    def mix_time(self, enable=None):
+        """tbf_debug_mix_time: enable True / False switches the event pair around every k_mix
+        launch on / off; None returns (milliseconds, launches) since the last query."""
+        f = self._lib.tbf_debug_mix_time
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_uint64)]
+        if enable is not None:
+            _check(f(self._h, 1 if enable else -1, None, None))
+            return None
+        ms, n = C.c_double(), C.c_uint64()
+        _check(f(self._h, 0, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def mix_device(self, n_rows, L_ptr, R_ptr, in_stride, frames, rows, n_buses, outL_ptr, outR_ptr, out_stride, counts=None,
+                   stream=None):
+        """tbf_mix_device: the mixdown stage alone over any two device planes of n_rows rows (row r
+        at r * in_stride floats; L_ptr == R_ptr: mono): rows MIX_ROW_DTYPE [n_rows] (params.mix_rows),
+        `frames` frames per row or counts[r] (host array) of them, into n_buses rows of `frames`
+        frames at outL_ptr / outR_ptr, out_stride floats apart."""
+        r = self._mix_rows(rows, int(n_rows))
+        c = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+        mo = MixOut(int(outL_ptr), int(outR_ptr), int(out_stride))
+        _check(self._lib.tbf_mix_device(
+            self._h, int(n_rows), C.c_void_p(int(L_ptr)), C.c_void_p(int(R_ptr)), int(in_stride), int(frames),
+            None if c is None else c.ctypes.data, r.ctypes.data if len(r) else None, int(n_buses), C.byref(mo),
+            None if stream is None else C.c_void_p(int(stream))))
+
+    def _mix_host(self, nblocks, rows, n_buses, call):
+        r = self._mix_rows(rows, self.n_instances)
+        L, R = np.zeros((int(n_buses), nblocks * 128), np.float32), np.zeros((int(n_buses), nblocks * 128), np.float32)
+        mo = MixOut(L.ctypes.data, R.ctypes.data, nblocks * 128)
+        _check(call(r.ctypes.data if len(r) else None, C.byref(mo)))
+        return L, R
+
+    def render_mix(self, nblocks, rows, n_buses):
+        """tbf_render_mix: one synchronous render summed into n_buses stereo buses: rows
+        MIX_ROW_DTYPE [n_instances] (params.mix_rows), row r = instance r; returns (L, R), each
+        [n_buses, nblocks*128]."""
+        return self._mix_host(nblocks, rows, n_buses, lambda r, mo: self._lib.tbf_render_mix(
+            self._h, int(nblocks), r, int(n_buses), mo))
+
+    def process_mix(self, x, rows, n_buses):
+        """tbf_process_mix: render_mix for an effects-only engine's input x [n_instances, nblocks*128]."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n = self.n_instances
+        if x.ndim != 2 or x.shape[0] != n or x.shape[1] % 128:
+            raise ValueError(f"input shape {x.shape}: want ({n}, nblocks*128)")
+        nb = x.shape[1] // 128
+        return self._mix_host(nb, rows, n_buses, lambda r, mo: self._lib.tbf_process_mix(
+            self._h, nb, x.ctypes.data, x.shape[1], r, int(n_buses), mo))
+
+    def render_mix_device(self, nblocks, rows, n_buses, outL_ptr, outR_ptr, out_stride, events=(), stream=None):
+        """tbf_render_mix_device: enqueue a render summed into n_buses stereo buses in device
+        memory: bus b from outL_ptr / outR_ptr + b * out_stride floats, events as Engine.events."""
+        ev = np.ascontiguousarray(events, dtype=EVENT_DTYPE) if len(events) else np.zeros(0, EVENT_DTYPE)
+        r = self._mix_rows(rows, self.n_instances)
+        mo = MixOut(int(outL_ptr), int(outR_ptr), int(out_stride))
+        _check(self._lib.tbf_render_mix_device(
+            self._h, int(nblocks), ev.ctypes.data if len(ev) else None, len(ev), r.ctypes.data if len(r) else None,
+            int(n_buses), C.byref(mo), None if stream is None else C.c_void_p(int(stream))))
+
+    def process_mix_device(self, nblocks, in_ptr, in_stride, rows, n_buses, outL_ptr, outR_ptr, out_stride, events=(),
+                           stream=None):
+        """tbf_process_mix_device: render_mix_device for an effects-only engine's device-resident
+        input rows."""
+        ev = np.ascontiguousarray(events, dtype=EVENT_DTYPE) if len(events) else np.zeros(0, EVENT_DTYPE)
+        r = self._mix_rows(rows, self.n_instances)
+        mo = MixOut(int(outL_ptr), int(outR_ptr), int(out_stride))
+        _check(self._lib.tbf_process_mix_device(
+            self._h, int(nblocks), ev.ctypes.data if len(ev) else None, len(ev),
+            None if in_ptr is None else C.c_void_p(int(in_ptr)), int(in_stride), r.ctypes.data if len(r) else None,
+            int(n_buses), C.byref(mo), None if stream is None else C.c_void_p(int(stream))))
 
     def synchronize(self):
         _check(self._lib.tbf_synchronize(self._h))

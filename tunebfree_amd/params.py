@@ -1,5 +1,7 @@
 """Parameter ids of include/tbf.h: the CLAP ids of src/clap.cpp:31-48 plus the
 setters the LV2/JACK hosts reach through MIDI CCs."""
+import numpy as np
+
 DRAWBAR_MIN, DRAWBAR_MAX = 0, 8
 VIBRATO, VIBRATO_TYPE = 9, 10
 DRUM, HORN = 11, 12
@@ -26,3 +28,27 @@ CAB_MAX_TAPS = 8192
 PCM_S16, PCM_S24_3LE, PCM_F32 = 0, 1, 2
 PCM_FRAME_BYTES = (4, 6, 8)
 PCM_DITHER = 1
+
+# the mixdown stage (Engine.mix_device, .render_mix, .process_mix): tbf_mix_row.bus of a row that is
+# in no bus (TBF_MIX_NONE), and the rows as a numpy record (20 B, as the C struct)
+MIX_NONE = 0xFFFFFFFF
+MIX_ROW_DTYPE = np.dtype([("bus", "<u4"), ("ll", "<f4"), ("lr", "<f4"), ("rl", "<f4"), ("rr", "<f4")])
+
+
+def mix_rows(bus, gain=1.0, pan=0.0):
+    """tbf_mix_row records for Engine.mix_device / .render_mix / .process_mix: row r goes to bus
+    bus[r] (MIX_NONE: to none) at gain[r] and pan[r] in [-1, 1] (scalars apply to every row), by a
+    constant-power law with unity at centre: ll = sqrt(2) g cos((pan + 1) pi / 4),
+    rr = sqrt(2) g sin((pan + 1) pi / 4), lr = rl = 0, computed in float64 and rounded to float32.
+    A convenience: the ABI knows only the four numbers, which a caller may set as it likes."""
+    bus = np.atleast_1d(np.asarray(bus, dtype=np.int64))
+    g = np.broadcast_to(np.asarray(gain, dtype=np.float64), bus.shape)
+    p = np.broadcast_to(np.asarray(pan, dtype=np.float64), bus.shape)
+    if np.any(np.abs(p) > 1.0):
+        raise ValueError("pan outside [-1, 1]")
+    a = (p + 1.0) * (np.pi / 4.0)
+    rows = np.zeros(bus.shape, MIX_ROW_DTYPE)
+    rows["bus"] = np.where(bus < 0, MIX_NONE, bus).astype(np.uint32)
+    rows["ll"] = (np.sqrt(2.0) * g * np.cos(a)).astype(np.float32)
+    rows["rr"] = (np.sqrt(2.0) * g * np.sin(a)).astype(np.float32)
+    return rows
