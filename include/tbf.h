@@ -703,6 +703,102 @@ int tbf_debug_mix_grid (uint32_t frames, uint32_t n_buses, uint32_t* frames_per_
 /* k_mix's own time, as tbf_debug_cabinet_time */
 int tbf_debug_mix_time (tbf_engine* e, int32_t enable, double* ms, uint64_t* launches);
 
+/* ---- Bus limiter: look-ahead peak limiting of planes, on the device ----
+ * A stage behind any two float32 device planes: the buses of tbf_mix_device in front of
+ * tbf_pcm_convert_device, or an instance's own L / R.  A feed-forward peak limiter with
+ * look-ahead, hold and a linear release.  Like the cabinet, the rate converter, the PCM stage and
+ * the mixdown it is specified here, not restated from the reference, which has no limiter
+ * (DESIGN.md section 7), and it is defined to the bit, so a limited mix is as reproducible at
+ * every cut into calls as the planes behind it.
+ * Parameters per limiter, fixed at creation: the ceiling c (float32, finite, 0 < c), ahead = A (a
+ * power of two, 2 <= A <= TBF_LIMIT_MAX_AHEAD), hold = H (0 <= H <= TBF_LIMIT_MAX_HOLD).
+ * Derived: W = A + H, the latency D = A - 1 frames, the history Hn = A + W - 2 frames per row and
+ * channel.
+ * For a row with input frames xL[n], xR[n], n counted from the row's first frame since creation
+ * or reset, all frames at n < 0 being +0.0f:
+ *     p[n]  = 0;  if (fabsf (xL[n]) > p) p = fabsf (xL[n]);  if (fabsf (xR[n]) > p) p = fabsf (xR[n])
+ *                                                          (a NaN sample is skipped)
+ *     t[n]  = p[n] > c ? c / p[n] : 1.0f                    one correctly rounded float32 division
+ *     m[n]  = min (t[n-W+1], ..., t[n])                     exact, any order
+ *     acc   = +0.0f;  for j = n-A+1 .. n ascending: acc = acc + m[j]       one float32 add per line
+ *     g[n]  = acc * (1.0f / A)                              exact: A is a power of two
+ *     yL[n] = g[n] * xL[n-D];  if (yL > c) yL = c;  if (yL < -c) yL = -c;  likewise yR  (NaN stays NaN)
+ * Denormals are kept.  NaN and Inf are literal: an Inf gives t = 0 and 0 * Inf = NaN.  The order
+ * of the sum is part of the definition: the kernel computes m in any order it likes, but it never
+ * re-associates the sum and keeps no running sum.  Because A is a power of two, a row that never
+ * exceeds c has g == 1.0f exactly and comes out as its own bits, D frames late, -0.0f and
+ * subnormals unchanged.  Every m[j] of the sum covers t[n-D], so g[n] <= t[n-D] up to rounding,
+ * and the final clamp makes |y| <= c unconditional.  After a peak the gain stays down for H frames
+ * and returns to 1 linearly over A.
+ * State: per row and channel the last Hn input frames, zero at creation and at reset.  It belongs
+ * to the limiter object, not to an instance: rows are whatever the caller feeds (buses, instances,
+ * resampled rows); tbf_instances_* do not know the limiter and tbf_debug_device_bytes does not
+ * count its memory.  Row r of a call consumes counts[r] <= frames frames and yields as many;
+ * with counts[r] == 0 its state is unchanged.  Nothing depends on how a row's frames are cut into
+ * calls.
+ * Meters, optional, one per row, overwritten by each call, exact: min_gain = the least g over the
+ * row's frames of this call (1.0f for an empty row), reduced = the frames with g < 1.0f, clamped =
+ * the samples the final clamp replaced, L and R counted separately. */
+#define TBF_LIMIT_MAX_AHEAD 512u
+#define TBF_LIMIT_MAX_HOLD 4096u
+typedef struct tbf_limiter tbf_limiter;
+typedef struct tbf_limiter_config {
+	float    ceiling; /* c */
+	uint32_t ahead;   /* A */
+	uint32_t hold;    /* H */
+} tbf_limiter_config;
+typedef struct tbf_limit_meter {
+	float    min_gain;
+	uint32_t reduced, clamped;
+} tbf_limit_meter;
+typedef struct tbf_limit_out {
+	float*           L;      /* n_rows rows, row r from r * stride floats: device memory, 4-byte aligned */
+	float*           R;
+	uint64_t         stride; /* floats between rows, >= frames */
+	tbf_limit_meter* meters; /* optional, one per row: device memory */
+} tbf_limit_out;
+/* A limiter of n_rows rows on e's device; e owns it: tbf_engine_destroy releases the ones still
+ * alive.  -22: a NULL pointer, a ceiling that is not finite or not positive, ahead no power of two
+ * or out of range, hold out of range, n_rows == 0.  A host-only engine validates, then returns
+ * -19.  -12 when the device cannot hold the state (16 B x Hn per row). */
+int tbf_limiter_create (tbf_engine* e, uint32_t n_rows, const tbf_limiter_config* cfg, tbf_limiter** out);
+int tbf_limiter_destroy (tbf_limiter* lim);
+/* The rows `rows` (host memory, n of them; NULL: all rows, n ignored) start anew, ordered on
+ * `stream` (NULL: the engine's own).  -22: a row index >= n_rows. */
+int tbf_limiter_reset (tbf_limiter* lim, uint32_t n, const uint32_t* rows, void* stream);
+/* D, the frames by which the output trails the input */
+int tbf_limiter_latency (const tbf_limiter* lim, uint32_t* frames);
+/* One call: the limiter's n_rows rows of d_L / d_R (device memory, row r at r * in_stride floats;
+ * any 4-byte-aligned pointers and odd strides, as tbf_render_device delivers them; d_L == d_R is
+ * allowed: both outputs are written and are equal) into out->L / out->R on `stream` (NULL: the
+ * engine's own), ordered as tbf_render_device: the planes must be complete where `stream` reaches
+ * the call, the outputs, meters and state are complete when it has passed it.  Row r takes
+ * counts[r] frames (counts: host memory, uploaded before the call returns), or `frames` when
+ * counts is NULL.  Nothing outside [0, counts[r]) of an output row is written, and nothing of the
+ * meters beyond n_rows.  Calls on one limiter are the caller's to order.
+ * -22, with a tbf_last_error that names the argument: a NULL pointer, a stride smaller than the
+ * row, a misaligned device pointer, counts[r] > frames, any overlap among the input, the two
+ * outputs and the meters (each taken as one range from its first row's first frame to its last
+ * row's last; in-place use is refused, because a tile reads its neighbours' input).  Validation
+ * comes first: a refused call writes nothing and moves no state. */
+int tbf_limit_device (tbf_limiter* lim, const float* d_L, const float* d_R, uint64_t in_stride, uint32_t frames,
+                      const uint32_t* counts, const tbf_limit_out* out, void* stream);
+/* test hook: the host restatement of the definition on one row, from the header the kernel is
+ * built from (csrc/tbf_limit.h): n frames of L / R (L == R allowed) behind the history histL /
+ * histR (Hn floats each, oldest first, read and then replaced by the row's next history) into
+ * outL / outR and (optional) one meter.  Needs no engine and no device.  -22 as above. */
+int tbf_debug_limit_ref (const tbf_limiter_config* cfg, const float* L, const float* R, uint64_t n, float* histL, float* histR,
+                         float* outL, float* outR, tbf_limit_meter* meter);
+/* test hook: how k_limit lays a configuration out: the frames a lane carries at a time, the frames
+ * of a workgroup's tile (a function of the configuration alone), the history Hn and the
+ * workgroup's LDS bytes.  No layout changes a bit.  Any out pointer may be NULL.  -22 as
+ * tbf_limiter_create. */
+int tbf_debug_limit_grid (const tbf_limiter_config* cfg, uint32_t* frames_per_lane, uint32_t* tile_frames, uint32_t* history,
+                          uint32_t* lds_bytes);
+/* k_limit's own time (with its meter preset, when a call has meters), as tbf_debug_cabinet_time:
+ * one launch set per call that took frames */
+int tbf_debug_limit_time (tbf_limiter* lim, int32_t enable, double* ms, uint64_t* launches);
+
 int tbf_synchronize (tbf_engine* e);
 /* Which exact-but-slow paths the kernels took since the engine's first render (cumulative,
  * informational; the results are bit-identical either way).  Waits for the engine's

@@ -26,6 +26,7 @@
 #include "../../include/tbf.h"
 #include "tbf_cabinet.h"
 #include "tbf_host.h"
+#include "tbf_limit.h"
 #include "tbf_mix.h"
 #include "tbf_pcm.h"
 #include "tbf_resample.h"
@@ -284,6 +285,29 @@ using namespace tbf; /* private header: the engine's own translation units only 
 
 #define TBF_NSTAGES 6 /* k_tonegen, k_mixpre, k_rv_pre, k_rv_core, k_rv_post, k_whirl */
 
+/* A bus limiter (tbf_limiter_create, csrc/tbf_limit.cpp): its rows' state and the staging of a
+ * call's counts.  The state is input only: per row two history buffers of 2 x Hn floats (L, R),
+ * of which rows[r].side is the live one; a call reads it, writes the other and flips the side of
+ * every row that took frames (k_limit, csrc/tbf_limit.hip). */
+struct tbf_limiter {
+	tbf_engine*                eng = nullptr;
+	tbf_limiter_config         cfg = {0.0f, 0u, 0u};
+	uint32_t                   nRows = 0, Hn = 0;
+	DevBuf<float>              hist;  /* [row][side][channel][Hn] */
+	DevBuf<tbf_limit_row>      drows; /* the call's rows on the device */
+	std::vector<tbf_limit_row> rows;  /* .side persists, .count is the call's */
+	uint64_t                   launches = 0;
+	bool                       timeOn = false; /* tbf_debug_limit_time: an event pair around every launch set */
+	std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
+	~tbf_limiter ()
+	{
+		for (auto& p : tev) {
+			(void)hipEventDestroy (p.first);
+			(void)hipEventDestroy (p.second);
+		}
+	}
+};
+
 struct tbf_engine {
 	tbf_engine_config                       cfg;
 	Config                                  conf; /* cfg keys (tbf_config_set) for tables built from now on */
@@ -523,6 +547,9 @@ struct tbf_engine {
 	uint32_t                                boffset = TBF_BLK; /* read position in the FIFO ... */
 	uint32_t                                fifoLen = TBF_BLK; /* ... of fifoLen samples per instance ... */
 	uint32_t                                fifoN   = 0;       /* ... for fifoN instances */
+	/* the bus limiters still alive (csrc/tbf_limit.cpp); they go with the engine.  The last member,
+	 * so that nothing the render path reads has moved. */
+	std::vector<std::unique_ptr<tbf_limiter>> limiters;
 };
 
 namespace tbf {

@@ -1,0 +1,339 @@
+/*
+ * tbf_limit.cpp -- the host side of the bus limiter: the limiter objects an engine owns,
+ * tbf_limit_device, reset, and the tbf_debug_limit* hooks.
+ *
+ * A post-stage on two float32 device planes (include/tbf.h): k_limit
+ * (csrc/tbf_limit.hip) limits each row's peaks to a ceiling with look-ahead, hold and a linear
+ * release.  The state, the last Hn input frames per row and channel, belongs to the limiter, not
+ * to an instance: the render path, clone, save, load and remove do not know it.  A row keeps two
+ * history buffers; a call reads the live one and writes the other, and the host flips the side of
+ * every row that took frames once the launch is issued (tbf_limiter.rows), so no tile of a call
+ * reads what another one writes.  Everything is checked before anything is staged or launched: a
+ * refused call writes nothing and moves no state.  tbf_debug_limit_ref is the definition on the
+ * host, one row at a time, from the functions of csrc/tbf_limit.h that the kernel runs.
+ */
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "../../include/tbf.h"
+#include "tbf_engine_impl.h"
+#include "tbf_limit.h"
+
+extern "C" int tbf_launch_limit (const tbf_limit_launch* P, hipStream_t stream);
+
+using namespace tbf;
+
+#define HIPCHK(x)                                                                        \
+	do {                                                                                 \
+		hipError_t _e = (x);                                                             \
+		if (_e != hipSuccess)                                                            \
+			return fail (-5, std::string (#x ": ") + hipGetErrorString (_e));           \
+	} while (0)
+
+namespace {
+
+/* [a, b) in bytes; empty ranges overlap nothing */
+struct Span {
+	uintptr_t a, b;
+};
+
+Span rowsSpan (const void* p, uint64_t rows, uint64_t strideBytes, uint64_t rowBytes)
+{
+	const uintptr_t a = (uintptr_t)p;
+	return {a, p && rows && rowBytes ? a + (uintptr_t)((rows - 1) * strideBytes + rowBytes) : a};
+}
+
+bool overlap (Span x, Span y) { return x.a < x.b && y.a < y.b && x.a < y.b && y.a < x.b; }
+
+int checkConfig (const tbf_limiter_config* cfg)
+{
+	if (!cfg)
+		return fail (-22, "limit: cfg is NULL");
+	if (!std::isfinite (cfg->ceiling) || !(cfg->ceiling > 0.0f))
+		return fail (-22, "limit: ceiling is not finite and positive");
+	if (cfg->ahead < 2u || cfg->ahead > TBF_LIMIT_MAX_AHEAD || (cfg->ahead & (cfg->ahead - 1u)))
+		return fail (-22, "limit: ahead " + std::to_string (cfg->ahead) + " is no power of two in [2, " +
+		                      std::to_string (TBF_LIMIT_MAX_AHEAD) + "]");
+	if (cfg->hold > TBF_LIMIT_MAX_HOLD)
+		return fail (-22, "limit: hold " + std::to_string (cfg->hold) + " above " + std::to_string (TBF_LIMIT_MAX_HOLD));
+	return 0;
+}
+
+/* the limiter's slot in its engine's list, or the list's end */
+std::vector<std::unique_ptr<tbf_limiter>>::iterator slotOf (tbf_limiter* lim)
+{
+	auto& v = lim->eng->limiters;
+	return std::find_if (v.begin (), v.end (), [lim] (const std::unique_ptr<tbf_limiter>& p) { return p.get () == lim; });
+}
+
+} // namespace
+
+extern "C" {
+
+int tbf_limiter_create (tbf_engine* e, uint32_t n_rows, const tbf_limiter_config* cfg, tbf_limiter** out)
+{
+	if (!e)
+		return fail (-22, "limit: engine is NULL");
+	if (!out)
+		return fail (-22, "limit: out is NULL");
+	if (int rc = checkConfig (cfg))
+		return rc;
+	if (n_rows == 0)
+		return fail (-22, "limit: n_rows is 0");
+	if (e->cfg.device < 0)
+		return fail (-19, "host-only engine (device -1) has no device to limit on");
+	HIPCHK (hipSetDevice (e->cfg.device));
+	std::unique_ptr<tbf_limiter> lim (new tbf_limiter ());
+	lim->eng   = e;
+	lim->cfg   = *cfg;
+	lim->nRows = n_rows;
+	lim->Hn    = limit_history (cfg->ahead, cfg->hold);
+	const size_t floats = (size_t)n_rows * 4u * lim->Hn;
+	if (lim->hist.ensure (floats) || lim->drows.ensure (n_rows)) {
+		(void)hipGetLastError ();
+		return fail (-12, "out of device memory (limiter state: 16 B per row and frame of history)");
+	}
+	HIPCHK (hipMemsetAsync (lim->hist.p, 0, floats * sizeof (float), e->stream));
+	HIPCHK (hipStreamSynchronize (e->stream));
+	lim->rows.assign (n_rows, tbf_limit_row{0u, 0u});
+	*out = lim.get ();
+	e->limiters.push_back (std::move (lim));
+	return 0;
+}
+
+int tbf_limiter_destroy (tbf_limiter* lim)
+{
+	if (!lim)
+		return 0;
+	auto it = slotOf (lim);
+	if (it == lim->eng->limiters.end ())
+		return fail (-22, "limit: not a limiter of its engine");
+	(void)hipSetDevice (lim->eng->cfg.device);
+	lim->eng->limiters.erase (it); /* hipFree waits for the work that still reads the state */
+	return 0;
+}
+
+int tbf_limiter_reset (tbf_limiter* lim, uint32_t n, const uint32_t* rows, void* stream)
+{
+	if (!lim)
+		return fail (-22, "limit: lim is NULL");
+	for (uint32_t k = 0; rows && k < n; k++)
+		if (rows[k] >= lim->nRows)
+			return fail (-22, "limit: rows[" + std::to_string (k) + "] " + std::to_string (rows[k]) + " is no row of n_rows " +
+			                      std::to_string (lim->nRows));
+	HIPCHK (hipSetDevice (lim->eng->cfg.device));
+	hipStream_t const s = stream ? (hipStream_t)stream : lim->eng->stream;
+	const size_t      per = (size_t)4u * lim->Hn; /* a row's floats: both sides, both channels */
+	if (!rows)
+		HIPCHK (hipMemsetAsync (lim->hist.p, 0, (size_t)lim->nRows * per * sizeof (float), s));
+	for (uint32_t k = 0; rows && k < n; k++)
+		HIPCHK (hipMemsetAsync (lim->hist.p + (size_t)rows[k] * per, 0, per * sizeof (float), s));
+	return 0;
+}
+
+int tbf_limiter_latency (const tbf_limiter* lim, uint32_t* frames)
+{
+	if (!lim)
+		return fail (-22, "limit: lim is NULL");
+	if (!frames)
+		return fail (-22, "limit: frames is NULL");
+	*frames = lim->cfg.ahead - 1u;
+	return 0;
+}
+
+int tbf_limit_device (tbf_limiter* lim, const float* d_L, const float* d_R, uint64_t in_stride, uint32_t frames,
+                      const uint32_t* counts, const tbf_limit_out* out, void* stream)
+{
+	if (!lim)
+		return fail (-22, "limit: lim is NULL");
+	if (!d_L || !d_R)
+		return fail (-22, std::string ("limit: ") + (d_L ? "d_R" : "d_L") + " is NULL");
+	if (!out)
+		return fail (-22, "limit: out is NULL");
+	if (!out->L || !out->R)
+		return fail (-22, std::string ("limit: ") + (out->L ? "out->R" : "out->L") + " is NULL");
+	if (in_stride < frames)
+		return fail (-22, "limit: in_stride smaller than frames");
+	if (out->stride < frames)
+		return fail (-22, "limit: out stride smaller than frames");
+	if (((uintptr_t)d_L | (uintptr_t)d_R | (uintptr_t)out->L | (uintptr_t)out->R | (uintptr_t)out->meters) & 3u)
+		return fail (-22, "limit: device pointer not 4-byte aligned");
+	const uint32_t n = lim->nRows;
+	uint32_t       most = counts ? 0u : frames;
+	for (uint32_t r = 0; counts && r < n; r++) {
+		if (counts[r] > frames)
+			return fail (-22, "limit: counts[" + std::to_string (r) + "] above frames");
+		most = std::max (most, counts[r]);
+	}
+	{
+		const Span il = rowsSpan (d_L, n, in_stride * 4, (uint64_t)frames * 4), ir = rowsSpan (d_R, n, in_stride * 4, (uint64_t)frames * 4);
+		const Span ol = rowsSpan (out->L, n, out->stride * 4, (uint64_t)frames * 4);
+		const Span orr = rowsSpan (out->R, n, out->stride * 4, (uint64_t)frames * 4);
+		const Span mt = rowsSpan (out->meters, n, sizeof (tbf_limit_meter), sizeof (tbf_limit_meter));
+		if (overlap (il, ol) || overlap (il, orr) || overlap (ir, ol) || overlap (ir, orr) || overlap (ol, orr) || overlap (mt, il) ||
+		    overlap (mt, ir) || overlap (mt, ol) || overlap (mt, orr))
+			return fail (-22, "limit: input rows, output planes and meters overlap (in-place use is refused)");
+	}
+	tbf_engine* const e = lim->eng;
+	HIPCHK (hipSetDevice (e->cfg.device));
+	hipStream_t const s = stream ? (hipStream_t)stream : e->stream;
+	if (most == 0 && !out->meters)
+		return 0;
+	/* The rows' counts and sides on the device.  They are read from the limiter's host vector,
+	 * which the next call rewrites, so the stream is waited for. */
+	for (uint32_t r = 0; r < n; r++)
+		lim->rows[r].count = counts ? counts[r] : frames;
+	HIPCHK (hipMemcpyAsync (lim->drows.p, lim->rows.data (), (size_t)n * sizeof (tbf_limit_row), hipMemcpyHostToDevice, s));
+	HIPCHK (hipStreamSynchronize (s));
+
+	tbf_limit_launch P;
+	memset (&P, 0, sizeof (P));
+	P.in[0]     = d_L;
+	P.in[1]     = d_R;
+	P.inStride  = in_stride;
+	P.out[0]    = out->L;
+	P.out[1]    = out->R;
+	P.outStride = out->stride;
+	P.hist      = lim->hist.p;
+	P.rows      = lim->drows.p;
+	P.meters    = out->meters;
+	P.ceiling   = lim->cfg.ceiling;
+	P.ahead     = lim->cfg.ahead;
+	P.hold      = lim->cfg.hold;
+	P.maxCount  = most;
+
+	hipEvent_t t0 = nullptr, t1 = nullptr;
+	auto       drop = [&] () { /* a failed step between the events' creation and their hand-over to tev */
+		if (t0)
+			(void)hipEventDestroy (t0);
+		if (t1)
+			(void)hipEventDestroy (t1);
+	};
+	if (lim->timeOn) { /* tbf_debug_limit_time: the launch set between two events on its stream */
+		if (hipEventCreate (&t0) != hipSuccess || hipEventCreate (&t1) != hipSuccess || hipEventRecord (t0, s) != hipSuccess) {
+			drop ();
+			return fail (-5, std::string ("limit timing events: ") + hipGetErrorString (hipGetLastError ()));
+		}
+	}
+	for (uint32_t r0 = 0; r0 < n; r0 += TBF_LIMIT_MAX_ROWS) {
+		P.rowBase = r0;
+		P.nRows   = std::min (TBF_LIMIT_MAX_ROWS, n - r0);
+		if (tbf_launch_limit (&P, s)) {
+			drop ();
+			return fail (-5, std::string ("k_limit launch failed: ") + hipGetErrorString (hipGetLastError ()));
+		}
+	}
+	for (uint32_t r = 0; r < n; r++) /* the rows that took frames now live on their other side */
+		if (lim->rows[r].count)
+			lim->rows[r].side ^= 1u;
+	if (lim->timeOn) {
+		if (hipEventRecord (t1, s) != hipSuccess) {
+			drop ();
+			return fail (-5, std::string ("limit timing events: ") + hipGetErrorString (hipGetLastError ()));
+		}
+		lim->tev.push_back ({t0, t1});
+	}
+	lim->launches++;
+	return 0;
+}
+
+int tbf_debug_limit_ref (const tbf_limiter_config* cfg, const float* L, const float* R, uint64_t n, float* histL, float* histR,
+                         float* outL, float* outR, tbf_limit_meter* meter)
+{
+	if (int rc = checkConfig (cfg))
+		return rc;
+	if (!histL || !histR)
+		return fail (-22, std::string ("limit: ") + (histL ? "histR" : "histL") + " is NULL");
+	if (n && (!L || !R || !outL || !outR))
+		return fail (-22, "limit: a plane is NULL");
+	const float    c = cfg->ceiling;
+	const uint32_t A = cfg->ahead, W = A + cfg->hold, D = A - 1u, Hn = limit_history (A, cfg->hold);
+	const uint64_t N = (uint64_t)Hn + n;
+	/* the history and the call's frames as one row, frame i of it being frame i - Hn of the call */
+	std::vector<float> xl (N), xr (N), t (N), m (N);
+	memcpy (xl.data (), histL, (size_t)Hn * 4), memcpy (xr.data (), histR, (size_t)Hn * 4);
+	if (n)
+		memcpy (xl.data () + Hn, L, (size_t)n * 4), memcpy (xr.data () + Hn, R, (size_t)n * 4);
+	for (uint64_t i = 0; i < N; i++)
+		t[i] = limit_target (limit_peak (xl[i], xr[i]), c);
+	/* m[i] = min t[i - W + 1 .. i] (what lies before the row's start is never used): the indices
+	 * of a non-decreasing run of candidates, the front one the window's minimum */
+	{
+		std::vector<uint64_t> q (N);
+		uint64_t              head = 0, tail = 0;
+		for (uint64_t i = 0; i < N; i++) {
+			while (tail > head && !(t[q[tail - 1]] < t[i]))
+				tail--;
+			q[tail++] = i;
+			if (q[head] + W <= i)
+				head++;
+			m[i] = t[q[head]];
+		}
+	}
+	const float inv = 1.0f / (float)A;
+	float       minG = 1.0f;
+	uint32_t    reduced = 0, clamped = 0;
+	for (uint64_t j = 0; j < n; j++) {
+		const uint64_t i   = Hn + j;
+		float          acc = 0.0f;
+		for (uint64_t k = i - A + 1u; k <= i; k++)
+			acc = acc + m[k];
+		const float g = acc * inv;
+		outL[j]       = limit_out (g, xl[i - D], c, clamped);
+		outR[j]       = limit_out (g, xr[i - D], c, clamped);
+		if (g < minG)
+			minG = g;
+		reduced += g < 1.0f ? 1u : 0u;
+	}
+	memcpy (histL, xl.data () + n, (size_t)Hn * 4), memcpy (histR, xr.data () + n, (size_t)Hn * 4);
+	if (meter)
+		*meter = {minG, reduced, clamped};
+	return 0;
+}
+
+int tbf_debug_limit_grid (const tbf_limiter_config* cfg, uint32_t* frames_per_lane, uint32_t* tile_frames, uint32_t* history,
+                          uint32_t* lds_bytes)
+{
+	if (int rc = checkConfig (cfg))
+		return rc;
+	if (frames_per_lane)
+		*frames_per_lane = TBF_LIMIT_GROUP;
+	if (tile_frames)
+		*tile_frames = limit_tile (cfg->ahead, cfg->hold);
+	if (history)
+		*history = limit_history (cfg->ahead, cfg->hold);
+	if (lds_bytes)
+		*lds_bytes = 2u * limit_lds_floats (cfg->ahead, cfg->hold) * (uint32_t)sizeof (float);
+	return 0;
+}
+
+int tbf_debug_limit_time (tbf_limiter* lim, int32_t enable, double* ms, uint64_t* launches)
+{
+	if (!lim)
+		return fail (-22, "limit: lim is NULL");
+	if (enable) {
+		lim->timeOn = enable > 0;
+		return 0;
+	}
+	double sum = 0.0;
+	for (auto& p : lim->tev) {
+		float t = 0.f;
+		HIPCHK (hipEventSynchronize (p.second));
+		HIPCHK (hipEventElapsedTime (&t, p.first, p.second));
+		sum += t;
+		(void)hipEventDestroy (p.first);
+		(void)hipEventDestroy (p.second);
+	}
+	if (ms)
+		*ms = sum;
+	if (launches)
+		*launches = lim->tev.size ();
+	lim->tev.clear ();
+	return 0;
+}
+
+} /* extern "C" */

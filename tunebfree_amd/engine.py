@@ -7,7 +7,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .params import MIX_ROW_DTYPE
+from .params import LIMIT_METER_DTYPE, MIX_ROW_DTYPE
 
 # TBF_LIB overrides the library path (build variants for A/B measurements)
 LIB_PATH = Path(os.environ.get("TBF_LIB", Path(__file__).resolve().parent / "libtbf.so"))
@@ -76,6 +76,22 @@ class MixOut(C.Structure):
 
 # tbf_mix_row.bus of a row in no bus (include/tbf.h TBF_MIX_NONE)
 MIX_NONE = 0xFFFFFFFF
+
+
+class LimiterConfig(C.Structure):
+    """tbf_limiter_config: the ceiling, the look-ahead A (a power of two) and the hold, in frames"""
+    _fields_ = [("ceiling", C.c_float), ("ahead", C.c_uint32), ("hold", C.c_uint32)]
+
+
+class LimitMeter(C.Structure):
+    """tbf_limit_meter: the least gain, the frames below unity and the clamped samples of a row in
+    one call; arrays of them are LIMIT_METER_DTYPE records"""
+    _fields_ = [("min_gain", C.c_float), ("reduced", C.c_uint32), ("clamped", C.c_uint32)]
+
+
+class LimitOut(C.Structure):
+    """tbf_limit_out: the two output planes, their common stride (in floats) and the optional meters"""
+    _fields_ = [("L", C.c_void_p), ("R", C.c_void_p), ("stride", C.c_uint64), ("meters", C.c_void_p)]
 
 
 # tbf_engine_config.debug_flags / tbf_error_flags bits (include/tbf.h)
@@ -162,6 +178,12 @@ SIGNATURES = {
                                   C.POINTER(MixOut)]),
     "tbf_process_mix_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
                                          C.c_void_p, C.c_uint32, C.POINTER(MixOut), C.c_void_p]),
+    "tbf_limiter_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(LimiterConfig), C.POINTER(C.c_void_p)]),
+    "tbf_limiter_destroy": (C.c_int, [C.c_void_p]),
+    "tbf_limiter_reset": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tbf_limiter_latency": (C.c_int, [C.c_void_p, _u32p]),
+    "tbf_limit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                                   C.POINTER(LimitOut), C.c_void_p]),
 }
 
 # tbf_engine_config.chain_mode of the effects-only chains (include/tbf.h TBF_CHAIN_FX*)
@@ -195,6 +217,67 @@ def _check(rc):
     if rc < 0:
         raise TbfError(f"tbf error {rc}: {load_library().tbf_last_error().decode(errors='replace')}")
     return rc
+
+
+class Limiter:
+    """A bus limiter (Engine.limiter): n_rows rows of look-ahead peak limiting behind any two
+    device planes; its state belongs to it, not to the engine's instances."""
+
+    def __init__(self, eng, handle, n_rows, cfg):
+        self._eng, self._lib, self._h = eng, eng._lib, handle
+        self.n_rows, self.ceiling, self.ahead, self.hold = n_rows, cfg.ceiling, cfg.ahead, cfg.hold
+
+    @property
+    def latency(self):
+        """tbf_limiter_latency: the frames by which the output trails the input (ahead - 1)"""
+        d = C.c_uint32()
+        _check(self._lib.tbf_limiter_latency(self._h, C.byref(d)))
+        return d.value
+
+    @property
+    def history(self):
+        """the frames of input a row keeps per channel (2 * ahead + hold - 2)"""
+        return 2 * self.ahead + self.hold - 2
+
+    def process_device(self, L_ptr, R_ptr, in_stride, frames, outL_ptr, outR_ptr, out_stride, counts=None, meters_ptr=None,
+                       stream=None):
+        """tbf_limit_device: the limiter's rows of the device planes L_ptr / R_ptr (row r at
+        r * in_stride floats; L_ptr == R_ptr: mono), `frames` frames per row or counts[r] (host
+        array) of them, into outL_ptr / outR_ptr, out_stride floats apart; meters_ptr None or
+        device memory of one tbf_limit_meter (12 B) per row."""
+        c = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+        if c is not None and len(c) != self.n_rows:
+            raise ValueError(f"{len(c)} counts for {self.n_rows} rows")
+        lo = LimitOut(None if outL_ptr is None else int(outL_ptr), None if outR_ptr is None else int(outR_ptr),
+                      int(out_stride), None if meters_ptr is None else int(meters_ptr))
+        _check(self._lib.tbf_limit_device(
+            self._h, None if L_ptr is None else C.c_void_p(int(L_ptr)), None if R_ptr is None else C.c_void_p(int(R_ptr)),
+            int(in_stride), int(frames), None if c is None else c.ctypes.data, C.byref(lo),
+            None if stream is None else C.c_void_p(int(stream))))
+
+    def reset(self, rows=None, stream=None):
+        """tbf_limiter_reset: the rows (None: all) start anew, ordered on the stream"""
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        _check(self._lib.tbf_limiter_reset(self._h, 0 if r is None else len(r), None if r is None else r.ctypes.data,
+                                           None if stream is None else C.c_void_p(int(stream))))
+
+    def time(self, enable=None):
+        """tbf_debug_limit_time: enable True / False switches the event pair around every call's
+        launches on / off; None returns (milliseconds, launch sets) since the last query."""
+        f = self._lib.tbf_debug_limit_time
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_uint64)]
+        if enable is not None:
+            _check(f(self._h, 1 if enable else -1, None, None))
+            return None
+        ms, n = C.c_double(), C.c_uint64()
+        _check(f(self._h, 0, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def close(self):
+        """tbf_limiter_destroy (the engine does it for the limiters still alive when it closes)"""
+        if self._h and getattr(self._eng, "_h", None):
+            _check(self._lib.tbf_limiter_destroy(self._h))
+        self._h = None
 
 
 class Engine:
@@ -955,6 +1038,50 @@ class Engine:
             self._h, int(nblocks), ev.ctypes.data if len(ev) else None, len(ev),
             None if in_ptr is None else C.c_void_p(int(in_ptr)), int(in_stride), r.ctypes.data if len(r) else None,
             int(n_buses), C.byref(mo), None if stream is None else C.c_void_p(int(stream))))
+
+    def limiter(self, n_rows, ceiling, ahead=64, hold=0):
+        """tbf_limiter_create: a look-ahead peak limiter of n_rows rows on this engine's device
+        (ceiling in float32; ahead a power of two in [2, LIMIT_MAX_AHEAD]; hold in
+        [0, LIMIT_MAX_HOLD] frames); the engine releases it when it closes"""
+        cfg = LimiterConfig(float(ceiling), int(ahead), int(hold))
+        h = C.c_void_p()
+        _check(self._lib.tbf_limiter_create(self._h, int(n_rows), C.byref(cfg), C.byref(h)))
+        return Limiter(self, h, int(n_rows), cfg)
+
+    @staticmethod
+    def limit_ref(L, R, ceiling, ahead=64, hold=0, hist=None):
+        """tbf_debug_limit_ref: the host restatement of the limiter on one row (no device needed):
+        L, R [n] float32 (the same array twice: mono), hist None (a new row) or the (histL, histR)
+        an earlier call returned; returns (outL, outR, LIMIT_METER_DTYPE record, (histL, histR))."""
+        f = load_library().tbf_debug_limit_ref
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(LimiterConfig), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                      C.c_void_p, C.c_void_p]
+        mono = L is R
+        L = np.ascontiguousarray(L, dtype=np.float32)
+        R = L if mono else np.ascontiguousarray(R, dtype=np.float32)
+        if L.ndim != 1 or L.shape != R.shape:
+            raise ValueError(f"rows of shape {L.shape} and {R.shape}: want two of [n]")
+        cfg = LimiterConfig(float(ceiling), int(ahead), int(hold))
+        hn = max(2 * int(ahead) + int(hold) - 2, 0)
+        hL, hR = (np.zeros(hn, np.float32), np.zeros(hn, np.float32)) if hist is None else \
+            (np.array(hist[0], np.float32), np.array(hist[1], np.float32))
+        oL, oR = np.full(len(L), np.nan, np.float32), np.full(len(L), np.nan, np.float32)
+        m = np.zeros(1, LIMIT_METER_DTYPE)
+        _check(f(C.byref(cfg), L.ctypes.data, R.ctypes.data, len(L), hL.ctypes.data, hR.ctypes.data, oL.ctypes.data,
+                 oR.ctypes.data, m.ctypes.data))
+        return oL, oR, m[0], (hL, hR)
+
+    @staticmethod
+    def limit_grid(ceiling, ahead=64, hold=0):
+        """tbf_debug_limit_grid: (frames per lane, frames per workgroup tile, history frames Hn, LDS
+        bytes per workgroup) of k_limit under a configuration"""
+        f = load_library().tbf_debug_limit_grid
+        f.restype, f.argtypes = C.c_int, [C.POINTER(LimiterConfig), _u32p, _u32p, _u32p, _u32p]
+        cfg = LimiterConfig(float(ceiling), int(ahead), int(hold))
+        g, t, h, b = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(f(C.byref(cfg), C.byref(g), C.byref(t), C.byref(h), C.byref(b)))
+        return g.value, t.value, h.value, b.value
 
     def synchronize(self):
         _check(self._lib.tbf_synchronize(self._h))

@@ -34,6 +34,11 @@ PCM_DITHER = 1
 MIX_NONE = 0xFFFFFFFF
 MIX_ROW_DTYPE = np.dtype([("bus", "<u4"), ("ll", "<f4"), ("lr", "<f4"), ("rl", "<f4"), ("rr", "<f4")])
 
+# the bus limiter (Engine.limiter): the largest look-ahead (a power of two from 2) and hold in
+# frames (TBF_LIMIT_MAX_*), and tbf_limit_meter as a numpy record (12 B, as the C struct)
+LIMIT_MAX_AHEAD, LIMIT_MAX_HOLD = 512, 4096
+LIMIT_METER_DTYPE = np.dtype([("min_gain", "<f4"), ("reduced", "<u4"), ("clamped", "<u4")])
+
 
 def mix_rows(bus, gain=1.0, pan=0.0):
     """tbf_mix_row records for Engine.mix_device / .render_mix / .process_mix: row r goes to bus
