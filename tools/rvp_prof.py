@@ -1,7 +1,7 @@
 """k_rv_post role clocks (profiling variant RVP_PROF=1, never the product): the bench's batch
 and registration in the reverb-tap chain mode, one 512-block launch after warm-up launches;
-workgroup 0's serial, dither and first helper waves write their s_memtime sums (k cycles) of
-work and barrier wait over instance 0's first output samples.
+workgroup 0's waves write their s_memtime sums (k cycles) of work and barrier wait, the SIMD
+they ran on and their role over instance 0's first output samples.
 
     TBF_LIB=tunebfree_amd/_variants/libtbf_rvpprof.so python tools/rvp_prof.py"""
 import sys
@@ -33,10 +33,17 @@ def main():
     print(f"k_rv_post per iteration (cycles), {it} iterations:")
     for name, o in (("serial", 0), ("dither", 4), ("helper0", 8)):
         print(f"  {name:8s} work {v[o] * 1e3 / it:8.0f}  barrier {v[o + 1] * 1e3 / it:8.0f}")
-    print("every wave of workgroup 0 (wave: work / barrier cycles per iteration, SIMD):")
-    for w in range(11):
-        b = 16 + 3 * w
-        print(f"  wave {w:2d}: {v[b] * 1e3 / it:8.0f} / {v[b + 1] * 1e3 / it:8.0f}  SIMD {v[b + 2]:.0f}")
+    waves = int(v[12])
+    print(f"the {waves} waves of workgroup 0 (wave: role, work / barrier cycles per iteration, SIMD):")
+    by_simd = {}
+    for w in range(waves):
+        work, barrier, simd, role = (float(x) for x in v[16 + 4 * w:20 + 4 * w])
+        name = {-2: "serial", -1: "dither"}.get(int(role), f"helper, {int(role)} task{'s' if role > 1 else ''}")
+        print(f"  wave {w:2d}: {name:15s} {work * 1e3 / it:8.0f} / {barrier * 1e3 / it:8.0f}  SIMD {simd:.0f}")
+        by_simd.setdefault(int(simd), []).append((w, work * 1e3 / it))
+    print("by SIMD (waves, the last one's work cycles):")
+    for simd, ws in sorted(by_simd.items()):
+        print(f"  SIMD {simd}: waves {[w for w, _ in ws]}  {max(c for _, c in ws):8.0f}")
 
 
 if __name__ == "__main__":

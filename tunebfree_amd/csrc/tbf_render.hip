@@ -1862,8 +1862,8 @@ static_assert (RVC_NC <= NL && RVC_T * 2 == NL && TBF_BLK % RVC_T == 0, "chain-b
 #define RVC_ROWS_OF(cb) (2 * (cb) + (2 * (cb) < NL)) /* chain rows, + one that the serial and dither waves' idle lanes use */
 #define RVC_ROWS RVC_ROWS_OF (RVC_CB)
 /* The shape of a k_rv_pre launch that runs ahead, beside the previous chunk's k_rv_post
- * (tbf_launch.preAhead): a k_rv_post workgroup sits on every CU with 11 waves at 112 VGPRs
- * and RvPostLds, which leaves 2 + 2 + 2 + 3 wave slots at 80 VGPRs and 50,584 B of
+ * (tbf_launch.preAhead): a k_rv_post workgroup sits on every CU with 12 waves at 112 VGPRs
+ * and RvPostLds, which leaves 2 + 2 + 2 + 2 wave slots at 80 VGPRs and 50,584 B of
  * LDS, so at most 8 waves (serial, dither, 6 helpers) and a chain block that fits (the
  * static_assert behind RvPostLds).  Measured slower than k_rv_pre in its own phase
  * (DESIGN.md section 4.7), so only TBF_PRE_AHEAD=1 launches it. */
@@ -2182,54 +2182,108 @@ k_rv_pre (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf_
 
 /* k_rv_post's chain block: RVP_CB instances per workgroup (k_rv_pre keeps RVC_CB) */
 #ifndef RVP_CB
-#define RVP_CB 16 /* 256 workgroups: all CUs (32 per workgroup: step 129.7 -> 127.5 ms at 16, profiles/r05/s37) */
+#define RVP_CB 16 /* 256 workgroups: all CUs (32 per workgroup: step 129.7 -> 127.5 ms at 16, profiles/r05/s37); its 32
+                   * biquadB and 32 biquadC chains fill the one serial wave */
 #endif
 #ifndef RVP_PROF
 #define RVP_PROF 0 /* profiling variant (never the product): s_memtime work / barrier clocks per role (tools/rvp_prof.py) */
 #endif
-#if RVP_PROF /* workgroup 0's serial, dither and first helper waves write k cycles over instance 0's first outputs (tap chain) */
+#if RVP_PROF /* workgroup 0's waves write k cycles over instance 0's first outputs (tap chain): the serial, dither and
+              * first helper waves at samples 0, 4 and 8, the workgroup's waves at 12, then every wave's work,
+              * barrier wait, SIMD and role (-2 serial, -1 dither, else the helper's tasks) from sample 16 */
 #define RVP_PROF_DECL() unsigned long long pw_ = 0, pb_ = 0, pa_ = 0, pc_ = 0
 #define RVP_T0() pa_ = __builtin_amdgcn_s_memtime ()
 #define RVP_T1() { asm volatile ("" ::: "memory"); pc_ = __builtin_amdgcn_s_memtime (); pw_ += pc_ - pa_; }
 #define RVP_T2() { asm volatile ("" ::: "memory"); pb_ += __builtin_amdgcn_s_memtime () - pc_; }
-#define RVP_PROF_OUT(i) { if (blockIdx.x == 0 && lane == 0) { \
+#define RVP_PROF_OUT(i, role) { if (blockIdx.x == 0 && lane == 0) { \
 	if ((i) >= 0) { P.outL[P.outOffset + (i)] = (float)(pw_ * 1e-3); P.outL[P.outOffset + (i) + 1] = (float)(pb_ * 1e-3); } \
-	P.outL[P.outOffset + 16 + 3 * w] = (float)(pw_ * 1e-3); P.outL[P.outOffset + 17 + 3 * w] = (float)(pb_ * 1e-3); \
-	P.outL[P.outOffset + 18 + 3 * w] = (float)((__builtin_amdgcn_s_getreg ((31 << 11) | 4) >> 4) & 3); } }
+	if (w == 0) P.outL[P.outOffset + 12] = (float)(RVP_THREADS / NL); \
+	P.outL[P.outOffset + 16 + 4 * w] = (float)(pw_ * 1e-3); P.outL[P.outOffset + 17 + 4 * w] = (float)(pb_ * 1e-3); \
+	P.outL[P.outOffset + 18 + 4 * w] = (float)((__builtin_amdgcn_s_getreg ((31 << 11) | 4) >> 4) & 3); \
+	P.outL[P.outOffset + 19 + 4 * w] = (float)(role); } }
 #else
 #define RVP_PROF_DECL()
 #define RVP_T0()
 #define RVP_T1()
 #define RVP_T2()
-#define RVP_PROF_OUT(i)
-#endif
-#ifndef RVP_H
-#define RVP_H 8 /* helper waves */
+#define RVP_PROF_OUT(i, role)
 #endif
 #define RVP_NC (2 * RVP_CB)
 #define RVP_ROWS (RVP_NC + (RVP_NC < NL)) /* chain rows, + one that the idle chain lanes use */
-#define RVP_NTK (RVP_CB / RVP_H)
-static_assert (RVP_CB % RVP_H == 0 && RVP_NC <= NL, "k_rv_post chain-block geometry");
+/* One serial wave runs both biquads: lanes 0-31 the biquadB chains, lanes 32-63 the biquadC
+ * chains.  They are one instruction stream (rvc_serial_p); on a wave each, with lanes 32-63
+ * idle, it was issued twice an iteration, beside two helpers each time (2.5 k cycles of work
+ * each; the iteration 3.4 k).  So a workgroup has at most 32 chains. */
+#define RVP_SER 1
+static_assert (2 * RVP_NC <= NL, "k_rv_post: biquadB and biquadC chains share one wave");
+/* The other waves: the dither wave RVP_DW and RVP_H helpers, which share the workgroup's RVP_CB
+ * instance tasks by the table RVP_TASK (helper -> its one or two tasks, -1: none; helper h is
+ * wave h + 1 below RVP_DW, wave h + 2 above).  Waves equal mod 4 share a SIMD and issue oldest
+ * first (the role clocks' SIMD ids and work cycles, tools/rvp_prof.py), so per SIMD:
+ *   waves 0 4 8   serial, 1 task, 1 task: the serial chain's 2.4 k cycles are the floor, and
+ *                 a helper with two tasks beside it takes 2.8 k
+ *   waves 1 5 9   2 tasks, 2 tasks, dither: the dither wave is latency-bound and finishes in
+ *                 2.3 k as the youngest; as the oldest it pushed the second helper to 2.6 k
+ *   waves 2 6 10 and 3 7 11   2, 2 and 1 tasks (2.2 k)
+ * 12 waves are 3 a SIMD: with at most 112 VGPRs each they leave 2 x 88 registers a SIMD for
+ * the ahead shape of k_rv_pre.  profiles/rvpost_roles has the clocks of every table tried. */
+#define RVP_NTK 2
+#define RVP_H 10
+#define RVP_DW 9
+constexpr int RVP_TASK[RVP_H][RVP_NTK] = { { 0, 1 }, { 2, 3 }, { 4, 5 }, { 6, -1 }, { 7, 8 }, { 9, 10 }, { 11, 12 }, { 13, -1 }, { 14, -1 }, { 15, -1 } };
+#define RVP_HELPER_OF(w) ((w) - RVP_SER - ((w) > RVP_DW)) /* the helper index of a wave that is neither serial nor dither */
+/* slot t of every helper wave, 5 bits each (31: none) */
+constexpr uint64_t rvp_task_bits (int t)
+{
+	uint64_t v = 0;
+	for (int h = 0; h < RVP_H; h++)
+		v |= (uint64_t)(RVP_TASK[h][t] & 31) << (5 * h);
+	return v;
+}
+constexpr bool rvp_tasks_once ()
+{
+	for (int j = 0; j < RVP_CB; j++) {
+		int n = 0;
+		for (int h = 0; h < RVP_H; h++)
+			for (int t = 0; t < RVP_NTK; t++)
+				n += RVP_TASK[h][t] == j;
+		if (n != 1)
+			return false;
+	}
+	for (int h = 0; h < RVP_H; h++)
+		if (RVP_TASK[h][0] < 0 || RVP_TASK[h][1] >= RVP_CB)
+			return false;
+	return true;
+}
+static_assert (RVP_NTK == 2 && RVP_H <= 12 && RVP_CB <= 31 && RVP_DW > 0 && RVP_DW <= RVP_SER + RVP_H && rvp_tasks_once (), "k_rv_post: every instance task on one helper wave");
 
-#define RVP_SER 2                                   /* serial chain waves (biquadB, biquadC) */
-#define RVP_THREADS (NL * (RVP_SER + 1 + RVP_H))    /* + the dither wave and the helpers */
+#define RVP_THREADS (NL * (RVP_SER + 1 + RVP_H))    /* the serial wave, the dither wave and the helpers */
 
 struct RvPostLds {
+	/* y, y1, y2 lie as z, z1, z2 do: the serial wave's lanes hold one row address each */
 	double   y[2][RVP_ROWS][RVC_S]; /* tap mix x c0 -> biquadB output, in place */
-	double   z[2][RVP_ROWS][RVC_S]; /* asin output x c0 -> biquadC output, in place */
 	double   y1[2][RVP_ROWS][RVC_S], y2[2][RVP_ROWS][RVC_S]; /* x c1, x c2 of the tap mix */
+	double   z[2][RVP_ROWS][RVC_S]; /* asin output x c0 -> biquadC output, in place */
 	double   z1[2][RVP_ROWS][RVC_S], z2[2][RVP_ROWS][RVC_S]; /* x c1, x c2 of the asin output */
 	uint32_t f[2][RVP_ROWS][RVC_S]; /* fpdL / fpdR before each sample (entry RVC_T: after the tile) */
 };
 /* a k_rv_pre workgroup of the ahead shape shares a CU (160 KB of LDS) with one of k_rv_post's */
 static_assert (sizeof (RvPreLds<RVC_ROWS_OF (RVA_CB)>) + sizeof (RvPostLds) <= 160 * 1024, "k_rv_pre ahead shape: LDS beside k_rv_post");
 
+template <int NTK>
+__device__ __forceinline__ void rvp_helper (RvPostLds& sm, const tbf_launch& P, const tbf_inst_const* __restrict__ cst,
+                                            const tbf_seg_ctl* __restrict__ ctl, const int w, const int lane, const uint32_t inst0,
+                                            const int nj, const int nT, const int nIt, const int (&jt)[NTK]);
+
 /* biquadB, clamp + asin, biquadC, dry mix, dither, (L + R) / sqrt 2 (src/reverb.cpp:733-787)
  * -> mid2.  A tile is loaded at iteration k (its HBM reads issued at k - 2), biquadB at
- * k + 1, asin at k + 2, biquadC at k + 3, output at k + 4.  Wave 0 runs the
- * biquadB chains, wave 1 the biquadC chains (one chain per lane each; one wave with both
- * interleaved was the kernel's bound, 4.2 k cycles an iteration against 1.4 k for the
- * helpers), wave 2 the dither streams, and the helpers write each input's three products. */
+ * k + 1, asin at k + 2, biquadC at k + 3, output at k + 4.  Wave 0 runs the serial chains,
+ * one per lane: biquadB in lanes 0-31, biquadC in lanes 32-63 (both in one lane, interleaved,
+ * was the kernel's bound: 4.2 k cycles an iteration against 1.4 k for the helpers; on a wave
+ * each, the one instruction stream issued twice).  Wave RVP_DW runs the dither streams, and
+ * the helpers (RVP_TASK: one or two instances each) write each input's three products.
+ * Resources, which the ahead shape of k_rv_pre counts on: sizeof (RvPostLds) = 113,256 B (the
+ * static_assert above), 12 waves of at most 112 VGPRs (110 as compiled), no scratch. */
 __global__ void __launch_bounds__ (RVP_THREADS)
 k_rv_post (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf_seg_ctl* __restrict__ ctl)
 {
@@ -2241,41 +2295,51 @@ k_rv_post (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf
 	const int     nj  = (int)min ((uint32_t)RVP_CB, P.nInst - inst0);
 	const int     nT  = (int)P.nBlocks * (TBF_BLK / RVC_T);
 	const int     nIt = nT + 4;
-	const int     cj = lane >> 1, cc = lane & 1;
-	const bool    cok = cj < nj;
-	const int     crow = lane < RVP_NC ? lane : RVP_NC; /* chain lanes past the block's chains: the idle row */
-	tbf_rv_state* CS  = &P.st[inst0 + (cok ? cj : 0)].rv;
-	if (w < 2) {
-		/* w 0: biquadB of tile it - 1 (rows y); w 1: biquadC of tile it - 3 (rows z) */
+	if (w < RVP_SER) {
+		/* lanes 0-31: biquadB of tile it - 1 (rows y); lanes 32-63: biquadC of tile it - 3
+		 * (rows z); both in the buffers of parity (it - 1) & 1.  In iterations 1, 2 and
+		 * nT + 1, nT + 2 one half has no tile: its lanes are masked off. */
+		const int             half = lane >> 5, ch = lane & 31;
+		const int             cj = ch >> 1, cc = ch & 1;
+		const bool            cok = cj < nj;
+		const int             crow = ch < RVP_NC ? ch : RVP_NC; /* chain lanes past the block's chains: the idle row */
+		tbf_rv_state*         CS = &P.st[inst0 + (cok ? cj : 0)].rv;
 		const tbf_inst_const& K  = cst[inst0 + (cok ? cj : 0)];
-		const int             q  = w + 1;
+		const int             q  = half + 1;
 		const double          c3 = K.bq[q][3], c4 = K.bq[q][4];
 		double                s7 = CS->bq[q][2 * cc], s8 = CS->bq[q][2 * cc + 1];
+		constexpr int         AR = 2 * RVP_ROWS * RVC_S; /* y -> y1 -> y2 and z -> z1 -> z2, in doubles */
+		static_assert (offsetof (RvPostLds, y1) - offsetof (RvPostLds, y) == AR * sizeof (double)
+		               && offsetof (RvPostLds, y2) - offsetof (RvPostLds, y) == 2 * AR * sizeof (double)
+		               && offsetof (RvPostLds, z1) - offsetof (RvPostLds, z) == AR * sizeof (double)
+		               && offsetof (RvPostLds, z2) - offsetof (RvPostLds, z) == 2 * AR * sizeof (double), "RvPostLds: product rows");
+		double*               r0 = reinterpret_cast<double*> (&sm) + (half ? offsetof (RvPostLds, z) / sizeof (double) : 0) + crow * RVC_S;
 		__syncthreads ();
 		RVP_PROF_DECL ();
 #pragma unroll 1
 		for (int it = 0; it < nIt; it++) {
 			RVP_T0 ();
-			const int tile = it - 1 - 2 * w;
+			const int tile = it - 1 - 2 * half;
 			if (tile >= 0 && tile < nT) {
-				const int pb = (it - 1) & 1;
-				if (w == 0)
-					rvc_serial_p (sm.y[pb][crow], sm.y1[pb][crow], sm.y2[pb][crow], c3, c4, s7, s8);
-				else
-					rvc_serial_p (sm.z[pb][crow], sm.z1[pb][crow], sm.z2[pb][crow], c3, c4, s7, s8);
+				const int po = ((it - 1) & 1) * (RVP_ROWS * RVC_S);
+				rvc_serial_p (r0 + po, r0 + po + AR, r0 + po + 2 * AR, c3, c4, s7, s8);
 			}
 			RVP_T1 ();
 			__syncthreads ();
 			RVP_T2 ();
 		}
-		RVP_PROF_OUT (w == 0 ? 0 : -1);
+		RVP_PROF_OUT (0, -2);
 		if (cok) {
 			CS->bq[q][2 * cc]     = s7;
 			CS->bq[q][2 * cc + 1] = s8;
 		}
 		return;
 	}
-	if (w == RVP_SER) {
+	if (w == RVP_DW) {
+		const int     cj = lane >> 1, cc = lane & 1;
+		const bool    cok = cj < nj;
+		const int     crow = lane < RVP_NC ? lane : RVP_NC; /* chain lanes past the block's chains: the idle row */
+		tbf_rv_state* CS  = &P.st[inst0 + (cok ? cj : 0)].rv;
 		uint32_t fs = cc ? CS->fpdR2 : CS->fpdL2;
 		__syncthreads ();
 		RVP_PROF_DECL ();
@@ -2288,7 +2352,7 @@ k_rv_post (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf
 			__syncthreads ();
 			RVP_T2 ();
 		}
-		RVP_PROF_OUT (4);
+		RVP_PROF_OUT (4, -1);
 		if (cok) {
 			if (cc)
 				CS->fpdR2 = fs;
@@ -2297,19 +2361,37 @@ k_rv_post (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf
 		}
 		return;
 	}
-	/* helpers: HBM reads two tiles ahead into two register sets alternating by iteration
-	 * parity (see k_rv_pre) */
+	/* helpers: the wave's one or two tasks (wave-uniform) */
+	const int h  = RVP_HELPER_OF (w);
+	const int j0 = (int)((rvp_task_bits (0) >> (5 * h)) & 31), j1 = (int)((rvp_task_bits (1) >> (5 * h)) & 31);
+	if (j1 < RVP_CB) {
+		const int jt[2] = { j0, j1 };
+		rvp_helper<2> (sm, P, cst, ctl, w, lane, inst0, nj, nT, nIt, jt);
+	} else {
+		const int jt[1] = { j0 };
+		rvp_helper<1> (sm, P, cst, ctl, w, lane, inst0, nj, nT, nIt, jt);
+	}
+}
+
+/* a helper wave of k_rv_post with NTK instance tasks jt[] of the workgroup's RVP_CB,
+ * interleaved: HBM reads two tiles ahead into two register sets alternating by iteration
+ * parity (see k_rv_pre) */
+template <int NTK>
+__device__ __forceinline__ void rvp_helper (RvPostLds& sm, const tbf_launch& P, const tbf_inst_const* __restrict__ cst,
+                                            const tbf_seg_ctl* __restrict__ ctl, const int w, const int lane, const uint32_t inst0,
+                                            const int nj, const int nT, const int nIt, const int (&jt)[NTK])
+{
 	const bool   tap = P.chain == TBF_CHAIN_TAP_REVERB;
-	const int    h = w - RVP_SER - 1, hc = lane >> 5, n = lane & (RVC_T - 1);
-	double       pB[2][RVP_NTK], wetv[RVP_NTK];
-	float        pIn[2][RVP_NTK];
-	const double* rb[RVP_NTK];
-	const float*  in[RVP_NTK];
-	float*        out[RVP_NTK];
-	double       cB[RVP_NTK][3], cC[RVP_NTK][3]; /* the task's biquadB / biquadC input coefficients c0 c1 c2 */
+	const int    hc = lane >> 5, n = lane & (RVC_T - 1);
+	double       pB[2][NTK], wetv[NTK];
+	float        pIn[2][NTK];
+	const double* rb[NTK];
+	const float*  in[NTK];
+	float*        out[NTK];
+	double       cB[NTK][3], cC[NTK][3]; /* the task's biquadB / biquadC input coefficients c0 c1 c2 */
 #pragma unroll
-	for (int t = 0; t < RVP_NTK; t++) {
-		const int      j    = h + t * RVP_H;
+	for (int t = 0; t < NTK; t++) {
+		const int      j    = jt[t];
 		const uint32_t inst = inst0 + (j < nj ? j : nj - 1);
 		rb[t]     = rv_buf (P.rvB, P, inst, hc) + n;
 		in[t]     = P.mid1 + (size_t)inst * P.midStride + n;
@@ -2326,18 +2408,18 @@ k_rv_post (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf
 	}
 	__syncthreads ();
 	RVP_PROF_DECL ();
-	auto step = [&] (const int it, double (&qB)[RVP_NTK], float (&qIn)[RVP_NTK]) {
+	auto step = [&] (const int it, double (&qB)[NTK], float (&qIn)[NTK]) {
 		RVP_T0 ();
 		const int b = it & 1; /* tiles it, it - 2 and it - 4 share the buffers */
 		/* output of tile it - 4: dry mix, dither, mono sum (src/reverb.cpp:766-787); the
 		 * half-waves hold L and R, and 0.7071 (L + R) == 0.7071 (R + L) */
-		float yv[RVP_NTK];
+		float yv[NTK];
 		if (it >= 4) {
 			const int ob = blk_lane (((it - 4) * RVC_T) / TBF_BLK);
 #pragma unroll
-			for (int t = 0; t < RVP_NTK; t++) {
+			for (int t = 0; t < NTK; t++) {
 				const double wet = rld (wetv[t], ob);
-				const int    r   = 2 * (h + t * RVP_H) + hc;
+				const int    r   = 2 * jt[t] + hc;
 				double       x   = sm.z[b][r][n];
 				if (wet != 1.0) {
 					double dry = (double)qIn[t];
@@ -2352,14 +2434,14 @@ k_rv_post (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf
 		}
 		/* clamp + asin of tile it - 2 (src/reverb.cpp:743-751); the tap mix of tile it,
 		 * which reuses the biquadB buffer, after the reads */
-		double av[RVP_NTK];
+		double av[NTK];
 #pragma unroll
-		for (int t = 0; t < RVP_NTK; t++)
-			av[t] = sm.y[b][2 * (h + t * RVP_H) + hc][n];
+		for (int t = 0; t < NTK; t++)
+			av[t] = sm.y[b][2 * jt[t] + hc][n];
 		if (it < nT) {
 #pragma unroll
-			for (int t = 0; t < RVP_NTK; t++) {
-				const int r = 2 * (h + t * RVP_H) + hc;
+			for (int t = 0; t < NTK; t++) {
+				const int r = 2 * jt[t] + hc;
 				sm.y[b][r][n]  = qB[t] * cB[t][0];
 				sm.y1[b][r][n] = qB[t] * cB[t][1];
 				sm.y2[b][r][n] = qB[t] * cB[t][2];
@@ -2370,15 +2452,15 @@ k_rv_post (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf
 		 * iteration it + 2) */
 		const int tb = min (it + 2, nT - 1), ti = max (0, min (it - 2, nT - 1));
 #pragma unroll
-		for (int t = 0; t < RVP_NTK; t++) {
+		for (int t = 0; t < NTK; t++) {
 			qB[t]  = rb[t][(size_t)tb * RVC_T];
 			qIn[t] = in[t][(size_t)ti * RVC_T];
 		}
 		if (it >= 2 && it - 2 < nT) {
-			double y[RVP_NTK];
+			double y[NTK];
 			bool   small = true;
 #pragma unroll
-			for (int t = 0; t < RVP_NTK; t++) {
+			for (int t = 0; t < NTK; t++) {
 				y[t] = av[t];
 				if (y[t] > 1.0)
 					y[t] = 1.0;
@@ -2388,19 +2470,19 @@ k_rv_post (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf
 			}
 			/* every task's value inside OCML asin's polynomial branch (the tap mix is small):
 			 * that branch alone, straight-line, so the tasks' chains interleave (tbf_sin.h) */
-			double as[RVP_NTK];
+			double as[NTK];
 			if (__all (small)) {
 #pragma unroll
-				for (int t = 0; t < RVP_NTK; t++)
+				for (int t = 0; t < NTK; t++)
 					as[t] = tbf_asin_poly (y[t]);
 			} else {
 #pragma unroll
-				for (int t = 0; t < RVP_NTK; t++)
+				for (int t = 0; t < NTK; t++)
 					as[t] = asin (y[t]);
 			}
 #pragma unroll
-			for (int t = 0; t < RVP_NTK; t++) {
-				const int r = 2 * (h + t * RVP_H) + hc;
+			for (int t = 0; t < NTK; t++) {
+				const int r = 2 * jt[t] + hc;
 				sm.z[b][r][n]  = as[t] * cC[t][0];
 				sm.z1[b][r][n] = as[t] * cC[t][1];
 				sm.z2[b][r][n] = as[t] * cC[t][2];
@@ -2409,8 +2491,8 @@ k_rv_post (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf
 		if (it >= 4) {
 			const size_t so = (size_t)(it - 4) * RVC_T;
 #pragma unroll
-			for (int t = 0; t < RVP_NTK; t++)
-				if (h + t * RVP_H < nj && (tap || hc == 0))
+			for (int t = 0; t < NTK; t++)
+				if (jt[t] < nj && (tap || hc == 0))
 					out[t][so] = yv[t];
 		}
 		RVP_T1 ();
@@ -2423,7 +2505,7 @@ k_rv_post (const tbf_launch P, const tbf_inst_const* __restrict__ cst, const tbf
 		if (it + 1 < nIt)
 			step (it + 1, pB[1], pIn[1]);
 	}
-	RVP_PROF_OUT (h == 0 ? 8 : -1);
+	RVP_PROF_OUT (RVP_HELPER_OF (w) == 0 ? 8 : -1, NTK);
 }
 
 /* ================================================================== k_whirl */
