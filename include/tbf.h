@@ -799,6 +799,108 @@ int tbf_debug_limit_grid (const tbf_limiter_config* cfg, uint32_t* frames_per_la
  * one launch set per call that took frames */
 int tbf_debug_limit_time (tbf_limiter* lim, int32_t enable, double* ms, uint64_t* launches);
 
+/* ---- Loudness meter: BS.1770 integrated loudness of planes, on the device ----
+ * A stage beside any two float32 device planes: it reads them and writes only its own memory.
+ * ITU-R BS.1770-4 integrated loudness with EBU R128 gating, for a stereo pair with both channel
+ * weights 1.0.  Like the mixdown and the limiter it is specified here, not restated from the
+ * reference, which has no meter, and it is defined to the bit up to the hop
+ * energies.  With a loudness per row, normalisation needs no stage of its own: tbf_mix_device with
+ * one bus per row and ll = rr = gain applies a per-row gain in front of the limiter.
+ * Parameters per meter, fixed at creation: rate_hz, an integer in [8000, 192000] and a multiple of
+ * 10; max_hops >= 1, the most 100 ms hops a row can hold between resets.  Derived: Hp = rate_hz / 10
+ * frames per hop.
+ * Coefficients: seven doubles, computed on the host once per meter in double with libm; the kernel
+ * receives them and never derives them.
+ *     shelf:  f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196
+ *             K = tan (pi*f0/rate); Vh = pow (10, G/20); Vb = pow (Vh, 0.4996667741545416); a0 = 1 + K/Q + K*K
+ *             b0 = (Vh + Vb*K/Q + K*K)/a0;  b1 = 2*(K*K - Vh)/a0;  b2 = (Vh - Vb*K/Q + K*K)/a0
+ *             a1 = 2*(K*K - 1)/a0;          a2 = (1 - K/Q + K*K)/a0
+ *     high-pass: f0 = 38.13547087602444, Q = 0.5003270373238773, K = tan (pi*f0/rate), a0 = 1 + K/Q + K*K
+ *             numerator 1, -2, 1 (literal);  c1 = 2*(K*K - 1)/a0;  c2 = (1 - K/Q + K*K)/a0
+ * (at 48000 these are the standard's printed table to its last digit.)
+ * Per row, per channel, per input frame, x = (double) sample; every *, + and - is one IEEE double
+ * operation, with no contraction, no fma and no flushing:
+ *     y  = b0*x + s1;   s1 = (b1*x + s2) - a1*y;    s2 = b2*x - a2*y
+ *     w  = y + t1;      t1 = (-2.0*y + t2) - c1*w;  t2 = y - c2*w
+ *     acc = acc + w*w;  k = k + 1
+ *     if (k == Hp) { E[row][hop][channel] = acc; acc = +0.0; k = 0; hop = hop + 1 }
+ * All state is zero at creation and at reset.  NaN and Inf are literal: a NaN poisons its row until
+ * the row is reset, and it touches no other row.  The order is part of the definition: a channel's
+ * frames form one serial chain; the kernel parallelises over rows and channels, never over a row's
+ * time, and keeps no block-wise transition matrices and no tree sums.  So a row's hop energies are
+ * the same bits however its frames are cut into calls.  d_L == d_R is allowed: such a row is
+ * measured as a pair of equal channels.
+ * Results, computed on the host in double by tbf_loudness_read from the row's N complete hops (an
+ * unfinished hop does not count):
+ *     u_h = EL_h + ER_h
+ *     z_j = (((u_j + u_{j+1}) + u_{j+2}) + u_{j+3}) / (4*Hp), j = 0 .. N-4          block energy
+ *     l_j = -0.691 + 10*log10 (z_j)                                                block loudness
+ *     absolute gate: l_j > -70;   relative gate: G = -0.691 + 10*log10 (mean z over the absolutely
+ *     gated blocks) - 10
+ *     integrated = -0.691 + 10*log10 (mean z over the blocks with l_j > -70 and l_j > G), the means
+ *     ascending serial sums
+ *     momentary_max = max l_j;  short_term_max the same over 30-hop (3 s) windows of u, once N >= 30
+ * A quantity with no block to take it from is -HUGE_VAL.  hops = N, blocks = the 400 ms blocks,
+ * gated = the blocks behind `integrated`.  These go through libm's log10 and are compared to a
+ * tolerance; the hop energies are compared in bits.
+ * State: 16 B x max_hops + 96 B per row.  It belongs to the meter object, not to an instance:
+ * tbf_instances_* do not know it, tbf_debug_device_bytes does not count it, and it is not saved.
+ * Left out: true-peak, loudness range, channel counts other than the pair, saving a meter. */
+typedef struct tbf_loudness tbf_loudness;
+typedef struct tbf_loudness_config {
+	uint32_t rate_hz, max_hops;
+} tbf_loudness_config;
+typedef struct tbf_loudness_result {
+	double   integrated, momentary_max, short_term_max; /* LUFS, or -HUGE_VAL */
+	uint32_t hops, blocks, gated, reserved;
+} tbf_loudness_result;
+/* A meter of n_rows rows on e's device; e owns it: tbf_engine_destroy releases the ones still
+ * alive.  -22: a NULL pointer, a rate_hz out of range or no multiple of 10, max_hops == 0,
+ * n_rows == 0.  A host-only engine validates, then returns -19.  -12 when the device cannot hold
+ * the state. */
+int tbf_loudness_create (tbf_engine* e, uint32_t n_rows, const tbf_loudness_config* cfg, tbf_loudness** out);
+int tbf_loudness_destroy (tbf_loudness* lm);
+/* The rows `rows` (host memory, n of them; NULL: all rows, n ignored) start anew, ordered on
+ * `stream` (NULL: the engine's own).  -22: a row index >= n_rows. */
+int tbf_loudness_reset (tbf_loudness* lm, uint32_t n, const uint32_t* rows, void* stream);
+/* One call: the meter's n_rows rows of d_L / d_R (device memory, row r at r * in_stride floats; any
+ * 4-byte-aligned pointers and odd strides; d_L == d_R allowed) on `stream` (NULL: the engine's
+ * own), ordered as tbf_render_device.  The planes are only read.  Row r takes counts[r] <= frames
+ * frames (counts: host memory, uploaded before the call returns), or `frames` when counts is NULL;
+ * a row with count 0 keeps its state.  Calls on one meter are the caller's to order.
+ * -22, with a tbf_last_error that names the argument: a NULL pointer, in_stride < frames, a
+ * misaligned pointer, counts[r] > frames.  -28 when some row would complete more than max_hops
+ * hops (the host knows every row's position).  Validation comes first: a refused call moves no
+ * state. */
+int tbf_loudness_device (tbf_loudness* lm, const float* d_L, const float* d_R, uint64_t in_stride, uint32_t frames,
+                         const uint32_t* counts, void* stream);
+/* The results of the rows `rows` (n of them; NULL: all rows in order, n ignored) into out.  Waits
+ * for the meter's last call on its stream.  -22: a NULL pointer, a row index >= n_rows. */
+int tbf_loudness_read (tbf_loudness* lm, uint32_t n, const uint32_t* rows, tbf_loudness_result* out);
+/* The energies of a row's complete hops as EL, ER pairs into e (room for cap_hops pairs) and
+ * their number into n_hops; waits as tbf_loudness_read.  -28 when cap_hops is too small, with
+ * n_hops set and nothing else written. */
+int tbf_loudness_hops (tbf_loudness* lm, uint32_t row, double* e, uint32_t cap_hops, uint32_t* n_hops);
+/* test hook: the seven coefficients b0, b1, b2, a1, a2, c1, c2 of a rate.  -22 as tbf_loudness_create. */
+int tbf_debug_loudness_coeffs (uint32_t rate_hz, double* c7);
+/* test hook: the host restatement of the definition on one row, from the header the kernel is
+ * built from (csrc/tbf_loud.h): n frames of L / R (L == R allowed) behind `state` = {s1, s2, t1, t2,
+ * acc, k} of L followed by the same of R (12 doubles, read and then replaced); the energies of the
+ * hops completed by these frames as EL, ER pairs into e and their number into n_hops.  Needs no
+ * engine and no device.  -22 as above, and for a state whose k is no integer in [0, Hp); -28 when
+ * cap_hops is too small, with nothing written. */
+int tbf_debug_loudness_ref (const tbf_loudness_config* cfg, const float* L, const float* R, uint64_t n, double* state,
+                            double* e, uint32_t cap_hops, uint32_t* n_hops);
+/* test hook: the gating alone, on n_hops EL, ER pairs in host memory; tbf_loudness_read calls the
+ * same code */
+int tbf_debug_loudness_result (uint32_t rate_hz, const double* e, uint32_t n_hops, tbf_loudness_result* out);
+/* test hook: how k_loud lays a meter of n_rows rows out: the rows of a workgroup, the frames of a
+ * row staged in LDS at a time, and the workgroup's LDS bytes.  No layout changes a bit.  Any out
+ * pointer may be NULL. */
+int tbf_debug_loudness_grid (uint32_t n_rows, uint32_t* rows_per_group, uint32_t* tile_frames, uint32_t* lds_bytes);
+/* k_loud's own time, as tbf_debug_limit_time: one launch set per call that took frames */
+int tbf_debug_loudness_time (tbf_loudness* lm, int32_t enable, double* ms, uint64_t* launches);
+
 int tbf_synchronize (tbf_engine* e);
 /* Which exact-but-slow paths the kernels took since the engine's first render (cumulative,
  * informational; the results are bit-identical either way).  Waits for the engine's

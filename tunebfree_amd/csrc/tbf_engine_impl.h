@@ -27,6 +27,7 @@
 #include "tbf_cabinet.h"
 #include "tbf_host.h"
 #include "tbf_limit.h"
+#include "tbf_loud.h"
 #include "tbf_mix.h"
 #include "tbf_pcm.h"
 #include "tbf_resample.h"
@@ -308,6 +309,31 @@ struct tbf_limiter {
 	}
 };
 
+/* A loudness meter (tbf_loudness_create, csrc/tbf_loud.cpp): per row and channel the two biquads'
+ * state, the open hop's sum and position (tbf_loud_chan), and the energies of the row's complete
+ * hops.  The host knows every row's position: pos[r] frames since creation or reset. */
+struct tbf_loudness {
+	tbf_engine*           eng = nullptr;
+	tbf_loudness_config   cfg = {0u, 0u};
+	uint32_t              nRows = 0, Hp = 0;
+	double                c[7] = {0, 0, 0, 0, 0, 0, 0};
+	DevBuf<tbf_loud_chan> state;   /* [row][channel] */
+	DevBuf<double>        energy;  /* [row][hop][channel], cfg.max_hops hops a row */
+	DevBuf<uint32_t>      dcounts; /* the call's counts on the device */
+	std::vector<uint32_t> counts;  /* the call's counts */
+	std::vector<uint64_t> pos;     /* frames a row has taken */
+	hipStream_t           last = nullptr; /* the stream of the meter's last call or reset */
+	bool                  timeOn = false; /* tbf_debug_loudness_time: an event pair around every launch */
+	std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
+	~tbf_loudness ()
+	{
+		for (auto& p : tev) {
+			(void)hipEventDestroy (p.first);
+			(void)hipEventDestroy (p.second);
+		}
+	}
+};
+
 struct tbf_engine {
 	tbf_engine_config                       cfg;
 	Config                                  conf; /* cfg keys (tbf_config_set) for tables built from now on */
@@ -547,9 +573,12 @@ struct tbf_engine {
 	uint32_t                                boffset = TBF_BLK; /* read position in the FIFO ... */
 	uint32_t                                fifoLen = TBF_BLK; /* ... of fifoLen samples per instance ... */
 	uint32_t                                fifoN   = 0;       /* ... for fifoN instances */
-	/* the bus limiters still alive (csrc/tbf_limit.cpp); they go with the engine.  The last member,
-	 * so that nothing the render path reads has moved. */
+	/* the bus limiters still alive (csrc/tbf_limit.cpp); they go with the engine.  Behind every
+	 * member the render path reads, so that nothing it reads has moved. */
 	std::vector<std::unique_ptr<tbf_limiter>> limiters;
+	/* the loudness meters still alive (csrc/tbf_loud.cpp), likewise, and behind the limiters for the
+	 * same reason */
+	std::vector<std::unique_ptr<tbf_loudness>> loudness;
 };
 
 namespace tbf {

@@ -94,6 +94,20 @@ class LimitOut(C.Structure):
     _fields_ = [("L", C.c_void_p), ("R", C.c_void_p), ("stride", C.c_uint64), ("meters", C.c_void_p)]
 
 
+class LoudnessConfig(C.Structure):
+    """tbf_loudness_config: the rate (a multiple of 10 in [8000, 192000]) and the most 100 ms hops a
+    row holds between resets"""
+    _fields_ = [("rate_hz", C.c_uint32), ("max_hops", C.c_uint32)]
+
+
+class LoudnessResult(C.Structure):
+    """tbf_loudness_result: integrated, largest momentary and largest short-term loudness in LUFS
+    (-inf where there is no block to take one from), the complete hops, the 400 ms blocks and the
+    blocks behind `integrated`; arrays of them are LOUDNESS_RESULT_DTYPE records"""
+    _fields_ = [("integrated", C.c_double), ("momentary_max", C.c_double), ("short_term_max", C.c_double),
+                ("hops", C.c_uint32), ("blocks", C.c_uint32), ("gated", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # tbf_engine_config.debug_flags / tbf_error_flags bits (include/tbf.h)
 DEBUG_FORCE_SERIAL = 1
 # tbf_engine_config.whirl_out (include/tbf.h TBF_WHIRL_OUT_*): whirlProc3's mic mix, whirlProc's direct sum
@@ -184,6 +198,12 @@ SIGNATURES = {
     "tbf_limiter_latency": (C.c_int, [C.c_void_p, _u32p]),
     "tbf_limit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
                                    C.POINTER(LimitOut), C.c_void_p]),
+    "tbf_loudness_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(LoudnessConfig), C.POINTER(C.c_void_p)]),
+    "tbf_loudness_destroy": (C.c_int, [C.c_void_p]),
+    "tbf_loudness_reset": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tbf_loudness_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tbf_loudness_read": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tbf_loudness_hops": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, _u32p]),
 }
 
 # tbf_engine_config.chain_mode of the effects-only chains (include/tbf.h TBF_CHAIN_FX*)
@@ -277,6 +297,81 @@ class Limiter:
         """tbf_limiter_destroy (the engine does it for the limiters still alive when it closes)"""
         if self._h and getattr(self._eng, "_h", None):
             _check(self._lib.tbf_limiter_destroy(self._h))
+        self._h = None
+
+
+class Loudness:
+    """A loudness meter (Engine.loudness): n_rows rows of BS.1770 K-weighted hop energies beside any
+    two device planes, and their gated loudness; its state belongs to it, not to the engine's
+    instances."""
+
+    def __init__(self, eng, handle, n_rows, cfg):
+        self._eng, self._lib, self._h = eng, eng._lib, handle
+        self.n_rows, self.rate_hz, self.max_hops = n_rows, cfg.rate_hz, cfg.max_hops
+
+    def measure_device(self, L_ptr, R_ptr, in_stride, frames, counts=None, stream=None):
+        """tbf_loudness_device: the meter's rows of the device planes L_ptr / R_ptr (row r at
+        r * in_stride floats; L_ptr == R_ptr: a pair of equal channels) take `frames` frames, or
+        counts[r] (host array) of them; the planes are only read."""
+        c = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+        if c is not None and len(c) != self.n_rows:
+            raise ValueError(f"{len(c)} counts for {self.n_rows} rows")
+        _check(self._lib.tbf_loudness_device(
+            self._h, None if L_ptr is None else C.c_void_p(int(L_ptr)), None if R_ptr is None else C.c_void_p(int(R_ptr)),
+            int(in_stride), int(frames), None if c is None else c.ctypes.data,
+            None if stream is None else C.c_void_p(int(stream))))
+
+    def read(self, rows=None):
+        """tbf_loudness_read: LOUDNESS_RESULT_DTYPE records of the rows (None: all), after the
+        meter's last call has passed its stream"""
+        from .params import LOUDNESS_RESULT_DTYPE
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        out = np.zeros(self.n_rows if r is None else len(r), LOUDNESS_RESULT_DTYPE)
+        _check(self._lib.tbf_loudness_read(self._h, 0 if r is None else len(r), None if r is None else r.ctypes.data,
+                                           out.ctypes.data))
+        return out
+
+    def hops(self, row):
+        """tbf_loudness_hops: the energies of the row's complete hops, [hops, 2] float64 (EL, ER)"""
+        n = C.c_uint32()
+        rc = self._lib.tbf_loudness_hops(self._h, int(row), None, 0, C.byref(n))
+        if rc not in (0, -28):
+            _check(rc)
+        e = np.zeros((n.value, 2), np.float64)
+        _check(self._lib.tbf_loudness_hops(self._h, int(row), e.ctypes.data, n.value, C.byref(n)))
+        return e
+
+    def gains(self, target_lufs):
+        """per row the float32 gain 10**((target_lufs - integrated) / 20) that brings it to the
+        target, computed in double and then rounded; 1.0 for a row with no gated block"""
+        res = self.read()
+        g = np.ones(self.n_rows, np.float64)
+        ok = res["gated"] > 0
+        g[ok] = 10.0 ** ((float(target_lufs) - res["integrated"][ok]) / 20.0)
+        return g.astype(np.float32)
+
+    def reset(self, rows=None, stream=None):
+        """tbf_loudness_reset: the rows (None: all) start anew, ordered on the stream"""
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        _check(self._lib.tbf_loudness_reset(self._h, 0 if r is None else len(r), None if r is None else r.ctypes.data,
+                                            None if stream is None else C.c_void_p(int(stream))))
+
+    def timing(self, enable=None):
+        """tbf_debug_loudness_time: enable True / False switches the event pair around every call's
+        launch on / off; None returns (milliseconds, launch sets) since the last query."""
+        f = self._lib.tbf_debug_loudness_time
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_uint64)]
+        if enable is not None:
+            _check(f(self._h, 1 if enable else -1, None, None))
+            return None
+        ms, n = C.c_double(), C.c_uint64()
+        _check(f(self._h, 0, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def close(self):
+        """tbf_loudness_destroy (the engine does it for the meters still alive when it closes)"""
+        if self._h and getattr(self._eng, "_h", None):
+            _check(self._lib.tbf_loudness_destroy(self._h))
         self._h = None
 
 
@@ -1082,6 +1177,70 @@ class Engine:
         g, t, h, b = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
         _check(f(C.byref(cfg), C.byref(g), C.byref(t), C.byref(h), C.byref(b)))
         return g.value, t.value, h.value, b.value
+
+    def loudness(self, n_rows, rate_hz=None, max_hops=6000):
+        """tbf_loudness_create: a BS.1770 loudness meter of n_rows rows on this engine's device, at
+        rate_hz (None: the engine's rate), each row holding up to max_hops 100 ms hops between
+        resets (16 B each); the engine releases it when it closes"""
+        cfg = LoudnessConfig(int(round(self.sample_rate)) if rate_hz is None else int(rate_hz), int(max_hops))
+        h = C.c_void_p()
+        _check(self._lib.tbf_loudness_create(self._h, int(n_rows), C.byref(cfg), C.byref(h)))
+        return Loudness(self, h, int(n_rows), cfg)
+
+    @staticmethod
+    def loudness_coeffs(rate_hz):
+        """tbf_debug_loudness_coeffs: b0, b1, b2, a1, a2 of the shelf and c1, c2 of the high-pass"""
+        f = load_library().tbf_debug_loudness_coeffs
+        f.restype, f.argtypes = C.c_int, [C.c_uint32, C.c_void_p]
+        c = np.zeros(7, np.float64)
+        _check(f(int(rate_hz), c.ctypes.data))
+        return c
+
+    @staticmethod
+    def loudness_ref(L, R, rate_hz, state=None, cap_hops=None):
+        """tbf_debug_loudness_ref: the host restatement of the meter's recurrence on one row (no
+        device needed): L, R [n] float32 (the same array twice: equal channels), state None (a new
+        row) or the 12 doubles an earlier call returned; returns (energies [hops, 2] of the hops
+        these frames complete, state).  cap_hops None: as many as are needed."""
+        f = load_library().tbf_debug_loudness_ref
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(LoudnessConfig), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, _u32p]
+        same = L is R
+        L = np.ascontiguousarray(L, dtype=np.float32)
+        R = L if same else np.ascontiguousarray(R, dtype=np.float32)
+        if L.ndim != 1 or L.shape != R.shape:
+            raise ValueError(f"rows of shape {L.shape} and {R.shape}: want two of [n]")
+        cfg = LoudnessConfig(int(rate_hz), 1)
+        st = np.zeros(12, np.float64) if state is None else np.array(state, np.float64)
+        if st.shape != (12,):
+            raise ValueError("state: want 12 doubles")
+        cap = len(L) // max(int(rate_hz) // 10, 1) + 1 if cap_hops is None else int(cap_hops)
+        e = np.zeros((cap, 2), np.float64)
+        n = C.c_uint32()
+        _check(f(C.byref(cfg), L.ctypes.data, R.ctypes.data, len(L), st.ctypes.data, e.ctypes.data, cap, C.byref(n)))
+        return e[:n.value].copy(), st
+
+    @staticmethod
+    def loudness_result(rate_hz, energies):
+        """tbf_debug_loudness_result: the gating alone on [hops, 2] energies; one
+        LOUDNESS_RESULT_DTYPE record"""
+        from .params import LOUDNESS_RESULT_DTYPE
+        f = load_library().tbf_debug_loudness_result
+        f.restype, f.argtypes = C.c_int, [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        e = np.ascontiguousarray(energies, dtype=np.float64).reshape(-1, 2)
+        out = np.zeros(1, LOUDNESS_RESULT_DTYPE)
+        _check(f(int(rate_hz), e.ctypes.data if len(e) else None, len(e), out.ctypes.data))
+        return out[0]
+
+    @staticmethod
+    def loudness_grid(n_rows=1):
+        """tbf_debug_loudness_grid: (rows per workgroup, frames per LDS tile, LDS bytes per
+        workgroup) of k_loud"""
+        f = load_library().tbf_debug_loudness_grid
+        f.restype, f.argtypes = C.c_int, [C.c_uint32, _u32p, _u32p, _u32p]
+        g, t, b = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(f(int(n_rows), C.byref(g), C.byref(t), C.byref(b)))
+        return g.value, t.value, b.value
 
     def synchronize(self):
         _check(self._lib.tbf_synchronize(self._h))

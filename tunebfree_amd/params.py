@@ -39,6 +39,10 @@ MIX_ROW_DTYPE = np.dtype([("bus", "<u4"), ("ll", "<f4"), ("lr", "<f4"), ("rl", "
 LIMIT_MAX_AHEAD, LIMIT_MAX_HOLD = 512, 4096
 LIMIT_METER_DTYPE = np.dtype([("min_gain", "<f4"), ("reduced", "<u4"), ("clamped", "<u4")])
 
+# the loudness meter (Engine.loudness): tbf_loudness_result as a numpy record (40 B, as the C struct)
+LOUDNESS_RESULT_DTYPE = np.dtype([("integrated", "<f8"), ("momentary_max", "<f8"), ("short_term_max", "<f8"),
+                                  ("hops", "<u4"), ("blocks", "<u4"), ("gated", "<u4"), ("reserved", "<u4")])
+
 
 def mix_rows(bus, gain=1.0, pan=0.0):
     """tbf_mix_row records for Engine.mix_device / .render_mix / .process_mix: row r goes to bus
@@ -56,4 +60,15 @@ def mix_rows(bus, gain=1.0, pan=0.0):
     rows["bus"] = np.where(bus < 0, MIX_NONE, bus).astype(np.uint32)
     rows["ll"] = (np.sqrt(2.0) * g * np.cos(a)).astype(np.float32)
     rows["rr"] = (np.sqrt(2.0) * g * np.sin(a)).astype(np.float32)
+    return rows
+
+
+def gain_rows(gains):
+    """tbf_mix_row records that apply a gain per row through Engine.mix_device: one bus per row
+    (row r to bus r) with ll = rr = gains[r] as float32 and lr = rl = 0, so bus r is gains[r] times
+    row r (Loudness.gains gives the gains that bring every row to a target loudness)."""
+    g = np.atleast_1d(np.asarray(gains, dtype=np.float32))
+    rows = np.zeros(g.shape, MIX_ROW_DTYPE)
+    rows["bus"] = np.arange(len(g), dtype=np.uint32)
+    rows["ll"] = rows["rr"] = g
     return rows
