@@ -911,6 +911,8 @@ int tbf_synchronize (tbf_engine* e);
 #define TBF_PATH_WH_MOTION 4u    /* whirl ring adds: sample-serial replay (src/whirl.cpp:1432-1469) */
 #define TBF_PATH_RV_PHASE 8u     /* reverb LFO phases: literal recurrence + sin (src/reverb.cpp:479-496) */
 #define TBF_PATH_RV_WINDOW 16u   /* reverb tap outside the staged window: direct ring reads */
+#define TBF_PATH_RV_SYNC 32u     /* not a path but a failure: a wave of k_rv_core_lds gave up waiting for a
+                                  * neighbour's phase (the kernel ends instead of hanging); the output is wrong */
 int tbf_error_flags (tbf_engine* e, uint32_t* flags);
 /* read back the wave bank of a template (wheels 1..256 concatenated) for checks */
 int tbf_template_bank (tbf_engine* e, uint32_t tpl_id, float* out, uint64_t cap, uint32_t* lens256);

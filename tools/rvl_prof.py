@@ -11,7 +11,7 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
-SEGS = ["pair start/ring load", "pre-loop barrier", "read phase", "barrier 1", "write phase", "barrier 2",
+SEGS = ["pair start/ring load", "pre-loop barrier", "read phase", "wait reads", "write phase", "wait writes/plan",
         "ring store", "groups"]
 
 

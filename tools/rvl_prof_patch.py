@@ -4,10 +4,10 @@ segment of rvl_pair on lane 0 and adds them, per wave index, to a device array r
 by tbf_debug_rvl_prof (tools/rvl_prof.py):
   0 pair start -> first barrier (ring load, or state load + first plan)
   1 the barrier before the group loop (first inputs)
-  2 read phase (workers) / planning (planner)      per group
-  3 first barrier wait                             per group
-  4 write phase                                    per group
-  5 second barrier wait                            per group
+  2 read phase (workers) / planning (planner)                                  per group
+  3 wait for the neighbours' reads                                              per group
+  4 write phase, with the loop's tail and the next group's HBM traffic          per group
+  5 wait for the writes and the plan (workers) / the workers' reads (planner)   per group
   6 after the loop -> end (ring and state stores)
   7 groups (count)
 
@@ -41,17 +41,23 @@ def main():
     # the worker loop
     body = sub(body, "#pragma unroll 1\n\t\tfor (uint32_t g = 0; g < nGrp; g++) {\n\t\t\tconst int  nb  =",
                "#pragma unroll 1\n\t\tfor (uint32_t g = 0; g < nGrp; g++) {\n\t\t\tpt[7]++;\n\t\t\tconst int  nb  =")
-    body = sub(body, "\t\t\t__syncthreads ();\n\t\t\t/* ---- write phase ---- */",
-               "\t\t\tt1 = RVP_T (); pt[2] += t1 - t0; t0 = t1;\n\t\t\t__syncthreads ();\n"
-               "\t\t\tt1 = RVP_T (); pt[3] += t1 - t0; t0 = t1;\n\t\t\t/* ---- write phase ---- */")
-    body = sub(body, "RVL_DLY[l]);\n\t\t\t__syncthreads ();\n\t\t}\n\t} else {",
-               "RVL_DLY[l]);\n\t\t\tt1 = RVP_T (); pt[4] += t1 - t0; t0 = t1;\n"
-               "\t\t\t__syncthreads ();\n\t\t\tt1 = RVP_T (); pt[5] += t1 - t0; t0 = t1;\n\t\t}\n\t} else {")
-    # the planner loop: planning as the "read phase", its two barriers
-    body = sub(body, "\t\t\t__syncthreads ();\n\t\t\t__syncthreads ();\n\t\t}\n",
-               "\t\t\tpt[7]++;\n\t\t\tt1 = RVP_T (); pt[2] += t1 - t0; t0 = t1;\n\t\t\t__syncthreads ();\n"
-               "\t\t\tt1 = RVP_T (); pt[3] += t1 - t0; t0 = t1;\n\t\t\t__syncthreads ();\n"
-               "\t\t\tt1 = RVP_T (); pt[5] += t1 - t0; t0 = t1;\n\t\t}\n")
+    body = sub(body, "\t\t\t\trvl_wait (sm.writeDone, n, (int)g + dR, P.errFlags);\n",
+               "\t\t\t\tt1 = RVP_T (); pt[4] += t1 - t0; t0 = t1;\n"
+               "\t\t\t\trvl_wait (sm.writeDone, n, (int)g + dR, P.errFlags);\n"
+               "\t\t\t\tt1 = RVP_T (); pt[5] += t1 - t0; t0 = t1;\n")
+    body = sub(body, "\t\t\trvl_publish (&sm.readDone[w], g + 1, n);",
+               "\t\t\trvl_publish (&sm.readDone[w], g + 1, n);\n\t\t\tt1 = RVP_T (); pt[2] += t1 - t0; t0 = t1;")
+    body = sub(body, "\t\t\t\trvl_wait (sm.readDone, n, (int)g + dW, P.errFlags);\n",
+               "\t\t\t\trvl_wait (sm.readDone, n, (int)g + dW, P.errFlags);\n"
+               "\t\t\t\tt1 = RVP_T (); pt[3] += t1 - t0; t0 = t1;\n")
+    body = sub(body, "\t\t\trvl_publish (&sm.writeDone[w], g + 1, n);\n",
+               "\t\t\trvl_publish (&sm.writeDone[w], g + 1, n);\n\t\t\tt1 = RVP_T (); pt[4] += t1 - t0; t0 = t1;\n")
+    # the planner loop: its wait for the workers' reads, then planning as the "read phase"
+    body = sub(body, "\t\t\t\trvl_wait (sm.readDone, n, n < RVL_G ? (int)g : RVL_NOWAIT, P.errFlags);\n",
+               "\t\t\t\tpt[7]++;\n\t\t\t\trvl_wait (sm.readDone, n, n < RVL_G ? (int)g : RVL_NOWAIT, P.errFlags);\n"
+               "\t\t\t\tt1 = RVP_T (); pt[5] += t1 - t0; t0 = t1;\n")
+    body = sub(body, "\t\t\t\trvl_publish (&sm.writeDone[RVL_G], g + 2, n);\n",
+               "\t\t\t\trvl_publish (&sm.writeDone[RVL_G], g + 2, n);\n\t\t\t\tt1 = RVP_T (); pt[2] += t1 - t0; t0 = t1;\n")
     body += ("\n\tt1 = RVP_T (); pt[6] += t1 - t0;\n"
              "\tif ((threadIdx.x & 63) == 0)\n\t\tfor (int k = 0; k < 8; k++)\n"
              "\t\t\tatomicAdd (&g_rvlprof[threadIdx.x >> 6][k], pt[k]);")

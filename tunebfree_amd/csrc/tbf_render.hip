@@ -1333,10 +1333,13 @@ k_rv_core (const tbf_launch P, const tbf_inst_const* __restrict__ cst)
  * group of RVL_G sub-blocks returns a value written before the group, and a write of
  * the group only ever replaces a value that the group's earlier samples read.  So all
  * reads of a group may precede all its writes, exactly as k_rv_core's reads of a
- * sub-block precede its writes; a worker's writes wait (barrier) for the reads of the
- * 72 samples before its first, which lie in the previous worker's sub-block.  The
+ * sub-block precede its writes; a worker's writes wait (readDone) for the reads of the
+ * 72 samples before its first, which lie in the two sub-blocks before its own.  The
  * one serial term, feedback(n - 1), crosses sub-blocks through LDS (carry) between the
- * read phase and the write phase.  Per sub-block the arithmetic is k_rv_core's: the
+ * read phase and the write phase.  A worker's reads of the next group wait (writeDone) for
+ * the writes up to its own sub-block of this group: with J = 11 g + w the sub-block's index,
+ * read (J) reads only times written by sub-blocks J - 31 .. J - 11.
+ * Per sub-block the arithmetic is k_rv_core's: the
  * same phases (closed form v0 + (n+1) D with the same start phases, or the literal
  * recurrence), the same sine rows, taps, Householder mix and allpasses. */
 #ifndef RVL_G
@@ -1375,9 +1378,41 @@ struct RvLds {
 	                                    * crossing a binade: the rows are computed inline) */
 	double      Dx[2][RVL_G][8];
 	double      carry[2][RVL_G][8];    /* feedback of sub-block j's last sample */
+	uint32_t    readDone[16];          /* [w]: the groups whose read phase worker w has finished ... */
+	uint32_t    writeDone[16];         /* ... and whose write phase; [RVL_G]: the groups the planner has planned */
 	tbf_rv_chan st;
 };
 static_assert (sizeof (RvLds) <= 160 * 1024, "k_rv_core_lds: a channel's rings fill gfx950's 160 KB of LDS");
+static_assert (RVL_G + 1 <= 16, "k_rv_core_lds: one counter per worker and one for the planner, polled by lanes 0..15");
+
+/* The phases of a group are ordered by counters in LDS instead of workgroup barriers: a wave
+ * publishes the groups it has finished a phase of (a release store after the phase's LDS
+ * accesses) and waits only for the waves whose data it touches (acquire loads, s_sleep between
+ * polls).  All waves of a workgroup are resident together, so a wait ends after a bounded
+ * number of polls; one that does not gives up, reports TBF_PATH_RV_SYNC and goes on (the output
+ * is then wrong, and the bit says so): no wait can hang the GPU. */
+#define RVL_POLLS (1 << 20)
+#define RVL_NOWAIT (-(1 << 30)) /* a lane's target offset where the wave does not wait for that lane's counter */
+__device__ __forceinline__ void rvl_publish (uint32_t* ctr, uint32_t v, int n)
+{
+	if (n == 0)
+		__hip_atomic_store (ctr, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+/* lane i < 16 polls ctr[i] until every lane's counter has reached its `need` */
+__device__ __forceinline__ void rvl_wait (uint32_t* ctr, int n, int need, uint32_t* errFlags)
+{
+	for (int k = 0;; k++) {
+		const int c = (int)__hip_atomic_load (&ctr[n & 15], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+		if (__all (c >= need))
+			break;
+		if (k == RVL_POLLS) {
+			if (n == 0)
+				atomicOr (errFlags, (uint32_t)TBF_PATH_RV_SYNC);
+			break;
+		}
+		__builtin_amdgcn_s_sleep (1);
+	}
+}
 
 /* the ring wrap / mirror branches are marked unlikely, so the common case falls through */
 #define RVL_RARE(x) __builtin_expect (!!(x), 0)
@@ -1581,6 +1616,11 @@ __device__ __forceinline__ void rvl_pair (const tbf_launch& P, const tbf_inst_co
 			sm.carry[1][RVL_G - 1][n] = sm.st.fb[n]; /* as the "previous group's" last feedback */
 		if (nGrp > 0)
 			rvl_plan (sm, vdl, (int)min ((uint32_t)RVL_G, nSub), 0, force, P.errFlags);
+		/* the pair's counters start again: no phase done, group 0 planned */
+		if (n < 16) {
+			sm.readDone[n]  = 0u;
+			sm.writeDone[n] = n == RVL_G ? 1u : 0u;
+		}
 	}
 	__syncthreads ();
 	int cntv = n < 12 ? sm.st.count[n] : 0;
@@ -1599,14 +1639,22 @@ __device__ __forceinline__ void rvl_pair (const tbf_launch& P, const tbf_inst_co
 	size_t po   = 0;
 	bool   pst  = false;
 	__syncthreads ();
-	/* the workers and the planner run separate loops with the same two barriers per group, so
-	 * the registers of one role are not held live across the other's code */
+	/* the workers and the planner run separate loops, so the registers of one role are not held
+	 * live across the other's code; the counters (rvl_publish / rvl_wait) order their phases */
 	if (w < RVL_G) {
 		/* this worker's first slot of each line in the group, wave-uniform (SGPRs) */
 		int cs[12];
 #pragma unroll
 		for (int l = 0; l < 12; l++)
 			cs[l] = rl (cw, l);
+		/* what lane i's counter must have reached, relative to the group g, before this worker
+		 * writes: the reads of the two sub-blocks before its own (they hold the 72 samples
+		 * before its first, and the nearer one its carry): workers w - 1 and w - 2 in group g,
+		 * or workers 10 and 9 in the group before ... */
+		const int dW = (n == w - 1 || n == w - 2) ? 1 : ((n == w + RVL_G - 1 || n == w + RVL_G - 2) && n < RVL_G) ? 0 : RVL_NOWAIT;
+		/* ... and before it reads: the writes of every sub-block up to its own of the group
+		 * before (workers <= w in group g - 1, the others in group g - 2), and the plan of group g */
+		const int dR = n <= w ? 0 : n < RVL_G ? -1 : n == RVL_G ? 1 : RVL_NOWAIT;
 #pragma unroll 1
 		for (uint32_t g = 0; g < nGrp; g++) {
 			const int  nb  = (int)min ((uint32_t)RVL_G, nSub - g * RVL_G);
@@ -1625,6 +1673,7 @@ __device__ __forceinline__ void rvl_pair (const tbf_launch& P, const tbf_inst_co
 			if (pst)
 				rv_st (&bout[po], pmix);
 			if (act) {
+				rvl_wait (sm.writeDone, n, (int)g + dR, P.errFlags);
 				/* the priority raised at a phase start and dropped part-way (here after the tap
 				 * reads), so the three workers of a SIMD progress together instead of in age order */
 				__builtin_amdgcn_s_setprio (1);
@@ -1733,10 +1782,15 @@ __device__ __forceinline__ void rvl_pair (const tbf_launch& P, const tbf_inst_co
 						sm.carry[par][w][l] = fb[l];
 				}
 			}
-			__syncthreads ();
+			rvl_publish (&sm.readDone[w], g + 1, n); /* a worker without a sub-block publishes too */
 			/* ---- write phase ---- */
 			if (act) {
-				__builtin_amdgcn_s_setprio (1);
+				rvl_wait (sm.readDone, n, (int)g + dW, P.errFlags);
+				/* the whole write phase above the read phases beside it on the SIMD: it is short,
+				 * and the next group's reads of this worker and of every later one wait for it
+				 * (at priority 1 for its first six writes only, as under the barriers, the kernel took
+				 * 8.2 ms alone per 512 blocks instead of 7.6: profiles/rvcore_sync) */
+				__builtin_amdgcn_s_setprio (2);
 				/* the previous sub-block's last feedback, all 8 lines read before any ring write */
 				const double* cp = w == 0 ? sm.carry[par ^ 1][RVL_G - 1] : sm.carry[par][w - 1];
 				double        cprv[8];
@@ -1750,17 +1804,18 @@ __device__ __forceinline__ void rvl_pair (const tbf_launch& P, const tbf_inst_co
 				/* feedback (n - 1): lane 0 takes the previous sub-block's last, the DPP move's old value */
 				rvl_write_s<RVL_DLY[0]> (sm.ring + RVL_LOFS[0], cs[0], n, ap[3] + lane_shr1_or (fb[0], cprv[0]));
 				rvl_write_s<RVL_DLY[1]> (sm.ring + RVL_LOFS[1], cs[1], n, ap[2] + lane_shr1_or (fb[1], cprv[1]));
-				__builtin_amdgcn_s_setprio (0);
 				rvl_write_s<RVL_DLY[2]> (sm.ring + RVL_LOFS[2], cs[2], n, ap[1] + lane_shr1_or (fb[2], cprv[2]));
 				rvl_write_s<RVL_DLY[3]> (sm.ring + RVL_LOFS[3], cs[3], n, ap[0] + lane_shr1_or (fb[3], cprv[3]));
 				rvl_write_s<RVL_DLY[4]> (sm.ring + RVL_LOFS[4], cs[4], n, ap[0] + lane_shr1_or (fb[4], cprv[4]));
 				rvl_write_s<RVL_DLY[5]> (sm.ring + RVL_LOFS[5], cs[5], n, ap[1] + lane_shr1_or (fb[5], cprv[5]));
 				rvl_write_s<RVL_DLY[6]> (sm.ring + RVL_LOFS[6], cs[6], n, ap[2] + lane_shr1_or (fb[6], cprv[6]));
 				rvl_write_s<RVL_DLY[7]> (sm.ring + RVL_LOFS[7], cs[7], n, ap[3] + lane_shr1_or (fb[7], cprv[7]));
+				__builtin_amdgcn_s_setprio (0);
 				/* the tap mix, stored at the start of the next group (see above) */
 				pmix = mix;
 				po   = o;
 			}
+			rvl_publish (&sm.writeDone[w], g + 1, n);
 			pst = act;
 			a0  = a0n;
 			a0n = nxt;
@@ -1768,12 +1823,13 @@ __device__ __forceinline__ void rvl_pair (const tbf_launch& P, const tbf_inst_co
 #pragma unroll
 			for (int l = 0; l < 12; l++)
 				cs[l] = wrap_slot (cs[l] + TBF_SUB * RVL_G, RVL_DLY[l]);
-			__syncthreads ();
 		}
 	} else {
 #pragma unroll 1
 		for (uint32_t g = 0; g < nGrp; g++) {
 			if (g + 1 < nGrp) {
+				/* the plan of group g + 1 replaces that of group g - 1: every worker has read it */
+				rvl_wait (sm.readDone, n, n < RVL_G ? (int)g : RVL_NOWAIT, P.errFlags);
 				/* the planner is the youngest wave of its SIMD: at equal priority the two
 				 * workers beside it took the issue slots first and every worker waited for
 				 * the plan at the barrier (tools/rvl_prof.py: 5.7k cycles per group against
@@ -1781,20 +1837,18 @@ __device__ __forceinline__ void rvl_pair (const tbf_launch& P, const tbf_inst_co
 				__builtin_amdgcn_s_setprio (2);
 				rvl_plan (sm, vdl, (int)min ((uint32_t)RVL_G, nSub - (g + 1) * RVL_G), (g & 1) ^ 1, force, P.errFlags);
 				__builtin_amdgcn_s_setprio (0);
+				rvl_publish (&sm.writeDone[RVL_G], g + 2, n);
 			}
-			__syncthreads ();
-			__syncthreads ();
 		}
 	}
 	if (pst)
 		rv_st (&bout[po], pmix);
-	/* state: counters after nSub * 64 steps, the last sample's feedback */
-	if (w == 0) {
-		if (n < 12)
-			sm.st.count[n] = (int)(((uint32_t)cntv + (uint64_t)nSub * TBF_SUB) % (uint32_t)(dlyv + 1));
-		if (n < 8 && nGrp > 0)
-			sm.st.fb[n] = sm.carry[(nGrp - 1) & 1][(nSub - 1) % RVL_G][n];
-	}
+	/* state: counters after nSub * 64 steps, the last sample's feedback (the carry that the
+	 * last sub-block's own worker wrote in its read phase) */
+	if (w == 0 && n < 12)
+		sm.st.count[n] = (int)(((uint32_t)cntv + (uint64_t)nSub * TBF_SUB) % (uint32_t)(dlyv + 1));
+	if (nGrp > 0 && (uint32_t)w == (nSub - 1) % RVL_G && n < 8)
+		sm.st.fb[n] = sm.carry[(nGrp - 1) & 1][w][n];
 	__syncthreads ();
 #pragma unroll
 	for (int l = 0; l < 12; l++) /* the canonical slots */

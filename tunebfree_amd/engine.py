@@ -112,7 +112,7 @@ class LoudnessResult(C.Structure):
 DEBUG_FORCE_SERIAL = 1
 # tbf_engine_config.whirl_out (include/tbf.h TBF_WHIRL_OUT_*): whirlProc3's mic mix, whirlProc's direct sum
 WHIRL_OUT_MIC, WHIRL_OUT_DIRECT = 0, 1
-PATH_VIB_SERIAL, PATH_WH_ANGLE, PATH_WH_MOTION, PATH_RV_PHASE, PATH_RV_WINDOW = 1, 2, 4, 8, 16
+PATH_VIB_SERIAL, PATH_WH_ANGLE, PATH_WH_MOTION, PATH_RV_PHASE, PATH_RV_WINDOW, PATH_RV_SYNC = 1, 2, 4, 8, 16, 32
 
 
 # every symbol include/tbf.h declares, with its ctypes signature
