@@ -845,7 +845,15 @@ int tbf_debug_limit_time (tbf_limiter* lim, int32_t enable, double* ms, uint64_t
  * tolerance; the hop energies are compared in bits.
  * State: 16 B x max_hops + 96 B per row.  It belongs to the meter object, not to an instance:
  * tbf_instances_* do not know it, tbf_debug_device_bytes does not count it, and it is not saved.
- * Left out: true-peak, loudness range, channel counts other than the pair, saving a meter. */
+ * Loudness range (EBU Tech 3342), computed on the host in double by tbf_loudness_range from the
+ * same N complete hops, u_h as above:
+ *     z_j = (serial ascending sum of u_j .. u_{j+29}) / (30*Hp), j = 0 .. N-30      short-term windows
+ *     l_j = -0.691 + 10*log10 (z_j)
+ *     absolute gate: l_j > -70;   relative gate: l_j > (-0.691 + 10*log10 (mean z over the absolutely
+ *     gated windows, an ascending serial sum)) - 20
+ *     s[0 .. n-1] the surviving l sorted ascending
+ *     LRA = s[floor ((n-1)*0.95 + 0.5)] - s[floor ((n-1)*0.10 + 0.5)];  windows = n;  LRA = 0.0 when n = 0
+ * Left out: channel counts other than the pair, saving a meter.  (True peak is the next section.) */
 typedef struct tbf_loudness tbf_loudness;
 typedef struct tbf_loudness_config {
 	uint32_t rate_hz, max_hops;
@@ -900,6 +908,98 @@ int tbf_debug_loudness_result (uint32_t rate_hz, const double* e, uint32_t n_hop
 int tbf_debug_loudness_grid (uint32_t n_rows, uint32_t* rows_per_group, uint32_t* tile_frames, uint32_t* lds_bytes);
 /* k_loud's own time, as tbf_debug_limit_time: one launch set per call that took frames */
 int tbf_debug_loudness_time (tbf_loudness* lm, int32_t enable, double* ms, uint64_t* launches);
+/* The loudness range in LU of the rows `rows` (n of them; NULL: all rows in order, n ignored) into
+ * lra, and the windows behind each into windows (may be NULL).  Waits as tbf_loudness_read.  -22: a
+ * NULL pointer, a row index >= n_rows. */
+int tbf_loudness_range (tbf_loudness* lm, uint32_t n, const uint32_t* rows, double* lra, uint32_t* windows);
+/* test hook: the range arithmetic alone, on n_hops EL, ER pairs in host memory; tbf_loudness_range
+ * calls the same code.  windows may be NULL. */
+int tbf_debug_loudness_range (uint32_t rate_hz, const double* e, uint32_t n_hops, double* lra, uint32_t* windows);
+
+/* ---- True-peak meter: oversampled inter-sample peaks of planes, on the device ----
+ * A stage beside any two float32 device planes: it reads them and writes only its own memory.  The
+ * limiter bounds the samples and k_pcm counts the samples that clip; this stage measures what lies
+ * between them, as ITU-R BS.1770-4 Annex 2 does.  Like the mixdown, the limiter and the loudness
+ * meter it is specified here, not restated from the reference, which has no meter (DESIGN.md
+ * section 7), and it is defined to the bit.
+ * Table: 4 phases x 12 taps, h[p][j] = k[p][j] / 8192, every coefficient exact in float32:
+ *     k[0] = {   14,  90, -161, 272,  -487, 1125, 7964,  -838, 390, -218, 122,  -68 }
+ *     k[1] = { -239, 240, -424, 730, -1364, 3810, 6388, -1641, 832, -477, 271, -155 }
+ *     k[2] = k[1] reversed,   k[3] = k[0] reversed
+ * (the annex's printed table: phase 0 is 0.0017089843750, 0.0109863281250, -0.0196533203125, ...).
+ * Parameter per meter, fixed at creation: oversample F in {1, 2, 4}.  The phases used are {0, 1, 2, 3}
+ * for F = 4, {0, 2} for F = 2 and none for F = 1.  (A caller picks F from its rate: 4 below 96 kHz, 2
+ * below 192 kHz, otherwise 1.)
+ * Per row, per channel, per input frame n: x[n] is the float32 sample and x[m] for m before the
+ * row's first frame since creation or reset is +0.0f.  For every phase p used:
+ *     acc = +0.0f;  for j = 0 .. 11 ascending:  acc = fmaf (h[p][j], x[n - j], acc);   y[n][p] = acc
+ *     inter_peak  = umax (inter_peak,  bits (y[n][p]) & 0x7fffffff)
+ *     sample_peak = umax (sample_peak, bits (x[n])    & 0x7fffffff)
+ * umax is the unsigned 32-bit maximum of the bit patterns of the magnitudes: on finite values the
+ * float maximum; Inf above every finite value and a NaN above Inf, so a NaN poisons its row and
+ * channel until reset and touches no other row; and, an integer maximum, exact in any order.  The tap
+ * order of each y is part of the definition: one float32 fmaf per tap, no contraction beyond it, no
+ * flushing.  The order in which the y are compared is not, which leaves the kernel free to be
+ * parallel over time.  A row's peaks are therefore the same bits however its frames are cut into
+ * calls.  A NaN's payload is not defined: a NaN result is compared as "is NaN", all else in bits.
+ * d_L == d_R is allowed: such a row is measured as a pair of equal channels.
+ * Read-out per row: sample_peak[2] and inter_peak[2] as floats (L, R), frames taken since reset, and
+ *     dbtp = 20*log10 (the largest of the four), in double on the host; -HUGE_VAL when that is 0,
+ *     NaN when it is a NaN.
+ * The samples are part of the maximum, so dbtp is never below the sample peak and F = 1 has a meaning.
+ * State: 200 B per row (two sides of 2 x 11 floats of history, four words of peaks, one record of
+ * the call).  It belongs to the meter object, not to an instance: tbf_instances_* do not know it,
+ * tbf_debug_device_bytes does not count it, and it is not saved.
+ * Left out: detection inside the limiter, a per-hop series, surround weights, saving a meter. */
+typedef struct tbf_true_peak tbf_true_peak;
+typedef struct tbf_true_peak_config {
+	uint32_t oversample, reserved;
+} tbf_true_peak_config;
+typedef struct tbf_true_peak_result {
+	float    sample_peak[2], inter_peak[2]; /* L, R */
+	uint64_t frames;
+	double   dbtp; /* or -HUGE_VAL, or NaN */
+} tbf_true_peak_result;
+/* A meter of n_rows rows on e's device; e owns it: tbf_engine_destroy releases the ones still
+ * alive.  -22: a NULL pointer, an oversample not in {1, 2, 4}, n_rows == 0.  A host-only engine
+ * validates, then returns -19.  -12 when the device cannot hold the state. */
+int tbf_true_peak_create (tbf_engine* e, uint32_t n_rows, const tbf_true_peak_config* cfg, tbf_true_peak** out);
+int tbf_true_peak_destroy (tbf_true_peak* tp);
+/* The rows `rows` (host memory, n of them; NULL: all rows, n ignored) start anew, ordered on
+ * `stream` (NULL: the engine's own).  -22: a row index >= n_rows. */
+int tbf_true_peak_reset (tbf_true_peak* tp, uint32_t n, const uint32_t* rows, void* stream);
+/* One call: the meter's n_rows rows of d_L / d_R (device memory, row r at r * in_stride floats; any
+ * 4-byte-aligned pointers and odd strides; d_L == d_R allowed) on `stream` (NULL: the engine's
+ * own), ordered as tbf_render_device.  The planes are only read.  Row r takes counts[r] <= frames
+ * frames (counts: host memory, uploaded before the call returns), or `frames` when counts is NULL;
+ * a row with count 0 keeps its state.  Calls on one meter are the caller's to order.
+ * -22, with a tbf_last_error that names the argument: a NULL pointer, in_stride < frames, a
+ * misaligned pointer, counts[r] > frames, more than 2^31 - 1 tiles of 1024 frames over all rows.
+ * Validation comes first: a refused call moves no state. */
+int tbf_true_peak_device (tbf_true_peak* tp, const float* d_L, const float* d_R, uint64_t in_stride, uint32_t frames,
+                          const uint32_t* counts, void* stream);
+/* The results of the rows `rows` (n of them; NULL: all rows in order, n ignored) into out.  Waits
+ * for the meter's last call on its stream.  -22: a NULL pointer, a row index >= n_rows. */
+int tbf_true_peak_read (tbf_true_peak* tp, uint32_t n, const uint32_t* rows, tbf_true_peak_result* out);
+/* test hook: the table h[p][j] as 48 floats, phase-major */
+int tbf_debug_true_peak_table (float* h48);
+/* test hook: the host restatement of the definition on one row, from the header the kernel is
+ * built from (csrc/tbf_tpeak.h): n frames of L / R (L == R allowed) behind hist22 = L's last 11
+ * frames, oldest first, followed by R's (read and then replaced by the last 11 of history ||
+ * frames) into peaks4 = the bit patterns {sample L, sample R, inter L, inter R} (read and then
+ * replaced).  y NULL, or room for every y[n][p]: L's n * P floats, frame-major, followed by R's,
+ * P = 4, 2 or 0 phases for oversample 4, 2, 1.  Needs no engine and no device. */
+int tbf_debug_true_peak_ref (const tbf_true_peak_config* cfg, const float* L, const float* R, uint64_t n, float* hist22,
+                             uint32_t* peaks4, float* y);
+/* test hook: the read-out's dbtp of four peak words */
+int tbf_debug_true_peak_dbtp (const uint32_t* peaks4, double* dbtp);
+/* test hook: how k_tpeak lays a call of `frames` frames on n_rows rows out: the frames of a row a
+ * workgroup takes (the tile), the consecutive frames of a lane, the workgroups of the launch and a
+ * workgroup's LDS bytes.  No layout changes a bit.  Any out pointer may be NULL. */
+int tbf_debug_true_peak_grid (uint32_t n_rows, uint32_t frames, uint32_t* tile_frames, uint32_t* frames_per_lane, uint64_t* groups,
+                              uint32_t* lds_bytes);
+/* k_tpeak's own time, as tbf_debug_loudness_time: one launch per call that took frames */
+int tbf_debug_true_peak_time (tbf_true_peak* tp, int32_t enable, double* ms, uint64_t* launches);
 
 int tbf_synchronize (tbf_engine* e);
 /* Which exact-but-slow paths the kernels took since the engine's first render (cumulative,

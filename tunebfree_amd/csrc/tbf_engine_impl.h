@@ -31,6 +31,7 @@
 #include "tbf_mix.h"
 #include "tbf_pcm.h"
 #include "tbf_resample.h"
+#include "tbf_tpeak.h"
 #include "tbf_types.h"
 
 namespace tbf {
@@ -334,6 +335,31 @@ struct tbf_loudness {
 	}
 };
 
+/* A true-peak meter (tbf_true_peak_create, csrc/tbf_tpeak.cpp): per row two sides of 2 x 11 floats
+ * of history, of which rows[r].side is the live one, and four words of peaks.  A call reads the live
+ * side, writes the other and flips the side of every row that took frames (k_tpeak,
+ * csrc/tbf_tpeak.hip).  The host knows every row's position: pos[r] frames since creation or reset. */
+struct tbf_true_peak {
+	tbf_engine*                eng = nullptr;
+	tbf_true_peak_config       cfg = {0u, 0u};
+	uint32_t                   nRows = 0;
+	DevBuf<float>              hist;  /* [row][side][channel][11] */
+	DevBuf<uint32_t>           peaks; /* [row]{sample L, sample R, inter L, inter R}: bit patterns of magnitudes */
+	DevBuf<tbf_tpeak_row>      drows; /* the call's rows on the device */
+	std::vector<tbf_tpeak_row> rows;  /* .side persists, .count is the call's */
+	std::vector<uint64_t>      pos;   /* frames a row has taken */
+	hipStream_t                last = nullptr; /* the stream of the meter's last call or reset */
+	bool                       timeOn = false; /* tbf_debug_true_peak_time: an event pair around every launch */
+	std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
+	~tbf_true_peak ()
+	{
+		for (auto& p : tev) {
+			(void)hipEventDestroy (p.first);
+			(void)hipEventDestroy (p.second);
+		}
+	}
+};
+
 struct tbf_engine {
 	tbf_engine_config                       cfg;
 	Config                                  conf; /* cfg keys (tbf_config_set) for tables built from now on */
@@ -579,6 +605,8 @@ struct tbf_engine {
 	/* the loudness meters still alive (csrc/tbf_loud.cpp), likewise, and behind the limiters for the
 	 * same reason */
 	std::vector<std::unique_ptr<tbf_loudness>> loudness;
+	/* the true-peak meters still alive (csrc/tbf_tpeak.cpp), likewise, and behind the loudness meters */
+	std::vector<std::unique_ptr<tbf_true_peak>> truePeaks;
 };
 
 namespace tbf {

@@ -131,6 +131,48 @@ void loud_result (uint32_t rate, const double* e, uint32_t n, tbf_loudness_resul
 	}
 }
 
+/* the loudness range of EBU Tech 3342 over n EL, ER pairs (include/tbf.h) */
+void loud_range (uint32_t rate, const double* e, uint32_t n, double* lra, uint32_t* windows)
+{
+	const double Hp = (double)(rate / 10u);
+	*lra            = 0.0;
+	if (windows)
+		*windows = 0u;
+	if (n < 30u)
+		return;
+	const uint32_t      nw = n - 29u;
+	std::vector<double> u (n), z (nw), l (nw);
+	for (uint32_t h = 0; h < n; h++)
+		u[h] = e[2u * h] + e[2u * h + 1u];
+	double   sumAbs = 0.0;
+	uint32_t nAbs   = 0;
+	for (uint32_t j = 0; j < nw; j++) {
+		double s = u[j];
+		for (uint32_t i = 1; i < 30u; i++)
+			s = s + u[j + i];
+		z[j] = s / (30.0 * Hp);
+		l[j] = lufs (z[j]);
+		if (l[j] > -70.0) {
+			sumAbs = sumAbs + z[j];
+			nAbs++;
+		}
+	}
+	if (!nAbs)
+		return;
+	const double        gate = lufs (sumAbs / (double)nAbs) - 20.0;
+	std::vector<double> s;
+	for (uint32_t j = 0; j < nw; j++)
+		if (l[j] > -70.0 && l[j] > gate)
+			s.push_back (l[j]);
+	if (s.empty ())
+		return;
+	std::sort (s.begin (), s.end ());
+	const double m = (double)(s.size () - 1u);
+	*lra           = s[(size_t)floor (m * 0.95 + 0.5)] - s[(size_t)floor (m * 0.10 + 0.5)];
+	if (windows)
+		*windows = (uint32_t)s.size ();
+}
+
 /* the meter's slot in its engine's list, or the list's end */
 std::vector<std::unique_ptr<tbf_loudness>>::iterator slotOf (tbf_loudness* lm)
 {
@@ -415,6 +457,44 @@ int tbf_debug_loudness_result (uint32_t rate_hz, const double* e, uint32_t n_hop
 	if (n_hops && !e)
 		return fail (-22, "loudness: e is NULL");
 	loud_result (rate_hz, e, n_hops, out);
+	return 0;
+}
+
+int tbf_loudness_range (tbf_loudness* lm, uint32_t n, const uint32_t* rows, double* lra, uint32_t* windows)
+{
+	if (!lm)
+		return fail (-22, "loudness: lm is NULL");
+	if (!lra)
+		return fail (-22, "loudness: lra is NULL");
+	if (!rows)
+		n = lm->nRows;
+	for (uint32_t k = 0; rows && k < n; k++)
+		if (rows[k] >= lm->nRows)
+			return fail (-22, "loudness: rows[" + std::to_string (k) + "] " + std::to_string (rows[k]) + " is no row of n_rows " +
+			                      std::to_string (lm->nRows));
+	if (int rc = settle (lm))
+		return rc;
+	std::vector<double> e;
+	for (uint32_t k = 0; k < n; k++) {
+		const uint32_t r = rows ? rows[k] : k;
+		const uint32_t N = (uint32_t)(lm->pos[r] / lm->Hp);
+		e.resize ((size_t)N * 2u);
+		if (int rc = fetch (lm, r, N, e.data ()))
+			return rc;
+		loud_range (lm->cfg.rate_hz, e.data (), N, lra + k, windows ? windows + k : nullptr);
+	}
+	return 0;
+}
+
+int tbf_debug_loudness_range (uint32_t rate_hz, const double* e, uint32_t n_hops, double* lra, uint32_t* windows)
+{
+	if (int rc = checkRate (rate_hz))
+		return rc;
+	if (!lra)
+		return fail (-22, "loudness: lra is NULL");
+	if (n_hops && !e)
+		return fail (-22, "loudness: e is NULL");
+	loud_range (rate_hz, e, n_hops, lra, windows);
 	return 0;
 }
 

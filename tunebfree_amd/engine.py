@@ -108,6 +108,18 @@ class LoudnessResult(C.Structure):
                 ("hops", C.c_uint32), ("blocks", C.c_uint32), ("gated", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class TruePeakConfig(C.Structure):
+    """tbf_true_peak_config: the oversampling factor (1, 2 or 4)"""
+    _fields_ = [("oversample", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TruePeakResult(C.Structure):
+    """tbf_true_peak_result: the largest sample and interpolated magnitudes of L and R, the frames
+    taken and 20 log10 of the largest of the four (-inf for silence, NaN for a NaN); arrays of them
+    are TRUE_PEAK_RESULT_DTYPE records"""
+    _fields_ = [("sample_peak", C.c_float * 2), ("inter_peak", C.c_float * 2), ("frames", C.c_uint64), ("dbtp", C.c_double)]
+
+
 # tbf_engine_config.debug_flags / tbf_error_flags bits (include/tbf.h)
 DEBUG_FORCE_SERIAL = 1
 # tbf_engine_config.whirl_out (include/tbf.h TBF_WHIRL_OUT_*): whirlProc3's mic mix, whirlProc's direct sum
@@ -204,6 +216,12 @@ SIGNATURES = {
     "tbf_loudness_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tbf_loudness_read": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tbf_loudness_hops": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, _u32p]),
+    "tbf_loudness_range": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tbf_true_peak_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(TruePeakConfig), C.POINTER(C.c_void_p)]),
+    "tbf_true_peak_destroy": (C.c_int, [C.c_void_p]),
+    "tbf_true_peak_reset": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tbf_true_peak_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tbf_true_peak_read": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
 }
 
 # tbf_engine_config.chain_mode of the effects-only chains (include/tbf.h TBF_CHAIN_FX*)
@@ -368,10 +386,92 @@ class Loudness:
         _check(f(self._h, 0, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
+    def range(self, rows=None):
+        """tbf_loudness_range: (loudness range in LU [k] float64, the short-term windows behind it [k]
+        uint32) of the rows (None: all), after the meter's last call has passed its stream"""
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        k = self.n_rows if r is None else len(r)
+        lra, win = np.zeros(k, np.float64), np.zeros(k, np.uint32)
+        _check(self._lib.tbf_loudness_range(self._h, 0 if r is None else len(r), None if r is None else r.ctypes.data,
+                                            lra.ctypes.data, win.ctypes.data))
+        return lra, win
+
     def close(self):
         """tbf_loudness_destroy (the engine does it for the meters still alive when it closes)"""
         if self._h and getattr(self._eng, "_h", None):
             _check(self._lib.tbf_loudness_destroy(self._h))
+        self._h = None
+
+
+def true_peak_oversample(rate_hz):
+    """the oversampling factor of BS.1770-4 Annex 2 for a rate: 4 below 96 kHz, 2 below 192 kHz, else 1"""
+    return 4 if rate_hz < 96000 else 2 if rate_hz < 192000 else 1
+
+
+class TruePeak:
+    """A true-peak meter (Engine.true_peak): n_rows rows of sample peaks and of the peaks of the
+    BS.1770-4 Annex 2 interpolator beside any two device planes; its state belongs to it, not to the
+    engine's instances."""
+
+    def __init__(self, eng, handle, n_rows, cfg):
+        self._eng, self._lib, self._h = eng, eng._lib, handle
+        self.n_rows, self.oversample = n_rows, cfg.oversample
+
+    def measure_device(self, L_ptr, R_ptr, in_stride, frames, counts=None, stream=None):
+        """tbf_true_peak_device: the meter's rows of the device planes L_ptr / R_ptr (row r at
+        r * in_stride floats; L_ptr == R_ptr: a pair of equal channels) take `frames` frames, or
+        counts[r] (host array) of them; the planes are only read."""
+        c = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+        if c is not None and len(c) != self.n_rows:
+            raise ValueError(f"{len(c)} counts for {self.n_rows} rows")
+        _check(self._lib.tbf_true_peak_device(
+            self._h, None if L_ptr is None else C.c_void_p(int(L_ptr)), None if R_ptr is None else C.c_void_p(int(R_ptr)),
+            int(in_stride), int(frames), None if c is None else c.ctypes.data,
+            None if stream is None else C.c_void_p(int(stream))))
+
+    def read(self, rows=None):
+        """tbf_true_peak_read: TRUE_PEAK_RESULT_DTYPE records of the rows (None: all), after the
+        meter's last call has passed its stream"""
+        from .params import TRUE_PEAK_RESULT_DTYPE
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        out = np.zeros(self.n_rows if r is None else len(r), TRUE_PEAK_RESULT_DTYPE)
+        _check(self._lib.tbf_true_peak_read(self._h, 0 if r is None else len(r), None if r is None else r.ctypes.data,
+                                            out.ctypes.data))
+        return out
+
+    def gains(self, ceiling_dbtp):
+        """per row the float32 gain 10**((ceiling_dbtp - dbtp) / 20) that brings its true peak down to
+        the ceiling, computed in double, capped at 1.0 and then rounded; 1.0 for a silent row (and
+        for a row whose peak is a NaN, which no gain mends)"""
+        d = self.read()["dbtp"]
+        g = np.ones(self.n_rows, np.float64)
+        ok = np.isfinite(d)
+        g[ok] = np.minimum(10.0 ** ((float(ceiling_dbtp) - d[ok]) / 20.0), 1.0)
+        g[np.isposinf(d)] = 0.0
+        return g.astype(np.float32)
+
+    def reset(self, rows=None, stream=None):
+        """tbf_true_peak_reset: the rows (None: all) start anew, ordered on the stream"""
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        _check(self._lib.tbf_true_peak_reset(self._h, 0 if r is None else len(r), None if r is None else r.ctypes.data,
+                                             None if stream is None else C.c_void_p(int(stream))))
+
+    def timing(self, enable=None):
+        """tbf_debug_true_peak_time: enable True / False switches the event pair around every call's
+        launch on / off; None returns (milliseconds, launches) since the last query."""
+        f = self._lib.tbf_debug_true_peak_time
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_uint64)]
+        if enable is not None:
+            _check(f(self._h, 1 if enable else -1, None, None))
+            return None
+        ms, n = C.c_double(), C.c_uint64()
+        _check(f(self._h, 0, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def close(self):
+        """tbf_true_peak_destroy (the engine does it for the meters still alive when it closes)"""
+        if self._h and getattr(self._eng, "_h", None):
+            _check(self._lib.tbf_true_peak_destroy(self._h))
         self._h = None
 
 
@@ -1241,6 +1341,83 @@ class Engine:
         g, t, b = C.c_uint32(), C.c_uint32(), C.c_uint32()
         _check(f(int(n_rows), C.byref(g), C.byref(t), C.byref(b)))
         return g.value, t.value, b.value
+
+    @staticmethod
+    def loudness_range(rate_hz, energies):
+        """tbf_debug_loudness_range: the loudness range alone on [hops, 2] energies; (LRA in LU, the
+        short-term windows behind it)"""
+        f = load_library().tbf_debug_loudness_range
+        f.restype, f.argtypes = C.c_int, [C.c_uint32, C.c_void_p, C.c_uint32, _dp, _u32p]
+        e = np.ascontiguousarray(energies, dtype=np.float64).reshape(-1, 2)
+        lra, win = C.c_double(), C.c_uint32()
+        _check(f(int(rate_hz), e.ctypes.data if len(e) else None, len(e), C.byref(lra), C.byref(win)))
+        return lra.value, win.value
+
+    def true_peak(self, n_rows, rate_hz=None, oversample=None):
+        """tbf_true_peak_create: a true-peak meter of n_rows rows on this engine's device, at the
+        oversampling factor `oversample` (1, 2 or 4) or the one of rate_hz (None: the engine's rate):
+        4 below 96 kHz, 2 below 192 kHz, else 1; the engine releases it when it closes"""
+        if oversample is None:
+            oversample = true_peak_oversample(self.sample_rate if rate_hz is None else rate_hz)
+        cfg = TruePeakConfig(int(oversample), 0)
+        h = C.c_void_p()
+        _check(self._lib.tbf_true_peak_create(self._h, int(n_rows), C.byref(cfg), C.byref(h)))
+        return TruePeak(self, h, int(n_rows), cfg)
+
+    @staticmethod
+    def true_peak_table():
+        """tbf_debug_true_peak_table: h[p][j], [4, 12] float32"""
+        f = load_library().tbf_debug_true_peak_table
+        f.restype, f.argtypes = C.c_int, [C.c_void_p]
+        h = np.zeros((4, 12), np.float32)
+        _check(f(h.ctypes.data))
+        return h
+
+    @staticmethod
+    def true_peak_ref(L, R, oversample=4, hist=None, peaks=None, want_y=False):
+        """tbf_debug_true_peak_ref: the host restatement of the meter on one row (no device needed):
+        L, R [n] float32 (the same array twice: equal channels), hist None (a new row) or the 22
+        floats and peaks None or the 4 words an earlier call returned.  Returns (peaks [4] uint32:
+        the bit patterns of sample L, sample R, inter L, inter R; hist [22] float32), and with
+        want_y also y [2, n, phases] float32."""
+        f = load_library().tbf_debug_true_peak_ref
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(TruePeakConfig), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        same = L is R
+        L = np.ascontiguousarray(L, dtype=np.float32)
+        R = L if same else np.ascontiguousarray(R, dtype=np.float32)
+        if L.ndim != 1 or L.shape != R.shape:
+            raise ValueError(f"rows of shape {L.shape} and {R.shape}: want two of [n]")
+        cfg = TruePeakConfig(int(oversample), 0)
+        h = np.zeros(22, np.float32) if hist is None else np.array(hist, np.float32)
+        p = np.zeros(4, np.uint32) if peaks is None else np.array(peaks, np.uint32)
+        if h.shape != (22,) or p.shape != (4,):
+            raise ValueError("hist: want 22 floats; peaks: want 4 words")
+        ph = {4: 4, 2: 2}.get(int(oversample), 0)
+        y = np.full((2, len(L), ph), np.nan, np.float32) if want_y else None
+        _check(f(C.byref(cfg), L.ctypes.data, R.ctypes.data, len(L), h.ctypes.data, p.ctypes.data,
+                 None if y is None else y.ctypes.data))
+        return (p, h, y) if want_y else (p, h)
+
+    @staticmethod
+    def true_peak_dbtp(peaks):
+        """tbf_debug_true_peak_dbtp: the read-out's dbtp of four peak words"""
+        f = load_library().tbf_debug_true_peak_dbtp
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, _dp]
+        p = np.ascontiguousarray(peaks, dtype=np.uint32).reshape(4)
+        d = C.c_double()
+        _check(f(p.ctypes.data, C.byref(d)))
+        return d.value
+
+    @staticmethod
+    def true_peak_grid(n_rows=1, frames=0):
+        """tbf_debug_true_peak_grid: (frames of a row per workgroup, frames per lane, workgroups of a
+        call of `frames` frames on n_rows rows, LDS bytes per workgroup) of k_tpeak"""
+        f = load_library().tbf_debug_true_peak_grid
+        f.restype, f.argtypes = C.c_int, [C.c_uint32, C.c_uint32, _u32p, _u32p, C.POINTER(C.c_uint64), _u32p]
+        t, g, n, b = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_uint32()
+        _check(f(int(n_rows), int(frames), C.byref(t), C.byref(g), C.byref(n), C.byref(b)))
+        return t.value, g.value, n.value, b.value
 
     def synchronize(self):
         _check(self._lib.tbf_synchronize(self._h))

@@ -43,6 +43,10 @@ LIMIT_METER_DTYPE = np.dtype([("min_gain", "<f4"), ("reduced", "<u4"), ("clamped
 LOUDNESS_RESULT_DTYPE = np.dtype([("integrated", "<f8"), ("momentary_max", "<f8"), ("short_term_max", "<f8"),
                                   ("hops", "<u4"), ("blocks", "<u4"), ("gated", "<u4"), ("reserved", "<u4")])
 
+# the true-peak meter (Engine.true_peak): tbf_true_peak_result as a numpy record (32 B, as the C struct)
+TRUE_PEAK_RESULT_DTYPE = np.dtype([("sample_peak", "<f4", (2,)), ("inter_peak", "<f4", (2,)), ("frames", "<u8"),
+                                   ("dbtp", "<f8")])
+
 
 def mix_rows(bus, gain=1.0, pan=0.0):
     """tbf_mix_row records for Engine.mix_device / .render_mix / .process_mix: row r goes to bus
