@@ -432,3 +432,20 @@ def test_gpu_cabinet_memory_contract(chain):
         for k, rows in got.items():
             same(rows[:, :per], ref[k], f"chain {chain} wet {wet} rotors {rotors}: odd stride rows, {k}")
             assert (rows[:, per:] == fill).all() and raw[k][0] == fill, f"{k}: sentinel overwritten"
+
+
+# ---------------------------------------------------------------- 8. timing
+def test_gpu_cabinet_time():
+    """cabinet_time counts k_cabinet's launches while it is on, hands them out once, and counts
+    nothing while it is off: one instance, one block, the one-tap response"""
+    eng = engine(FULL, responses(1), n=1)
+    eng.cabinet_time(True)
+    for _ in range(2):
+        eng.render_cabinet(1)
+    ms, n = eng.cabinet_time()
+    assert n == 2 and ms > 0.0
+    assert eng.cabinet_time() == (0.0, 0)
+    eng.cabinet_time(False)
+    eng.render_cabinet(1)
+    assert eng.cabinet_time() == (0.0, 0)
+    eng.close()

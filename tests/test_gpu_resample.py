@@ -443,3 +443,20 @@ def test_gpu_resample_device_bytes(fi, fo):
     assert eng.device_bytes()[0] - plain.device_bytes()[0] == (N - 1) * share
     eng.close()
     plain.close()
+
+
+# ---------------------------------------------------------------- 7. timing
+def test_gpu_resample_time():
+    """resample_time counts k_resample's launches while it is on, hands them out once, and counts
+    nothing while it is off: one instance, one block, the pair with the shortest filter (T 64)"""
+    eng = engine(44100, 48000, n=1)
+    eng.resample_time(True)
+    for _ in range(2):
+        eng.render_resampled(1)
+    ms, n = eng.resample_time()
+    assert n == 2 and ms > 0.0
+    assert eng.resample_time() == (0.0, 0)
+    eng.resample_time(False)
+    eng.render_resampled(1)
+    assert eng.resample_time() == (0.0, 0)
+    eng.close()

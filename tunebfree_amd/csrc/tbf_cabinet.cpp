@@ -11,8 +11,8 @@
  *
  * Scratch: with the caller's rotor planes (rotors != NULL) there is none.  Without them the
  * four planes go to engine scratch (tbf_engine.rotBuf), 16 B per instance and sample, and the
- * call is cut into pieces of at most TBF_CAB_PIECE blocks, so the scratch never exceeds
- * n x TBF_CAB_PIECE x 128 x 16 B (2.1 GB at 4096 instances); the pieces render what one call
+ * call is cut into pieces of at most TBF_STAGE_PIECE blocks, so the scratch never exceeds
+ * n x TBF_STAGE_PIECE x 128 x 16 B (2.1 GB at 4096 instances); the pieces render what one call
  * renders, bit for bit, like any other cut.  -12 when the device cannot hold it.
  * The mix (convolution.mix) is a host control: k_cabinet reads it per instance (wet0, uploaded
  * when it changed) or, in a call in which a mix event lands, per instance and block (wetBlk).
@@ -30,24 +30,12 @@
 
 extern "C" int tbf_launch_cabinet (const tbf_cab_launch* P, hipStream_t stream);
 extern "C" int tbf_chain_stages (uint32_t chain);
-extern "C" int tbf_chain_first_stage (uint32_t chain);
 
 using namespace tbf;
-
-#define HIPCHK(x)                                                                        \
-	do {                                                                                 \
-		hipError_t _e = (x);                                                             \
-		if (_e != hipSuccess)                                                            \
-			return fail (-5, std::string (#x ": ") + hipGetErrorString (_e));           \
-	} while (0)
-
-/* blocks per piece of a call that renders its rotor planes into engine scratch */
-#define TBF_CAB_PIECE 256u
 
 namespace {
 
 bool chainWhirl (uint32_t chain) { return tbf_chain_stages (chain) == TBF_NSTAGES; }
-bool chainFx (uint32_t chain) { return tbf_chain_first_stage (chain) > 0; }
 
 /* H_k = FFT-256 of taps [128 k, 128 k + 128) zero-padded, in double, rounded to float, packed
  * (csrc/tbf_cabinet.h); tw: cos and -sin of 2 pi j / 256 */
@@ -118,11 +106,6 @@ int uploadTables (tbf_engine* e)
 	return 0;
 }
 
-struct Range {
-	const float* p;
-	uint64_t     stride;
-};
-
 /* The checks of the cabinet calls, all before anything renders or steps (in: the effects-only
  * calls' input rows); pointers are compared on the host only. */
 int cabinetArgs (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, bool fx, const float* in,
@@ -147,27 +130,18 @@ int cabinetArgs (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t 
 	if (fx && inStride < per)
 		return fail (-22, "in_stride smaller than nblocks*128");
 	const uint64_t n = e->inst.size ();
-	if (n && per) { /* [first float, one past the last float) of each range, pairwise */
-		Range r[9];
-		int   nr = 0;
-		r[nr++]  = {cab->L, cab->stride};
-		r[nr++]  = {cab->R, cab->stride};
-		if (cab->wetL) {
-			r[nr++] = {cab->wetL, cab->stride};
-			r[nr++] = {cab->wetR, cab->stride};
-		}
+	{ /* every range against every other; an absent wet pair is empty, and without instances or blocks all are */
+		Span r[9];
+		int  nr = 0;
+		for (const float* p : {cab->L, cab->R, cab->wetL, cab->wetR})
+			r[nr++] = rowsSpan (p, n, cab->stride * 4, per * 4);
 		if (rot)
 			for (const float* p : {rot->hornL, rot->hornR, rot->drumL, rot->drumR})
-				r[nr++] = {p, rot->stride};
+				r[nr++] = rowsSpan (p, n, rot->stride * 4, per * 4);
 		if (fx)
-			r[nr++] = {in, inStride};
-		for (int a = 0; a < nr; a++)
-			for (int b = a + 1; b < nr; b++) {
-				const uintptr_t a0 = (uintptr_t)r[a].p, a1 = (uintptr_t)(r[a].p + (n - 1) * r[a].stride + per);
-				const uintptr_t b0 = (uintptr_t)r[b].p, b1 = (uintptr_t)(r[b].p + (n - 1) * r[b].stride + per);
-				if (a0 < b1 && b0 < a1)
-					return fail (-22, "input, cabinet and rotor ranges overlap");
-			}
+			r[nr++] = rowsSpan (in, n, inStride * 4, per * 4);
+		if (anyOverlap (r, nr))
+			return fail (-22, "input, cabinet and rotor ranges overlap");
 	}
 	if (int rc = eventsInOrder (ev, nev))
 		return rc;
@@ -236,7 +210,7 @@ int cabinetDevice (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_
 	const uint32_t       n = (uint32_t)e->inst.size ();
 	if (n == 0 || nblocks == 0) /* nothing renders and no event applies, as in every render call */
 		return 0;
-	const uint32_t piece = rot ? nblocks : std::min (nblocks, TBF_CAB_PIECE);
+	const uint32_t piece = rot ? nblocks : std::min (nblocks, TBF_STAGE_PIECE);
 	tbf_rotor_out  planes;
 	if (rot)
 		planes = *rot;
@@ -248,31 +222,15 @@ int cabinetDevice (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_
 		}
 		planes = {e->rotBuf.p, e->rotBuf.p + plane, e->rotBuf.p + 2 * plane, e->rotBuf.p + 3 * plane, (uint64_t)piece * TBF_BLK};
 	}
-	std::vector<tbf_event> pev;
-	uint32_t               evi = 0;
-	for (uint32_t p0 = 0; p0 < nblocks; p0 += piece) {
-		const uint32_t len  = std::min (piece, nblocks - p0);
-		const bool     last = p0 + len == nblocks;
-		/* the piece's events, their blocks counted from the piece; the last piece takes those
-		 * at or beyond the call's end too, which apply after it */
-		uint32_t evEnd = evi;
-		while (evEnd < nev && (last || ev[evEnd].block < p0 + len))
-			evEnd++;
-		const tbf_event* pe = ev + evi;
-		if (p0 && evEnd > evi) {
-			pev.assign (ev + evi, ev + evEnd);
-			for (tbf_event& v : pev)
-				v.block -= p0;
-			pe = pev.data ();
-		}
+	for (Pieces pc (ev, nev, nblocks, piece); pc.next ();) {
+		const uint32_t p0 = pc.p0, len = pc.len;
 		tbf_cab_launch P;
 		memset (&P, 0, sizeof (P));
-		if (int rc = stageMix (e, pe, evEnd - evi, len, s, P))
+		if (int rc = stageMix (e, pc.pe, pc.npe, len, s, P))
 			return rc;
-		if (int rc = rotorRender (e, len, evEnd > evi ? pe : nullptr, evEnd - evi, dIn ? dIn + (size_t)p0 * TBF_BLK : nullptr,
-		                          inStride, planes, s))
+		if (int rc = rotorRender (e, len, pc.npe ? pc.pe : nullptr, pc.npe, dIn ? dIn + (size_t)p0 * TBF_BLK : nullptr, inStride,
+		                          planes, s))
 			return rc;
-		evi = evEnd;
 		const size_t off = (size_t)p0 * TBF_BLK;
 		P.horn[0]   = planes.hornL;
 		P.horn[1]   = planes.hornR;
@@ -293,18 +251,13 @@ int cabinetDevice (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_
 		P.nb        = len;
 		P.K         = c.K;
 		P.R         = TBF_CAB_RING (c.K);
-		hipEvent_t t0 = nullptr, t1 = nullptr;
-		if (c.timeOn) { /* tbf_debug_cabinet_time: k_cabinet between two events on its stream */
-			HIPCHK (hipEventCreate (&t0));
-			HIPCHK (hipEventCreate (&t1));
-			HIPCHK (hipEventRecord (t0, s));
-		}
+		StageTimer::Guard tg (c.timer, s, "cabinet"); /* tbf_debug_cabinet_time: k_cabinet between two events on its stream */
+		if (int rc = tg.begin ())
+			return rc;
 		if (tbf_launch_cabinet (&P, s))
 			return fail (-5, std::string ("k_cabinet launch failed: ") + hipGetErrorString (hipGetLastError ()));
-		if (c.timeOn) {
-			HIPCHK (hipEventRecord (t1, s));
-			c.tev.push_back ({t0, t1});
-		}
+		if (int rc = tg.end ())
+			return rc;
 		c.launches++;
 	}
 	return 0;
@@ -327,7 +280,8 @@ int cabinetHost (tbf_engine* e, uint32_t nblocks, const float* in, uint64_t inSt
 		return fail (-12, "out of device memory (cabinet outputs)");
 	}
 	if (in)
-		HIPCHK (hipMemcpy2DAsync (e->extBuf.p, per * 4, in, inStride * 4, per * 4, n, hipMemcpyHostToDevice, e->stream));
+		if (int rc = stageHostInput (e->extBuf.p, in, inStride, per, n, e->stream))
+			return rc;
 	float*          x = e->cab.hostOut.p;
 	tbf_cabinet_out dc = {e->outL.p, e->outR.p, nullptr, nullptr, per};
 	if (cab->wetL) {
@@ -415,7 +369,7 @@ int tbf_render_cabinet_device (tbf_engine* e, uint32_t nblocks, const tbf_event*
 	if (int rc = cabinetArgs (e, nblocks, ev, nev, false, nullptr, 0, cab, rotors))
 		return rc;
 	HIPCHK (hipSetDevice (e->cfg.device));
-	return cabinetDevice (e, nblocks, ev, nev, nullptr, 0, *cab, rotors, stream ? (hipStream_t)stream : e->stream);
+	return cabinetDevice (e, nblocks, ev, nev, nullptr, 0, *cab, rotors, streamOr (stream, e->stream));
 }
 
 int tbf_process_cabinet (tbf_engine* e, uint32_t nblocks, const float* in, uint64_t inStride, const tbf_cabinet_out* cab,
@@ -432,33 +386,14 @@ int tbf_process_cabinet_device (tbf_engine* e, uint32_t nblocks, const tbf_event
 	if (int rc = cabinetArgs (e, nblocks, ev, nev, true, dIn, inStride, cab, rotors))
 		return rc;
 	HIPCHK (hipSetDevice (e->cfg.device));
-	return cabinetDevice (e, nblocks, ev, nev, dIn, inStride, *cab, rotors, stream ? (hipStream_t)stream : e->stream);
+	return cabinetDevice (e, nblocks, ev, nev, dIn, inStride, *cab, rotors, streamOr (stream, e->stream));
 }
 
 int tbf_debug_cabinet_time (tbf_engine* e, int32_t enable, double* ms, uint64_t* launches)
 {
 	if (!e)
 		return fail (-22, "null argument");
-	tbf_engine::Cabinet& c = e->cab;
-	if (enable) {
-		c.timeOn = enable > 0;
-		return 0;
-	}
-	double sum = 0.0;
-	for (auto& p : c.tev) {
-		float t = 0.f;
-		HIPCHK (hipEventSynchronize (p.second));
-		HIPCHK (hipEventElapsedTime (&t, p.first, p.second));
-		sum += t;
-		(void)hipEventDestroy (p.first);
-		(void)hipEventDestroy (p.second);
-	}
-	if (ms)
-		*ms = sum;
-	if (launches)
-		*launches = c.tev.size ();
-	c.tev.clear ();
-	return 0;
+	return e->cab.timer.query (enable, ms, launches);
 }
 
 int tbf_debug_cabinet (const tbf_engine* e, uint32_t inst, uint32_t* taps, uint32_t* parts, uint64_t* inst_bytes,

@@ -33,11 +33,8 @@
 
 extern "C" int tbf_launch_stage (const tbf_launch* P, int k, hipStream_t stream);
 extern "C" int tbf_chain_stages (uint32_t chain);
-extern "C" int tbf_chain_first_stage (uint32_t chain);
 extern "C" uint32_t tbf_chain_kernels (uint32_t chain);
 
-/* an effects-only chain (TBF_CHAIN_FX*): the caller's audio in place of the tone generator's */
-static bool chainFx (uint32_t chain) { return tbf_chain_first_stage (chain) > 0; }
 /* whether the chain runs the reverb stages (and so holds their stage buffers) */
 static bool chainReverb (uint32_t chain) { return tbf_chain_stages (chain) > 2; }
 /* the chain ends in the whirl (TBF_CHAIN_FULL, TBF_CHAIN_FX) */
@@ -57,14 +54,6 @@ int tbf::fail (int code, const std::string& msg)
 	g_err = msg;
 	return code;
 }
-
-#define HIPCHK(x)                                                                        \
-	do {                                                                                 \
-		hipError_t _e = (x);                                                             \
-		if (_e != hipSuccess)                                                            \
-			return fail (-5, std::string (#x ": ") + hipGetErrorString (_e));           \
-	} while (0)
-
 
 /* (program slots, chunk sizes and the control pool region -- SLOT, PSLOTS, PERSIST, TBF_CHUNK,
  * DPROG_CAP, CTL_REGION: tbf_engine_impl.h) */

@@ -31,6 +31,7 @@
 #include "tbf_mix.h"
 #include "tbf_pcm.h"
 #include "tbf_resample.h"
+#include "tbf_stage.h"
 #include "tbf_tpeak.h"
 #include "tbf_types.h"
 
@@ -51,7 +52,6 @@ struct Programme {
 	int      transpose[7] = {0};
 };
 
-int  fail (int code, const std::string& msg);
 int  controlById (struct Instance& in, int id, int value); /* tbf_control.cpp */
 void setCharacter (struct Instance& in, float v);
 
@@ -299,15 +299,7 @@ struct tbf_limiter {
 	DevBuf<tbf_limit_row>      drows; /* the call's rows on the device */
 	std::vector<tbf_limit_row> rows;  /* .side persists, .count is the call's */
 	uint64_t                   launches = 0;
-	bool                       timeOn = false; /* tbf_debug_limit_time: an event pair around every launch set */
-	std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
-	~tbf_limiter ()
-	{
-		for (auto& p : tev) {
-			(void)hipEventDestroy (p.first);
-			(void)hipEventDestroy (p.second);
-		}
-	}
+	StageTimer                 timer; /* tbf_debug_limit_time: an event pair around every launch set */
 };
 
 /* A loudness meter (tbf_loudness_create, csrc/tbf_loud.cpp): per row and channel the two biquads'
@@ -324,15 +316,7 @@ struct tbf_loudness {
 	std::vector<uint32_t> counts;  /* the call's counts */
 	std::vector<uint64_t> pos;     /* frames a row has taken */
 	hipStream_t           last = nullptr; /* the stream of the meter's last call or reset */
-	bool                  timeOn = false; /* tbf_debug_loudness_time: an event pair around every launch */
-	std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
-	~tbf_loudness ()
-	{
-		for (auto& p : tev) {
-			(void)hipEventDestroy (p.first);
-			(void)hipEventDestroy (p.second);
-		}
-	}
+	StageTimer            timer;   /* tbf_debug_loudness_time: an event pair around every launch */
 };
 
 /* A true-peak meter (tbf_true_peak_create, csrc/tbf_tpeak.cpp): per row two sides of 2 x 11 floats
@@ -349,15 +333,7 @@ struct tbf_true_peak {
 	std::vector<tbf_tpeak_row> rows;  /* .side persists, .count is the call's */
 	std::vector<uint64_t>      pos;   /* frames a row has taken */
 	hipStream_t                last = nullptr; /* the stream of the meter's last call or reset */
-	bool                       timeOn = false; /* tbf_debug_true_peak_time: an event pair around every launch */
-	std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
-	~tbf_true_peak ()
-	{
-		for (auto& p : tev) {
-			(void)hipEventDestroy (p.first);
-			(void)hipEventDestroy (p.second);
-		}
-	}
+	StageTimer                 timer; /* tbf_debug_true_peak_time: an event pair around every launch */
 };
 
 struct tbf_engine {
@@ -530,8 +506,7 @@ struct tbf_engine {
 		DevBuf<float>      hostOut;          /* the host-buffer calls' staging: wet pair and rotor planes */
 		std::vector<float> wetDev;           /* wet0 as uploaded */
 		uint64_t           launches = 0;     /* k_cabinet launches (tbf_debug_cabinet) */
-		bool               timeOn = false;   /* tbf_debug_cabinet_time: an event pair around every launch */
-		std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
+		StageTimer         timer;            /* tbf_debug_cabinet_time: an event pair around every launch */
 		uint64_t           instFloats () const { return K ? 2 * TBF_CAB_CH_FLOATS (K) : 0; }
 	} cab;
 	/* the output rate converter (tbf_resampler_set, csrc/tbf_resample.cpp): the engine-wide
@@ -548,8 +523,7 @@ struct tbf_engine {
 		DevBuf<float>      tab, st, hostOut;            /* hostOut: the host-buffer calls' staging of the converted pair */
 		DevBuf<uint64_t>   pos;                         /* positions per instance, when they differ */
 		uint64_t           launches = 0;
-		bool               timeOn = false;              /* tbf_debug_resample_time: an event pair around every launch */
-		std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
+		StageTimer         timer;                       /* tbf_debug_resample_time: an event pair around every launch */
 		uint32_t           histFloats () const { return L ? TBF_RS_HIST (T) : 0; }
 		uint64_t           instFloats () const { return 2 * (uint64_t)histFloats (); }
 	} rs;
@@ -560,8 +534,7 @@ struct tbf_engine {
 		DevBuf<unsigned char> hostOut;
 		DevBuf<tbf_pcm_meter> hostMeters;
 		uint64_t              launches = 0;
-		bool                  timeOn = false; /* tbf_debug_pcm_time: an event pair around every launch */
-		std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
+		StageTimer            timer;        /* tbf_debug_pcm_time: an event pair around every launch */
 	} pcm;
 	/* the mixdown stage (csrc/tbf_mix.cpp): no instance state, only the calls' staging -- the
 	 * bus-sorted member list and the host-buffer calls' bus planes */
@@ -570,8 +543,7 @@ struct tbf_engine {
 		DevBuf<tbf_mix_member> members;
 		DevBuf<float>          hostOut;
 		uint64_t               launches = 0;
-		bool                   timeOn = false; /* tbf_debug_mix_time: an event pair around every launch */
-		std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
+		StageTimer             timer;        /* tbf_debug_mix_time: an event pair around every launch */
 	} mix;
 	bool                                    rvLdsOn  = true;  /* k_rv_core_lds when the rings fit (TBF_RV_LDS=0: k_rv_core) */
 	bool                                    rvLdsFit = false; /* the instances' rings fit k_rv_core_lds */

@@ -37,13 +37,6 @@ extern "C" int tbf_launch_state_move (tbf_move_table* T, const uint32_t* dPairSr
 
 using namespace tbf;
 
-#define HIPCHK(x)                                                                        \
-	do {                                                                                 \
-		hipError_t _e = (x);                                                             \
-		if (_e != hipSuccess)                                                            \
-			return fail (-5, std::string (#x ": ") + hipGetErrorString (_e));           \
-	} while (0)
-
 static_assert (sizeof (tbf_inst_state) % 8 == 0, "k_state_move's narrow path moves 8-B elements");
 static_assert (sizeof (tbf_tgc_state) % 16 == 0 && sizeof (tbf_prog_entry) % 16 == 0, "16-B segments");
 

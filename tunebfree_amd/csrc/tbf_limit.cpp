@@ -27,27 +27,7 @@ extern "C" int tbf_launch_limit (const tbf_limit_launch* P, hipStream_t stream);
 
 using namespace tbf;
 
-#define HIPCHK(x)                                                                        \
-	do {                                                                                 \
-		hipError_t _e = (x);                                                             \
-		if (_e != hipSuccess)                                                            \
-			return fail (-5, std::string (#x ": ") + hipGetErrorString (_e));           \
-	} while (0)
-
 namespace {
-
-/* [a, b) in bytes; empty ranges overlap nothing */
-struct Span {
-	uintptr_t a, b;
-};
-
-Span rowsSpan (const void* p, uint64_t rows, uint64_t strideBytes, uint64_t rowBytes)
-{
-	const uintptr_t a = (uintptr_t)p;
-	return {a, p && rows && rowBytes ? a + (uintptr_t)((rows - 1) * strideBytes + rowBytes) : a};
-}
-
-bool overlap (Span x, Span y) { return x.a < x.b && y.a < y.b && x.a < y.b && y.a < x.b; }
 
 int checkConfig (const tbf_limiter_config* cfg)
 {
@@ -61,13 +41,6 @@ int checkConfig (const tbf_limiter_config* cfg)
 	if (cfg->hold > TBF_LIMIT_MAX_HOLD)
 		return fail (-22, "limit: hold " + std::to_string (cfg->hold) + " above " + std::to_string (TBF_LIMIT_MAX_HOLD));
 	return 0;
-}
-
-/* the limiter's slot in its engine's list, or the list's end */
-std::vector<std::unique_ptr<tbf_limiter>>::iterator slotOf (tbf_limiter* lim)
-{
-	auto& v = lim->eng->limiters;
-	return std::find_if (v.begin (), v.end (), [lim] (const std::unique_ptr<tbf_limiter>& p) { return p.get () == lim; });
 }
 
 } // namespace
@@ -109,7 +82,7 @@ int tbf_limiter_destroy (tbf_limiter* lim)
 {
 	if (!lim)
 		return 0;
-	auto it = slotOf (lim);
+	auto it = slotOf (lim->eng->limiters, lim);
 	if (it == lim->eng->limiters.end ())
 		return fail (-22, "limit: not a limiter of its engine");
 	(void)hipSetDevice (lim->eng->cfg.device);
@@ -121,12 +94,10 @@ int tbf_limiter_reset (tbf_limiter* lim, uint32_t n, const uint32_t* rows, void*
 {
 	if (!lim)
 		return fail (-22, "limit: lim is NULL");
-	for (uint32_t k = 0; rows && k < n; k++)
-		if (rows[k] >= lim->nRows)
-			return fail (-22, "limit: rows[" + std::to_string (k) + "] " + std::to_string (rows[k]) + " is no row of n_rows " +
-			                      std::to_string (lim->nRows));
+	if (int rc = checkRows ("limit", n, rows, lim->nRows))
+		return rc;
 	HIPCHK (hipSetDevice (lim->eng->cfg.device));
-	hipStream_t const s = stream ? (hipStream_t)stream : lim->eng->stream;
+	hipStream_t const s = streamOr (stream, lim->eng->stream);
 	const size_t      per = (size_t)4u * lim->Hn; /* a row's floats: both sides, both channels */
 	if (!rows)
 		HIPCHK (hipMemsetAsync (lim->hist.p, 0, (size_t)lim->nRows * per * sizeof (float), s));
@@ -163,24 +134,20 @@ int tbf_limit_device (tbf_limiter* lim, const float* d_L, const float* d_R, uint
 	if (((uintptr_t)d_L | (uintptr_t)d_R | (uintptr_t)out->L | (uintptr_t)out->R | (uintptr_t)out->meters) & 3u)
 		return fail (-22, "limit: device pointer not 4-byte aligned");
 	const uint32_t n = lim->nRows;
-	uint32_t       most = counts ? 0u : frames;
-	for (uint32_t r = 0; counts && r < n; r++) {
-		if (counts[r] > frames)
-			return fail (-22, "limit: counts[" + std::to_string (r) + "] above frames");
-		most = std::max (most, counts[r]);
-	}
+	uint32_t       most;
+	if (int rc = countsMost ("limit", counts, n, frames, &most))
+		return rc;
 	{
-		const Span il = rowsSpan (d_L, n, in_stride * 4, (uint64_t)frames * 4), ir = rowsSpan (d_R, n, in_stride * 4, (uint64_t)frames * 4);
-		const Span ol = rowsSpan (out->L, n, out->stride * 4, (uint64_t)frames * 4);
-		const Span orr = rowsSpan (out->R, n, out->stride * 4, (uint64_t)frames * 4);
-		const Span mt = rowsSpan (out->meters, n, sizeof (tbf_limit_meter), sizeof (tbf_limit_meter));
-		if (overlap (il, ol) || overlap (il, orr) || overlap (ir, ol) || overlap (ir, orr) || overlap (ol, orr) || overlap (mt, il) ||
-		    overlap (mt, ir) || overlap (mt, ol) || overlap (mt, orr))
+		const uint64_t rowBytes = (uint64_t)frames * 4;
+		const Span     sp[5]    = {rowsSpan (d_L, n, in_stride * 4, rowBytes), rowsSpan (d_R, n, in_stride * 4, rowBytes),
+		                           rowsSpan (out->L, n, out->stride * 4, rowBytes), rowsSpan (out->R, n, out->stride * 4, rowBytes),
+		                           rowsSpan (out->meters, n, sizeof (tbf_limit_meter), sizeof (tbf_limit_meter))};
+		if (anyOverlap (sp, 5, 2)) /* d_L and d_R may be one plane: mono */
 			return fail (-22, "limit: input rows, output planes and meters overlap (in-place use is refused)");
 	}
 	tbf_engine* const e = lim->eng;
 	HIPCHK (hipSetDevice (e->cfg.device));
-	hipStream_t const s = stream ? (hipStream_t)stream : e->stream;
+	hipStream_t const s = streamOr (stream, e->stream);
 	if (most == 0 && !out->meters)
 		return 0;
 	/* The rows' counts and sides on the device.  They are read from the limiter's host vector,
@@ -206,37 +173,20 @@ int tbf_limit_device (tbf_limiter* lim, const float* d_L, const float* d_R, uint
 	P.hold      = lim->cfg.hold;
 	P.maxCount  = most;
 
-	hipEvent_t t0 = nullptr, t1 = nullptr;
-	auto       drop = [&] () { /* a failed step between the events' creation and their hand-over to tev */
-		if (t0)
-			(void)hipEventDestroy (t0);
-		if (t1)
-			(void)hipEventDestroy (t1);
-	};
-	if (lim->timeOn) { /* tbf_debug_limit_time: the launch set between two events on its stream */
-		if (hipEventCreate (&t0) != hipSuccess || hipEventCreate (&t1) != hipSuccess || hipEventRecord (t0, s) != hipSuccess) {
-			drop ();
-			return fail (-5, std::string ("limit timing events: ") + hipGetErrorString (hipGetLastError ()));
-		}
-	}
+	StageTimer::Guard tg (lim->timer, s, "limit"); /* tbf_debug_limit_time: the launch set between two events on its stream */
+	if (int rc = tg.begin ())
+		return rc;
 	for (uint32_t r0 = 0; r0 < n; r0 += TBF_LIMIT_MAX_ROWS) {
 		P.rowBase = r0;
 		P.nRows   = std::min (TBF_LIMIT_MAX_ROWS, n - r0);
-		if (tbf_launch_limit (&P, s)) {
-			drop ();
+		if (tbf_launch_limit (&P, s))
 			return fail (-5, std::string ("k_limit launch failed: ") + hipGetErrorString (hipGetLastError ()));
-		}
 	}
 	for (uint32_t r = 0; r < n; r++) /* the rows that took frames now live on their other side */
 		if (lim->rows[r].count)
 			lim->rows[r].side ^= 1u;
-	if (lim->timeOn) {
-		if (hipEventRecord (t1, s) != hipSuccess) {
-			drop ();
-			return fail (-5, std::string ("limit timing events: ") + hipGetErrorString (hipGetLastError ()));
-		}
-		lim->tev.push_back ({t0, t1});
-	}
+	if (int rc = tg.end ())
+		return rc;
 	lim->launches++;
 	return 0;
 }
@@ -315,25 +265,7 @@ int tbf_debug_limit_time (tbf_limiter* lim, int32_t enable, double* ms, uint64_t
 {
 	if (!lim)
 		return fail (-22, "limit: lim is NULL");
-	if (enable) {
-		lim->timeOn = enable > 0;
-		return 0;
-	}
-	double sum = 0.0;
-	for (auto& p : lim->tev) {
-		float t = 0.f;
-		HIPCHK (hipEventSynchronize (p.second));
-		HIPCHK (hipEventElapsedTime (&t, p.first, p.second));
-		sum += t;
-		(void)hipEventDestroy (p.first);
-		(void)hipEventDestroy (p.second);
-	}
-	if (ms)
-		*ms = sum;
-	if (launches)
-		*launches = lim->tev.size ();
-	lim->tev.clear ();
-	return 0;
+	return lim->timer.query (enable, ms, launches);
 }
 
 } /* extern "C" */

@@ -28,13 +28,6 @@ extern "C" int tbf_launch_loud (const tbf_loud_launch* P, hipStream_t stream);
 
 using namespace tbf;
 
-#define HIPCHK(x)                                                                        \
-	do {                                                                                 \
-		hipError_t _e = (x);                                                             \
-		if (_e != hipSuccess)                                                            \
-			return fail (-5, std::string (#x ": ") + hipGetErrorString (_e));           \
-	} while (0)
-
 namespace {
 
 int checkRate (uint32_t rate)
@@ -173,13 +166,6 @@ void loud_range (uint32_t rate, const double* e, uint32_t n, double* lra, uint32
 		*windows = (uint32_t)s.size ();
 }
 
-/* the meter's slot in its engine's list, or the list's end */
-std::vector<std::unique_ptr<tbf_loudness>>::iterator slotOf (tbf_loudness* lm)
-{
-	auto& v = lm->eng->loudness;
-	return std::find_if (v.begin (), v.end (), [lm] (const std::unique_ptr<tbf_loudness>& p) { return p.get () == lm; });
-}
-
 /* the meter's last call has passed its stream */
 int settle (tbf_loudness* lm)
 {
@@ -238,7 +224,7 @@ int tbf_loudness_destroy (tbf_loudness* lm)
 {
 	if (!lm)
 		return 0;
-	auto it = slotOf (lm);
+	auto it = slotOf (lm->eng->loudness, lm);
 	if (it == lm->eng->loudness.end ())
 		return fail (-22, "loudness: not a meter of its engine");
 	(void)hipSetDevice (lm->eng->cfg.device);
@@ -250,12 +236,10 @@ int tbf_loudness_reset (tbf_loudness* lm, uint32_t n, const uint32_t* rows, void
 {
 	if (!lm)
 		return fail (-22, "loudness: lm is NULL");
-	for (uint32_t k = 0; rows && k < n; k++)
-		if (rows[k] >= lm->nRows)
-			return fail (-22, "loudness: rows[" + std::to_string (k) + "] " + std::to_string (rows[k]) + " is no row of n_rows " +
-			                      std::to_string (lm->nRows));
+	if (int rc = checkRows ("loudness", n, rows, lm->nRows))
+		return rc;
 	HIPCHK (hipSetDevice (lm->eng->cfg.device));
-	hipStream_t const s   = stream ? (hipStream_t)stream : lm->eng->stream;
+	hipStream_t const s   = streamOr (stream, lm->eng->stream);
 	const size_t      per = 2u * sizeof (tbf_loud_chan); /* a row's state: both channels */
 	if (!rows) {
 		HIPCHK (hipMemsetAsync (lm->state.p, 0, (size_t)lm->nRows * per, s));
@@ -281,12 +265,9 @@ int tbf_loudness_device (tbf_loudness* lm, const float* d_L, const float* d_R, u
 	if (((uintptr_t)d_L | (uintptr_t)d_R) & 3u)
 		return fail (-22, "loudness: device pointer not 4-byte aligned");
 	const uint32_t n    = lm->nRows;
-	uint32_t       most = counts ? 0u : frames;
-	for (uint32_t r = 0; counts && r < n; r++) {
-		if (counts[r] > frames)
-			return fail (-22, "loudness: counts[" + std::to_string (r) + "] above frames");
-		most = std::max (most, counts[r]);
-	}
+	uint32_t       most;
+	if (int rc = countsMost ("loudness", counts, n, frames, &most))
+		return rc;
 	for (uint32_t r = 0; r < n; r++) {
 		const uint64_t c = counts ? counts[r] : frames;
 		if ((lm->pos[r] + c) / lm->Hp > lm->cfg.max_hops)
@@ -295,7 +276,7 @@ int tbf_loudness_device (tbf_loudness* lm, const float* d_L, const float* d_R, u
 	}
 	tbf_engine* const e = lm->eng;
 	HIPCHK (hipSetDevice (e->cfg.device));
-	hipStream_t const s = stream ? (hipStream_t)stream : e->stream;
+	hipStream_t const s = streamOr (stream, e->stream);
 	if (most == 0)
 		return 0;
 	/* The counts on the device.  They are read from the meter's host vector, which the next call
@@ -318,34 +299,15 @@ int tbf_loudness_device (tbf_loudness* lm, const float* d_L, const float* d_R, u
 	P.maxHops = lm->cfg.max_hops;
 	P.nRows   = n;
 
-	hipEvent_t t0 = nullptr, t1 = nullptr;
-	auto       drop = [&] () { /* a failed step between the events' creation and their hand-over to tev */
-		if (t0)
-			(void)hipEventDestroy (t0);
-		if (t1)
-			(void)hipEventDestroy (t1);
-	};
-	if (lm->timeOn) { /* tbf_debug_loudness_time: the launch between two events on its stream */
-		if (hipEventCreate (&t0) != hipSuccess || hipEventCreate (&t1) != hipSuccess || hipEventRecord (t0, s) != hipSuccess) {
-			drop ();
-			return fail (-5, std::string ("loudness timing events: ") + hipGetErrorString (hipGetLastError ()));
-		}
-	}
-	if (tbf_launch_loud (&P, s)) {
-		drop ();
+	StageTimer::Guard tg (lm->timer, s, "loudness"); /* tbf_debug_loudness_time: the launch between two events on its stream */
+	if (int rc = tg.begin ())
+		return rc;
+	if (tbf_launch_loud (&P, s))
 		return fail (-5, std::string ("k_loud launch failed: ") + hipGetErrorString (hipGetLastError ()));
-	}
 	for (uint32_t r = 0; r < n; r++)
 		lm->pos[r] += lm->counts[r];
 	lm->last = s;
-	if (lm->timeOn) {
-		if (hipEventRecord (t1, s) != hipSuccess) {
-			drop ();
-			return fail (-5, std::string ("loudness timing events: ") + hipGetErrorString (hipGetLastError ()));
-		}
-		lm->tev.push_back ({t0, t1});
-	}
-	return 0;
+	return tg.end ();
 }
 
 int tbf_loudness_read (tbf_loudness* lm, uint32_t n, const uint32_t* rows, tbf_loudness_result* out)
@@ -356,10 +318,8 @@ int tbf_loudness_read (tbf_loudness* lm, uint32_t n, const uint32_t* rows, tbf_l
 		return fail (-22, "loudness: out is NULL");
 	if (!rows)
 		n = lm->nRows;
-	for (uint32_t k = 0; rows && k < n; k++)
-		if (rows[k] >= lm->nRows)
-			return fail (-22, "loudness: rows[" + std::to_string (k) + "] " + std::to_string (rows[k]) + " is no row of n_rows " +
-			                      std::to_string (lm->nRows));
+	if (int rc = checkRows ("loudness", n, rows, lm->nRows))
+		return rc;
 	if (int rc = settle (lm))
 		return rc;
 	std::vector<double> e;
@@ -468,10 +428,8 @@ int tbf_loudness_range (tbf_loudness* lm, uint32_t n, const uint32_t* rows, doub
 		return fail (-22, "loudness: lra is NULL");
 	if (!rows)
 		n = lm->nRows;
-	for (uint32_t k = 0; rows && k < n; k++)
-		if (rows[k] >= lm->nRows)
-			return fail (-22, "loudness: rows[" + std::to_string (k) + "] " + std::to_string (rows[k]) + " is no row of n_rows " +
-			                      std::to_string (lm->nRows));
+	if (int rc = checkRows ("loudness", n, rows, lm->nRows))
+		return rc;
 	if (int rc = settle (lm))
 		return rc;
 	std::vector<double> e;
@@ -514,25 +472,7 @@ int tbf_debug_loudness_time (tbf_loudness* lm, int32_t enable, double* ms, uint6
 {
 	if (!lm)
 		return fail (-22, "loudness: lm is NULL");
-	if (enable) {
-		lm->timeOn = enable > 0;
-		return 0;
-	}
-	double sum = 0.0;
-	for (auto& p : lm->tev) {
-		float t = 0.f;
-		HIPCHK (hipEventSynchronize (p.second));
-		HIPCHK (hipEventElapsedTime (&t, p.first, p.second));
-		sum += t;
-		(void)hipEventDestroy (p.first);
-		(void)hipEventDestroy (p.second);
-	}
-	if (ms)
-		*ms = sum;
-	if (launches)
-		*launches = lm->tev.size ();
-	lm->tev.clear ();
-	return 0;
+	return lm->timer.query (enable, ms, launches);
 }
 
 } /* extern "C" */

@@ -9,7 +9,7 @@
  * walks on the host and the device calls upload.  tbf_mix_device runs the stage alone on the
  * caller's planes.  The render and process calls render the engine-rate pair through the
  * ordinary render path (plainRender, csrc/tbf_engine.cpp) into engine scratch
- * (tbf_engine.rotBuf), 8 B per instance and sample, cut into pieces of at most TBF_MIX_PIECE
+ * (tbf_engine.rotBuf), 8 B per instance and sample, cut into pieces of at most TBF_STAGE_PIECE
  * blocks, and k_mix follows each piece on the call's stream, writing at the piece's frame offset.
  * A bus sample depends on its own frame alone, so the pieces deliver what one call delivers.
  * The host-buffer calls mix into device staging and copy the bus rows out once per piece.
@@ -27,36 +27,10 @@
 #include "tbf_mix.h"
 
 extern "C" int tbf_launch_mix (const tbf_mix_launch* P, hipStream_t stream);
-extern "C" int tbf_chain_first_stage (uint32_t chain);
 
 using namespace tbf;
 
-#define HIPCHK(x)                                                                        \
-	do {                                                                                 \
-		hipError_t _e = (x);                                                             \
-		if (_e != hipSuccess)                                                            \
-			return fail (-5, std::string (#x ": ") + hipGetErrorString (_e));           \
-	} while (0)
-
-/* blocks per piece of a render or process call */
-#define TBF_MIX_PIECE 256u
-
 namespace {
-
-bool chainFx (uint32_t chain) { return tbf_chain_first_stage (chain) > 0; }
-
-/* [a, b) in bytes; empty ranges overlap nothing */
-struct Span {
-	uintptr_t a, b;
-};
-
-Span rowsSpan (const void* p, uint64_t rows, uint64_t stride, uint64_t frames)
-{
-	const uintptr_t a = (uintptr_t)p;
-	return {a, rows && frames ? a + (uintptr_t)(((rows - 1) * stride + frames) * 4) : a};
-}
-
-bool overlap (Span x, Span y) { return x.a < x.b && y.a < y.b && x.a < y.b && y.a < x.b; }
 
 /* the bus-sorted member list of a call's rows */
 struct List {
@@ -112,13 +86,12 @@ int outArgs (const tbf_mix_out* o, uint64_t frames, bool device)
 int rangesApart (const tbf_mix_out* o, uint64_t nBuses, uint64_t frames, const float* const* in, int nin, uint64_t inRows,
                  uint64_t inStride, uint64_t inFrames)
 {
-	const Span l = rowsSpan (o->L, nBuses, o->stride, frames), r = rowsSpan (o->R, nBuses, o->stride, frames);
-	bool       bad = overlap (l, r);
-	for (int k = 0; k < nin; k++) {
-		const Span i = rowsSpan (in[k], inRows, inStride, inFrames);
-		bad          = bad || overlap (i, l) || overlap (i, r);
-	}
-	return bad ? fail (-22, "mix: input rows and output planes overlap") : 0;
+	Span sp[4]; /* the inputs (nin <= 2), which may alias each other, then the two bus planes */
+	for (int k = 0; k < nin; k++)
+		sp[k] = rowsSpan (in[k], inRows, inStride * 4, inFrames * 4);
+	sp[nin]     = rowsSpan (o->L, nBuses, o->stride * 4, frames * 4);
+	sp[nin + 1] = rowsSpan (o->R, nBuses, o->stride * 4, frames * 4);
+	return anyOverlap (sp, nin + 2, nin) ? fail (-22, "mix: input rows and output planes overlap") : 0;
 }
 
 /* The checks of the render and process calls and the list, all before anything renders or steps
@@ -178,35 +151,18 @@ int launchStage (tbf_engine* e, tbf_mix_launch P, uint32_t nBuses, hipStream_t s
 	tbf_engine::Mix& c = e->mix;
 	if (nBuses == 0 || P.frames == 0)
 		return 0;
-	hipEvent_t t0 = nullptr, t1 = nullptr;
-	auto       drop = [&] () { /* a failed step between the events' creation and their hand-over to tev */
-		if (t0)
-			(void)hipEventDestroy (t0);
-		if (t1)
-			(void)hipEventDestroy (t1);
-	};
-	if (c.timeOn) { /* tbf_debug_mix_time: k_mix between two events on its stream */
-		if (hipEventCreate (&t0) != hipSuccess || hipEventCreate (&t1) != hipSuccess || hipEventRecord (t0, s) != hipSuccess) {
-			drop ();
-			return fail (-5, std::string ("mix timing events: ") + hipGetErrorString (hipGetLastError ()));
-		}
-	}
+	StageTimer::Guard tg (c.timer, s, "mix"); /* tbf_debug_mix_time: k_mix between two events on its stream */
+	if (int rc = tg.begin ())
+		return rc;
 	P.group = mix_frames_per_lane (P.frames, nBuses);
 	for (uint32_t b0 = 0; b0 < nBuses; b0 += TBF_MIX_MAX_BUSES) {
 		P.busBase = b0;
 		P.nBuses  = std::min (TBF_MIX_MAX_BUSES, nBuses - b0);
-		if (tbf_launch_mix (&P, s)) {
-			drop ();
+		if (tbf_launch_mix (&P, s))
 			return fail (-5, std::string ("k_mix launch failed: ") + hipGetErrorString (hipGetLastError ()));
-		}
 	}
-	if (c.timeOn) {
-		if (hipEventRecord (t1, s) != hipSuccess) {
-			drop ();
-			return fail (-5, std::string ("mix timing events: ") + hipGetErrorString (hipGetLastError ()));
-		}
-		c.tev.push_back ({t0, t1});
-	}
+	if (int rc = tg.end ())
+		return rc;
 	c.launches++;
 	return 0;
 }
@@ -223,7 +179,7 @@ int renderMix (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t ne
 		return rc;
 	if (nblocks == 0 || (n == 0 && nBuses == 0)) /* nothing renders and no event applies, as in every render call */
 		return 0;
-	const uint32_t piece = std::min (nblocks, TBF_MIX_PIECE);
+	const uint32_t piece = std::min (nblocks, TBF_STAGE_PIECE);
 	const size_t   per = (size_t)nblocks * TBF_BLK, pframes = (size_t)piece * TBF_BLK, plane = (size_t)n * pframes;
 	const size_t   oplane = (size_t)nBuses * pframes;
 	if (e->rotBuf.ensure (2 * plane) || (host && (c.hostOut.ensure (2 * oplane) || (in && e->extBuf.ensure ((size_t)n * per))))) {
@@ -236,7 +192,8 @@ int renderMix (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t ne
 		return rc;
 	const float* dIn = in;
 	if (host && in && n) {
-		HIPCHK (hipMemcpy2DAsync (e->extBuf.p, per * 4, in, inStride * 4, per * 4, n, hipMemcpyHostToDevice, s));
+		if (int rc = stageHostInput (e->extBuf.p, in, inStride, per, n, s))
+			return rc;
 		dIn      = e->extBuf.p;
 		inStride = per;
 	}
@@ -244,28 +201,12 @@ int renderMix (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t ne
 	P.in[0]    = pl;
 	P.in[1]    = pr;
 	P.inStride = pframes;
-	std::vector<tbf_event> pev;
-	uint32_t               evi = 0;
-	for (uint32_t p0 = 0; p0 < nblocks; p0 += piece) {
-		const uint32_t len  = std::min (piece, nblocks - p0);
-		const bool     last = p0 + len == nblocks;
-		/* the piece's events, their blocks counted from the piece; the last piece takes those
-		 * at or beyond the call's end too, which apply after it */
-		uint32_t evEnd = evi;
-		while (evEnd < nev && (last || ev[evEnd].block < p0 + len))
-			evEnd++;
-		const tbf_event* pe = ev + evi;
-		if (p0 && evEnd > evi) {
-			pev.assign (ev + evi, ev + evEnd);
-			for (tbf_event& v : pev)
-				v.block -= p0;
-			pe = pev.data ();
-		}
+	for (Pieces pc (ev, nev, nblocks, piece); pc.next ();) {
+		const uint32_t p0 = pc.p0, len = pc.len;
 		if (n)
-			if (int rc = plainRender (e, len, evEnd > evi ? pe : nullptr, evEnd - evi, dIn ? dIn + (size_t)p0 * TBF_BLK : nullptr,
-			                          inStride, pl, pr, pframes, s))
+			if (int rc = plainRender (e, len, pc.npe ? pc.pe : nullptr, pc.npe, dIn ? dIn + (size_t)p0 * TBF_BLK : nullptr, inStride,
+			                          pl, pr, pframes, s))
 				return rc;
-		evi = evEnd;
 		const size_t off = (size_t)p0 * TBF_BLK, rowFrames = (size_t)len * TBF_BLK;
 		P.out[0]    = host ? c.hostOut.p : o.L + off;
 		P.out[1]    = host ? c.hostOut.p + oplane : o.R + off;
@@ -306,7 +247,7 @@ int tbf_mix_device (tbf_engine* e, uint32_t n_rows, const float* d_L, const floa
 	if (e->cfg.device < 0)
 		return fail (-19, "host-only engine (device -1) has no device to mix on");
 	HIPCHK (hipSetDevice (e->cfg.device));
-	hipStream_t const s = stream ? (hipStream_t)stream : e->stream;
+	hipStream_t const s = streamOr (stream, e->stream);
 	if (n_buses == 0 || frames == 0)
 		return 0;
 	tbf_mix_launch P;
@@ -337,7 +278,7 @@ int tbf_render_mix_device (tbf_engine* e, uint32_t nblocks, const tbf_event* ev,
 	List list;
 	if (int rc = renderArgs (e, nblocks, ev, nev, false, nullptr, 0, rows, n_buses, out, true, list))
 		return rc;
-	return renderMix (e, nblocks, ev, nev, nullptr, 0, list, n_buses, *out, stream ? (hipStream_t)stream : e->stream, false);
+	return renderMix (e, nblocks, ev, nev, nullptr, 0, list, n_buses, *out, streamOr (stream, e->stream), false);
 }
 
 int tbf_process_mix (tbf_engine* e, uint32_t nblocks, const float* in, uint64_t inStride, const tbf_mix_row* rows, uint32_t n_buses,
@@ -355,7 +296,7 @@ int tbf_process_mix_device (tbf_engine* e, uint32_t nblocks, const tbf_event* ev
 	List list;
 	if (int rc = renderArgs (e, nblocks, ev, nev, true, dIn, inStride, rows, n_buses, out, true, list))
 		return rc;
-	return renderMix (e, nblocks, ev, nev, dIn, inStride, list, n_buses, *out, stream ? (hipStream_t)stream : e->stream, false);
+	return renderMix (e, nblocks, ev, nev, dIn, inStride, list, n_buses, *out, streamOr (stream, e->stream), false);
 }
 
 int tbf_debug_mix_ref (uint32_t n_rows, const float* L, const float* R, uint64_t in_stride, uint32_t frames, const uint32_t* counts,
@@ -403,26 +344,7 @@ int tbf_debug_mix_time (tbf_engine* e, int32_t enable, double* ms, uint64_t* lau
 {
 	if (!e)
 		return fail (-22, "null argument");
-	tbf_engine::Mix& c = e->mix;
-	if (enable) {
-		c.timeOn = enable > 0;
-		return 0;
-	}
-	double sum = 0.0;
-	for (auto& p : c.tev) {
-		float t = 0.f;
-		HIPCHK (hipEventSynchronize (p.second));
-		HIPCHK (hipEventElapsedTime (&t, p.first, p.second));
-		sum += t;
-		(void)hipEventDestroy (p.first);
-		(void)hipEventDestroy (p.second);
-	}
-	if (ms)
-		*ms = sum;
-	if (launches)
-		*launches = c.tev.size ();
-	c.tev.clear ();
-	return 0;
+	return e->mix.timer.query (enable, ms, launches);
 }
 
 } /* extern "C" */

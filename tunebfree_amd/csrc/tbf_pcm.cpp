@@ -7,8 +7,8 @@
  * The stage has no instance state.  tbf_pcm_convert_device runs it alone on the caller's planes.
  * The render and process calls render the engine-rate pair through the ordinary render path
  * (plainRender, csrc/tbf_engine.cpp) into engine scratch (tbf_engine.rotBuf), 8 B per instance and
- * sample, cut into pieces of at most TBF_PCM_PIECE blocks so the scratch never exceeds
- * n x TBF_PCM_PIECE x 128 x 8 B, and k_pcm follows each piece on the call's stream.  Dither is a
+ * sample, cut into pieces of at most TBF_STAGE_PIECE blocks so the scratch never exceeds
+ * n x TBF_STAGE_PIECE x 128 x 8 B, and k_pcm follows each piece on the call's stream.  Dither is a
  * function of the frame index and the meters are integer maxima and sums, so the pieces deliver
  * what one call delivers.  The host-buffer calls convert into device staging and copy the packed
  * rows out once per piece.  Everything is allocated before the first piece renders: -12 renders
@@ -25,36 +25,10 @@
 #include "tbf_pcm.h"
 
 extern "C" int tbf_launch_pcm (const tbf_pcm_launch* P, hipStream_t stream);
-extern "C" int tbf_chain_first_stage (uint32_t chain);
 
 using namespace tbf;
 
-#define HIPCHK(x)                                                                        \
-	do {                                                                                 \
-		hipError_t _e = (x);                                                             \
-		if (_e != hipSuccess)                                                            \
-			return fail (-5, std::string (#x ": ") + hipGetErrorString (_e));           \
-	} while (0)
-
-/* blocks per piece of a render or process call */
-#define TBF_PCM_PIECE 256u
-
 namespace {
-
-bool chainFx (uint32_t chain) { return tbf_chain_first_stage (chain) > 0; }
-
-/* [a, b) in bytes; empty ranges overlap nothing */
-struct Span {
-	uintptr_t a, b;
-};
-
-Span rowsSpan (const void* p, uint64_t rows, uint64_t strideBytes, uint64_t rowBytes)
-{
-	const uintptr_t a = (uintptr_t)p;
-	return {a, rows && rowBytes ? a + (uintptr_t)((rows - 1) * strideBytes + rowBytes) : a};
-}
-
-bool overlap (Span x, Span y) { return x.a < x.b && y.a < y.b && x.a < y.b && y.a < x.b; }
 
 /* format, flags, stride and alignment of a tbf_pcm_out for rows of `frames` frames */
 int outArgs (const tbf_pcm_out* o, uint64_t frames, bool device)
@@ -79,14 +53,12 @@ int outArgs (const tbf_pcm_out* o, uint64_t frames, bool device)
 /* the frames and the meters against each other and against input rows */
 int rangesApart (const tbf_pcm_out* o, uint64_t rows, uint64_t frames, const float* const* in, int nin, uint64_t inStride)
 {
-	const Span out = rowsSpan (o->out, rows, o->out_stride_bytes, frames * pcm_frame_bytes (o->format));
-	const Span met = rowsSpan (o->meters, o->meters ? rows : 0, sizeof (tbf_pcm_meter), sizeof (tbf_pcm_meter));
-	bool       bad = overlap (out, met);
-	for (int k = 0; k < nin; k++) {
-		const Span i = rowsSpan (in[k], rows, inStride * 4, frames * 4);
-		bad          = bad || overlap (i, out) || overlap (i, met);
-	}
-	return bad ? fail (-22, "pcm: input, frame and meter ranges overlap") : 0;
+	Span sp[4]; /* the inputs (nin <= 2), which may alias each other, then the frames and the meters */
+	for (int k = 0; k < nin; k++)
+		sp[k] = rowsSpan (in[k], rows, inStride * 4, frames * 4);
+	sp[nin]     = rowsSpan (o->out, rows, o->out_stride_bytes, frames * pcm_frame_bytes (o->format));
+	sp[nin + 1] = rowsSpan (o->meters, rows, sizeof (tbf_pcm_meter), sizeof (tbf_pcm_meter));
+	return anyOverlap (sp, nin + 2, nin) ? fail (-22, "pcm: input, frame and meter ranges overlap") : 0;
 }
 
 /* The checks of the render and process calls, all before anything renders or steps (in: the
@@ -146,34 +118,17 @@ int launchStage (tbf_engine* e, tbf_pcm_launch P, uint32_t nRows, hipStream_t s)
 	tbf_engine::Pcm& c = e->pcm;
 	if (nRows == 0 || P.maxCount == 0)
 		return 0;
-	hipEvent_t t0 = nullptr, t1 = nullptr;
-	auto       drop = [&] () { /* a failed step between the events' creation and their hand-over to tev */
-		if (t0)
-			(void)hipEventDestroy (t0);
-		if (t1)
-			(void)hipEventDestroy (t1);
-	};
-	if (c.timeOn) { /* tbf_debug_pcm_time: k_pcm between two events on its stream */
-		if (hipEventCreate (&t0) != hipSuccess || hipEventCreate (&t1) != hipSuccess || hipEventRecord (t0, s) != hipSuccess) {
-			drop ();
-			return fail (-5, std::string ("pcm timing events: ") + hipGetErrorString (hipGetLastError ()));
-		}
-	}
+	StageTimer::Guard tg (c.timer, s, "pcm"); /* tbf_debug_pcm_time: k_pcm between two events on its stream */
+	if (int rc = tg.begin ())
+		return rc;
 	for (uint32_t r0 = 0; r0 < nRows; r0 += TBF_PCM_MAX_ROWS) {
 		P.rowBase = r0;
 		P.nRows   = std::min (TBF_PCM_MAX_ROWS, nRows - r0);
-		if (tbf_launch_pcm (&P, s)) {
-			drop ();
+		if (tbf_launch_pcm (&P, s))
 			return fail (-5, std::string ("k_pcm launch failed: ") + hipGetErrorString (hipGetLastError ()));
-		}
 	}
-	if (c.timeOn) {
-		if (hipEventRecord (t1, s) != hipSuccess) {
-			drop ();
-			return fail (-5, std::string ("pcm timing events: ") + hipGetErrorString (hipGetLastError ()));
-		}
-		c.tev.push_back ({t0, t1});
-	}
+	if (int rc = tg.end ())
+		return rc;
 	c.launches++;
 	return 0;
 }
@@ -201,7 +156,7 @@ int renderPcm (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t ne
 		return rc;
 	if (n == 0 || nblocks == 0) /* nothing renders and no event applies, as in every render call */
 		return 0;
-	const uint32_t piece = std::min (nblocks, TBF_PCM_PIECE), fb = pcm_frame_bytes (o.format);
+	const uint32_t piece = std::min (nblocks, TBF_STAGE_PIECE), fb = pcm_frame_bytes (o.format);
 	const size_t   per = (size_t)nblocks * TBF_BLK, pframes = (size_t)piece * TBF_BLK, plane = (size_t)n * pframes;
 	if (e->rotBuf.ensure (2 * plane) ||
 	    (host && (c.hostOut.ensure (plane * fb) || (o.meters && c.hostMeters.ensure (n)) || (in && e->extBuf.ensure ((size_t)n * per))))) {
@@ -213,7 +168,8 @@ int renderPcm (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t ne
 		return rc;
 	const float* dIn = in;
 	if (host && in) {
-		HIPCHK (hipMemcpy2DAsync (e->extBuf.p, per * 4, in, inStride * 4, per * 4, n, hipMemcpyHostToDevice, s));
+		if (int rc = stageHostInput (e->extBuf.p, in, inStride, per, n, s))
+			return rc;
 		dIn      = e->extBuf.p;
 		inStride = per;
 	}
@@ -224,27 +180,11 @@ int renderPcm (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t ne
 	P.meters   = o.meters ? (host ? c.hostMeters.p : o.meters) : nullptr;
 	if (P.meters)
 		HIPCHK (hipMemsetAsync (P.meters, 0, (size_t)n * sizeof (tbf_pcm_meter), s));
-	std::vector<tbf_event> pev;
-	uint32_t               evi = 0;
-	for (uint32_t p0 = 0; p0 < nblocks; p0 += piece) {
-		const uint32_t len  = std::min (piece, nblocks - p0);
-		const bool     last = p0 + len == nblocks;
-		/* the piece's events, their blocks counted from the piece; the last piece takes those
-		 * at or beyond the call's end too, which apply after it */
-		uint32_t evEnd = evi;
-		while (evEnd < nev && (last || ev[evEnd].block < p0 + len))
-			evEnd++;
-		const tbf_event* pe = ev + evi;
-		if (p0 && evEnd > evi) {
-			pev.assign (ev + evi, ev + evEnd);
-			for (tbf_event& v : pev)
-				v.block -= p0;
-			pe = pev.data ();
-		}
-		if (int rc = plainRender (e, len, evEnd > evi ? pe : nullptr, evEnd - evi, dIn ? dIn + (size_t)p0 * TBF_BLK : nullptr,
-		                          inStride, pl, pr, pframes, s))
+	for (Pieces pc (ev, nev, nblocks, piece); pc.next ();) {
+		const uint32_t p0 = pc.p0, len = pc.len;
+		if (int rc = plainRender (e, len, pc.npe ? pc.pe : nullptr, pc.npe, dIn ? dIn + (size_t)p0 * TBF_BLK : nullptr, inStride, pl,
+		                          pr, pframes, s))
 			return rc;
-		evi = evEnd;
 		const size_t off = (size_t)p0 * TBF_BLK * fb, rowBytes = (size_t)len * TBF_BLK * fb;
 		P.out            = host ? c.hostOut.p : (unsigned char*)o.out + off;
 		P.outStride      = host ? rowBytes : o.out_stride_bytes;
@@ -295,19 +235,16 @@ int tbf_pcm_convert_device (tbf_engine* e, uint32_t n_rows, const float* d_L, co
 		return fail (-22, "pcm: device pointer not 4-byte aligned");
 	if (in_stride < frames)
 		return fail (-22, "in_stride smaller than frames");
-	uint32_t most = counts ? 0u : frames;
-	for (uint32_t r = 0; counts && r < n_rows; r++) {
-		if (counts[r] > frames)
-			return fail (-22, "pcm: counts[" + std::to_string (r) + "] above frames");
-		most = std::max (most, counts[r]);
-	}
+	uint32_t most;
+	if (int rc = countsMost ("pcm", counts, n_rows, frames, &most))
+		return rc;
 	const float* const in[2] = {d_L, d_R};
 	if (int rc = rangesApart (out, n_rows, frames, in, 2, in_stride))
 		return rc;
 	if (e->cfg.device < 0)
 		return fail (-19, "host-only engine (device -1) has no device to convert on");
 	HIPCHK (hipSetDevice (e->cfg.device));
-	hipStream_t const s = stream ? (hipStream_t)stream : e->stream;
+	hipStream_t const s = streamOr (stream, e->stream);
 	if (n_rows == 0)
 		return 0;
 	tbf_pcm_launch P = launchOf (*out);
@@ -338,7 +275,7 @@ int tbf_render_pcm_device (tbf_engine* e, uint32_t nblocks, const tbf_event* ev,
 {
 	if (int rc = renderArgs (e, nblocks, ev, nev, false, nullptr, 0, out, true))
 		return rc;
-	return renderPcm (e, nblocks, ev, nev, nullptr, 0, *out, stream ? (hipStream_t)stream : e->stream, false);
+	return renderPcm (e, nblocks, ev, nev, nullptr, 0, *out, streamOr (stream, e->stream), false);
 }
 
 int tbf_process_pcm (tbf_engine* e, uint32_t nblocks, const float* in, uint64_t inStride, const tbf_pcm_out* out)
@@ -353,7 +290,7 @@ int tbf_process_pcm_device (tbf_engine* e, uint32_t nblocks, const tbf_event* ev
 {
 	if (int rc = renderArgs (e, nblocks, ev, nev, true, dIn, inStride, out, true))
 		return rc;
-	return renderPcm (e, nblocks, ev, nev, dIn, inStride, *out, stream ? (hipStream_t)stream : e->stream, false);
+	return renderPcm (e, nblocks, ev, nev, dIn, inStride, *out, streamOr (stream, e->stream), false);
 }
 
 int tbf_debug_pcm_ref (uint32_t format, uint32_t flags, uint32_t seed, uint32_t row, uint64_t frame0, const float* L,
@@ -386,26 +323,7 @@ int tbf_debug_pcm_time (tbf_engine* e, int32_t enable, double* ms, uint64_t* lau
 {
 	if (!e)
 		return fail (-22, "null argument");
-	tbf_engine::Pcm& c = e->pcm;
-	if (enable) {
-		c.timeOn = enable > 0;
-		return 0;
-	}
-	double sum = 0.0;
-	for (auto& p : c.tev) {
-		float t = 0.f;
-		HIPCHK (hipEventSynchronize (p.second));
-		HIPCHK (hipEventElapsedTime (&t, p.first, p.second));
-		sum += t;
-		(void)hipEventDestroy (p.first);
-		(void)hipEventDestroy (p.second);
-	}
-	if (ms)
-		*ms = sum;
-	if (launches)
-		*launches = c.tev.size ();
-	c.tev.clear ();
-	return 0;
+	return e->pcm.timer.query (enable, ms, launches);
 }
 
 } /* extern "C" */

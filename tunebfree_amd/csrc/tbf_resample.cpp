@@ -12,7 +12,7 @@
  * known before anything is launched and the call never waits for the device to learn them.
  * Scratch: with the caller's raw planes there is none.  Without them the pair goes to engine
  * scratch (tbf_engine.rotBuf), 8 B per instance and sample, and the call is cut into pieces of at
- * most TBF_RS_PIECE blocks, so the scratch never exceeds n x TBF_RS_PIECE x 128 x 8 B; the pieces
+ * most TBF_STAGE_PIECE blocks, so the scratch never exceeds n x TBF_STAGE_PIECE x 128 x 8 B; the pieces
  * deliver what one call delivers, bit for bit, like any other cut.  -12 when the device cannot
  * hold it.
  */
@@ -29,23 +29,10 @@
 #include "tbf_resample.h"
 
 extern "C" int tbf_launch_resample (const tbf_rs_launch* P, hipStream_t stream);
-extern "C" int tbf_chain_first_stage (uint32_t chain);
 
 using namespace tbf;
 
-#define HIPCHK(x)                                                                        \
-	do {                                                                                 \
-		hipError_t _e = (x);                                                             \
-		if (_e != hipSuccess)                                                            \
-			return fail (-5, std::string (#x ": ") + hipGetErrorString (_e));           \
-	} while (0)
-
-/* blocks per piece of a call that renders its L / R into engine scratch */
-#define TBF_RS_PIECE 256u
-
 namespace {
-
-bool chainFx (uint32_t chain) { return tbf_chain_first_stage (chain) > 0; }
 
 /* I0 (x), the power series in double, to the last term that changes the sum */
 double besselI0 (double x)
@@ -102,11 +89,6 @@ int uploadTable (tbf_engine* e)
 	return 0;
 }
 
-struct Range {
-	const float* p;
-	uint64_t     stride, len;
-};
-
 /* The checks of the resampled calls, all before anything renders or steps (in: the effects-only
  * calls' input rows); pointers are compared on the host only. */
 int resampleArgs (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t nev, bool fx, const float* in,
@@ -133,24 +115,13 @@ int resampleArgs (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32_t
 	if (fx && inStride < per)
 		return fail (-22, "in_stride smaller than nblocks*128");
 	const uint64_t n = e->inst.size ();
-	if (n && per) { /* [first float, one past the last float) of each range, pairwise */
-		Range g[5];
-		int   ng = 0;
-		g[ng++]  = {o->L, o->stride, frames};
-		g[ng++]  = {o->R, o->stride, frames};
-		if (o->rawL) {
-			g[ng++] = {o->rawL, o->raw_stride, per};
-			g[ng++] = {o->rawR, o->raw_stride, per};
-		}
-		if (fx)
-			g[ng++] = {in, inStride, per};
-		for (int a = 0; a < ng; a++)
-			for (int b = a + 1; b < ng; b++) {
-				const uintptr_t a0 = (uintptr_t)g[a].p, a1 = (uintptr_t)(g[a].p + (n - 1) * g[a].stride + g[a].len);
-				const uintptr_t b0 = (uintptr_t)g[b].p, b1 = (uintptr_t)(g[b].p + (n - 1) * g[b].stride + g[b].len);
-				if (a0 < b1 && b0 < a1)
-					return fail (-22, "input, resampled and raw ranges overlap");
-			}
+	{ /* every range against every other.  Without instances or blocks all are empty; with both,
+	   * frames = ceil (per L / M) >= 1, so the resampled rows are never empty beside raw ones that are not */
+		const Span g[5] = {rowsSpan (o->L, n, o->stride * 4, frames * 4), rowsSpan (o->R, n, o->stride * 4, frames * 4),
+		                   rowsSpan (o->rawL, n, o->raw_stride * 4, per * 4), rowsSpan (o->rawR, n, o->raw_stride * 4, per * 4),
+		                   rowsSpan (fx ? in : nullptr, n, inStride * 4, per * 4)};
+		if (anyOverlap (g, 5))
+			return fail (-22, "input, resampled and raw ranges overlap");
 	}
 	if (int rc = eventsInOrder (ev, nev))
 		return rc;
@@ -174,7 +145,7 @@ int resampleDevice (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32
 		return 0;
 	}
 	const bool     raw   = o.rawL != nullptr;
-	const uint32_t piece = raw ? nblocks : std::min (nblocks, TBF_RS_PIECE);
+	const uint32_t piece = raw ? nblocks : std::min (nblocks, TBF_STAGE_PIECE);
 	float *        pl = o.rawL, *pr = o.rawR;
 	uint64_t       pstride = o.raw_stride;
 	if (!raw) {
@@ -201,23 +172,8 @@ int resampleDevice (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32
 	/* every allocation of the call has succeeded: only now the caller's counts are written */
 	for (uint32_t i = 0; i < n; i++)
 		o.counts[i] = (uint32_t)(rs_count (pos0[i] + (uint64_t)nblocks * TBF_BLK, r.L, r.M) - rs_count (pos0[i], r.L, r.M));
-	std::vector<tbf_event> pev;
-	uint32_t               evi = 0;
-	for (uint32_t p0 = 0; p0 < nblocks; p0 += piece) {
-		const uint32_t len  = std::min (piece, nblocks - p0);
-		const bool     last = p0 + len == nblocks;
-		/* the piece's events, their blocks counted from the piece; the last piece takes those
-		 * at or beyond the call's end too, which apply after it */
-		uint32_t evEnd = evi;
-		while (evEnd < nev && (last || ev[evEnd].block < p0 + len))
-			evEnd++;
-		const tbf_event* pe = ev + evi;
-		if (p0 && evEnd > evi) {
-			pev.assign (ev + evi, ev + evEnd);
-			for (tbf_event& v : pev)
-				v.block -= p0;
-			pe = pev.data ();
-		}
+	for (Pieces pc (ev, nev, nblocks, piece); pc.next ();) {
+		const uint32_t p0 = pc.p0, len = pc.len;
 		tbf_rs_launch P;
 		memset (&P, 0, sizeof (P));
 		if (!uni) {
@@ -233,10 +189,9 @@ int resampleDevice (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32
 			P.pos = r.pos.p;
 		}
 		const size_t off = raw ? (size_t)p0 * TBF_BLK : 0;
-		if (int rc = plainRender (e, len, evEnd > evi ? pe : nullptr, evEnd - evi, dIn ? dIn + (size_t)p0 * TBF_BLK : nullptr,
-		                          inStride, pl + off, pr + off, pstride, s))
+		if (int rc = plainRender (e, len, pc.npe ? pc.pe : nullptr, pc.npe, dIn ? dIn + (size_t)p0 * TBF_BLK : nullptr, inStride,
+		                          pl + off, pr + off, pstride, s))
 			return rc;
-		evi          = evEnd;
 		P.in[0]      = pl + off;
 		P.in[1]      = pr + off;
 		P.inStride   = pstride;
@@ -257,30 +212,13 @@ int resampleDevice (tbf_engine* e, uint32_t nblocks, const tbf_event* ev, uint32
 		P.TS         = r.TS;
 		P.winFloats  = r.winFloats;
 		P.ldsRow     = r.ldsRow;
-		hipEvent_t t0 = nullptr, t1 = nullptr;
-		auto       drop = [&] () { /* a failed step between the events' creation and their hand-over to tev */
-			if (t0)
-				(void)hipEventDestroy (t0);
-			if (t1)
-				(void)hipEventDestroy (t1);
-		};
-		if (r.timeOn) { /* tbf_debug_resample_time: k_resample between two events on its stream */
-			if (hipEventCreate (&t0) != hipSuccess || hipEventCreate (&t1) != hipSuccess || hipEventRecord (t0, s) != hipSuccess) {
-				drop ();
-				return fail (-5, std::string ("resampler timing events: ") + hipGetErrorString (hipGetLastError ()));
-			}
-		}
-		if (tbf_launch_resample (&P, s)) {
-			drop ();
+		StageTimer::Guard tg (r.timer, s, "resampler"); /* tbf_debug_resample_time: k_resample between two events on its stream */
+		if (int rc = tg.begin ())
+			return rc;
+		if (tbf_launch_resample (&P, s))
 			return fail (-5, std::string ("k_resample launch failed: ") + hipGetErrorString (hipGetLastError ()));
-		}
-		if (r.timeOn) {
-			if (hipEventRecord (t1, s) != hipSuccess) {
-				drop ();
-				return fail (-5, std::string ("resampler timing events: ") + hipGetErrorString (hipGetLastError ()));
-			}
-			r.tev.push_back ({t0, t1});
-		}
+		if (int rc = tg.end ())
+			return rc;
 		r.launches++;
 		for (uint32_t i = 0; i < n; i++)
 			e->inst[i].rsPos += (uint64_t)len * TBF_BLK;
@@ -306,7 +244,8 @@ int resampleHost (tbf_engine* e, uint32_t nblocks, const float* in, uint64_t inS
 		return fail (-12, "out of device memory (resampled outputs)");
 	}
 	if (in)
-		HIPCHK (hipMemcpy2DAsync (e->extBuf.p, per * 4, in, inStride * 4, per * 4, n, hipMemcpyHostToDevice, e->stream));
+		if (int rc = stageHostInput (e->extBuf.p, in, inStride, per, n, e->stream))
+			return rc;
 	tbf_resampled_out d = {r.hostOut.p, r.hostOut.p + oplane, nullptr, nullptr, frames, per, o->counts};
 	if (o->rawL) {
 		d.rawL = e->outL.p;
@@ -424,7 +363,7 @@ int tbf_render_resampled_device (tbf_engine* e, uint32_t nblocks, const tbf_even
 	if (int rc = resampleArgs (e, nblocks, ev, nev, false, nullptr, 0, out))
 		return rc;
 	HIPCHK (hipSetDevice (e->cfg.device));
-	return resampleDevice (e, nblocks, ev, nev, nullptr, 0, *out, stream ? (hipStream_t)stream : e->stream);
+	return resampleDevice (e, nblocks, ev, nev, nullptr, 0, *out, streamOr (stream, e->stream));
 }
 
 int tbf_process_resampled (tbf_engine* e, uint32_t nblocks, const float* in, uint64_t inStride, const tbf_resampled_out* out)
@@ -440,7 +379,7 @@ int tbf_process_resampled_device (tbf_engine* e, uint32_t nblocks, const tbf_eve
 	if (int rc = resampleArgs (e, nblocks, ev, nev, true, dIn, inStride, out))
 		return rc;
 	HIPCHK (hipSetDevice (e->cfg.device));
-	return resampleDevice (e, nblocks, ev, nev, dIn, inStride, *out, stream ? (hipStream_t)stream : e->stream);
+	return resampleDevice (e, nblocks, ev, nev, dIn, inStride, *out, streamOr (stream, e->stream));
 }
 
 int tbf_debug_resampler (const tbf_engine* e, uint32_t* L, uint32_t* M, uint32_t* T, float* table, uint64_t cap,
@@ -507,26 +446,7 @@ int tbf_debug_resample_time (tbf_engine* e, int32_t enable, double* ms, uint64_t
 {
 	if (!e)
 		return fail (-22, "null argument");
-	tbf_engine::Resampler& r = e->rs;
-	if (enable) {
-		r.timeOn = enable > 0;
-		return 0;
-	}
-	double sum = 0.0;
-	for (auto& p : r.tev) {
-		float t = 0.f;
-		HIPCHK (hipEventSynchronize (p.second));
-		HIPCHK (hipEventElapsedTime (&t, p.first, p.second));
-		sum += t;
-		(void)hipEventDestroy (p.first);
-		(void)hipEventDestroy (p.second);
-	}
-	if (ms)
-		*ms = sum;
-	if (launches)
-		*launches = r.tev.size ();
-	r.tev.clear ();
-	return 0;
+	return e->rs.timer.query (enable, ms, launches);
 }
 
 } /* extern "C" */

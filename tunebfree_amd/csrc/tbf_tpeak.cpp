@@ -28,13 +28,6 @@ extern "C" int tbf_launch_tpeak (const tbf_tpeak_launch* P, hipStream_t stream);
 
 using namespace tbf;
 
-#define HIPCHK(x)                                                                        \
-	do {                                                                                 \
-		hipError_t _e = (x);                                                             \
-		if (_e != hipSuccess)                                                            \
-			return fail (-5, std::string (#x ": ") + hipGetErrorString (_e));           \
-	} while (0)
-
 namespace {
 
 int checkConfig (const tbf_true_peak_config* cfg)
@@ -44,22 +37,6 @@ int checkConfig (const tbf_true_peak_config* cfg)
 	if (cfg->oversample != 1u && cfg->oversample != 2u && cfg->oversample != 4u)
 		return fail (-22, "true_peak: oversample " + std::to_string (cfg->oversample) + " is none of 1, 2, 4");
 	return 0;
-}
-
-int checkRows (const tbf_true_peak* tp, uint32_t n, const uint32_t* rows)
-{
-	for (uint32_t k = 0; rows && k < n; k++)
-		if (rows[k] >= tp->nRows)
-			return fail (-22, "true_peak: rows[" + std::to_string (k) + "] " + std::to_string (rows[k]) + " is no row of n_rows " +
-			                      std::to_string (tp->nRows));
-	return 0;
-}
-
-/* the meter's slot in its engine's list, or the list's end */
-std::vector<std::unique_ptr<tbf_true_peak>>::iterator slotOf (tbf_true_peak* tp)
-{
-	auto& v = tp->eng->truePeaks;
-	return std::find_if (v.begin (), v.end (), [tp] (const std::unique_ptr<tbf_true_peak>& p) { return p.get () == tp; });
 }
 
 float asFloat (uint32_t u)
@@ -120,7 +97,7 @@ int tbf_true_peak_destroy (tbf_true_peak* tp)
 {
 	if (!tp)
 		return 0;
-	auto it = slotOf (tp);
+	auto it = slotOf (tp->eng->truePeaks, tp);
 	if (it == tp->eng->truePeaks.end ())
 		return fail (-22, "true_peak: not a meter of its engine");
 	(void)hipSetDevice (tp->eng->cfg.device);
@@ -132,10 +109,10 @@ int tbf_true_peak_reset (tbf_true_peak* tp, uint32_t n, const uint32_t* rows, vo
 {
 	if (!tp)
 		return fail (-22, "true_peak: tp is NULL");
-	if (int rc = checkRows (tp, n, rows))
+	if (int rc = checkRows ("true_peak", n, rows, tp->nRows))
 		return rc;
 	HIPCHK (hipSetDevice (tp->eng->cfg.device));
-	hipStream_t const s  = stream ? (hipStream_t)stream : tp->eng->stream;
+	hipStream_t const s  = streamOr (stream, tp->eng->stream);
 	const size_t      hb = TBF_TPEAK_ROW_HIST * sizeof (float), pb = 4u * sizeof (uint32_t); /* a row's history, both sides, and its peaks */
 	if (!rows) {
 		HIPCHK (hipMemsetAsync (tp->hist.p, 0, (size_t)tp->nRows * hb, s));
@@ -163,18 +140,15 @@ int tbf_true_peak_device (tbf_true_peak* tp, const float* d_L, const float* d_R,
 	if (((uintptr_t)d_L | (uintptr_t)d_R) & 3u)
 		return fail (-22, "true_peak: device pointer not 4-byte aligned");
 	const uint32_t n    = tp->nRows;
-	uint32_t       most = counts ? 0u : frames;
-	for (uint32_t r = 0; counts && r < n; r++) {
-		if (counts[r] > frames)
-			return fail (-22, "true_peak: counts[" + std::to_string (r) + "] above frames");
-		most = std::max (most, counts[r]);
-	}
+	uint32_t       most;
+	if (int rc = countsMost ("true_peak", counts, n, frames, &most))
+		return rc;
 	const uint32_t tiles = (uint32_t)(((uint64_t)most + TBF_TPEAK_TILE - 1u) / TBF_TPEAK_TILE);
 	if ((uint64_t)n * tiles > 0x7fffffffull)
 		return fail (-22, "true_peak: frames " + std::to_string (most) + " of " + std::to_string (n) + " rows are more than one launch's 2^31 - 1 tiles");
 	tbf_engine* const e = tp->eng;
 	HIPCHK (hipSetDevice (e->cfg.device));
-	hipStream_t const s = stream ? (hipStream_t)stream : e->stream;
+	hipStream_t const s = streamOr (stream, e->stream);
 	if (most == 0)
 		return 0;
 	/* The rows on the device.  They are read from the meter's host vector, which the next call
@@ -196,37 +170,18 @@ int tbf_true_peak_device (tbf_true_peak* tp, const float* d_L, const float* d_R,
 	P.tiles    = tiles;
 	P.F        = tp->cfg.oversample;
 
-	hipEvent_t t0 = nullptr, t1 = nullptr;
-	auto       drop = [&] () { /* a failed step between the events' creation and their hand-over to tev */
-		if (t0)
-			(void)hipEventDestroy (t0);
-		if (t1)
-			(void)hipEventDestroy (t1);
-	};
-	if (tp->timeOn) { /* tbf_debug_true_peak_time: the launch between two events on its stream */
-		if (hipEventCreate (&t0) != hipSuccess || hipEventCreate (&t1) != hipSuccess || hipEventRecord (t0, s) != hipSuccess) {
-			drop ();
-			return fail (-5, std::string ("true_peak timing events: ") + hipGetErrorString (hipGetLastError ()));
-		}
-	}
-	if (tbf_launch_tpeak (&P, s)) {
-		drop ();
+	StageTimer::Guard tg (tp->timer, s, "true_peak"); /* tbf_debug_true_peak_time: the launch between two events on its stream */
+	if (int rc = tg.begin ())
+		return rc;
+	if (tbf_launch_tpeak (&P, s))
 		return fail (-5, std::string ("k_tpeak launch failed: ") + hipGetErrorString (hipGetLastError ()));
-	}
 	for (uint32_t r = 0; r < n; r++)
 		if (tp->rows[r].count) { /* the launch wrote the other side of the rows that took frames */
 			tp->rows[r].side ^= 1u;
 			tp->pos[r] += tp->rows[r].count;
 		}
 	tp->last = s;
-	if (tp->timeOn) {
-		if (hipEventRecord (t1, s) != hipSuccess) {
-			drop ();
-			return fail (-5, std::string ("true_peak timing events: ") + hipGetErrorString (hipGetLastError ()));
-		}
-		tp->tev.push_back ({t0, t1});
-	}
-	return 0;
+	return tg.end ();
 }
 
 int tbf_true_peak_read (tbf_true_peak* tp, uint32_t n, const uint32_t* rows, tbf_true_peak_result* out)
@@ -237,7 +192,7 @@ int tbf_true_peak_read (tbf_true_peak* tp, uint32_t n, const uint32_t* rows, tbf
 		return fail (-22, "true_peak: out is NULL");
 	if (!rows)
 		n = tp->nRows;
-	if (int rc = checkRows (tp, n, rows))
+	if (int rc = checkRows ("true_peak", n, rows, tp->nRows))
 		return rc;
 	HIPCHK (hipSetDevice (tp->eng->cfg.device));
 	HIPCHK (hipStreamSynchronize (tp->last ? tp->last : tp->eng->stream));
@@ -329,25 +284,7 @@ int tbf_debug_true_peak_time (tbf_true_peak* tp, int32_t enable, double* ms, uin
 {
 	if (!tp)
 		return fail (-22, "true_peak: tp is NULL");
-	if (enable) {
-		tp->timeOn = enable > 0;
-		return 0;
-	}
-	double sum = 0.0;
-	for (auto& p : tp->tev) {
-		float t = 0.f;
-		HIPCHK (hipEventSynchronize (p.second));
-		HIPCHK (hipEventElapsedTime (&t, p.first, p.second));
-		sum += t;
-		(void)hipEventDestroy (p.first);
-		(void)hipEventDestroy (p.second);
-	}
-	if (ms)
-		*ms = sum;
-	if (launches)
-		*launches = tp->tev.size ();
-	tp->tev.clear ();
-	return 0;
+	return tp->timer.query (enable, ms, launches);
 }
 
 } /* extern "C" */

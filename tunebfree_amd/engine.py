@@ -223,6 +223,9 @@ SIGNATURES = {
     "tbf_true_peak_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tbf_true_peak_read": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
 }
+# the stages' timing hooks (_stage_time), which share one signature; debug calls stay out of SIGNATURES
+STAGE_TIME = {f"tbf_debug_{stage}_time": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_uint64)])
+              for stage in ("cabinet", "resample", "pcm", "mix", "limit", "loudness", "true_peak")}
 
 # tbf_engine_config.chain_mode of the effects-only chains (include/tbf.h TBF_CHAIN_FX*)
 CHAIN_FX, CHAIN_FX_TAP_PREAMP, CHAIN_FX_TAP_REVERB = 4, 5, 6
@@ -244,7 +247,7 @@ def load_library():
         if not LIB_PATH.exists():
             raise TbfError(f"{LIB_PATH} not built -- run __graft_entry__.build() or `make -C tunebfree_amd`")
         lib = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **STAGE_TIME}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib
@@ -255,6 +258,40 @@ def _check(rc):
     if rc < 0:
         raise TbfError(f"tbf error {rc}: {load_library().tbf_last_error().decode(errors='replace')}")
     return rc
+
+
+def _stage_time(fn, handle, enable):
+    """a stage's tbf_debug_*_time call fn on its engine or object: enable True / False switches its
+    timing on / off and returns None; None returns (milliseconds, launch sets) since the last query"""
+    if enable is not None:
+        _check(fn(handle, 1 if enable else -1, None, None))
+        return None
+    ms, n = C.c_double(), C.c_uint64()
+    _check(fn(handle, 0, C.byref(ms), C.byref(n)))
+    return ms.value, n.value
+
+
+def _ptr(p):
+    """an optional device pointer or stream as a call's argument"""
+    return None if p is None else C.c_void_p(int(p))
+
+
+def _rows_arg(rows):
+    """a stage object's rows argument (None: all): (n, pointer, the array the pointer reads)"""
+    if rows is None:
+        return 0, None, None
+    r = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+    return len(r), r.ctypes.data, r
+
+
+def _counts_arg(counts, n_rows):
+    """a stage object's counts argument (None: every row whole): (pointer, the array it reads)"""
+    if counts is None:
+        return None, None
+    c = np.ascontiguousarray(counts, dtype=np.uint32)
+    if len(c) != n_rows:
+        raise ValueError(f"{len(c)} counts for {n_rows} rows")
+    return c.ctypes.data, c
 
 
 class Limiter:
@@ -283,33 +320,20 @@ class Limiter:
         r * in_stride floats; L_ptr == R_ptr: mono), `frames` frames per row or counts[r] (host
         array) of them, into outL_ptr / outR_ptr, out_stride floats apart; meters_ptr None or
         device memory of one tbf_limit_meter (12 B) per row."""
-        c = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
-        if c is not None and len(c) != self.n_rows:
-            raise ValueError(f"{len(c)} counts for {self.n_rows} rows")
-        lo = LimitOut(None if outL_ptr is None else int(outL_ptr), None if outR_ptr is None else int(outR_ptr),
-                      int(out_stride), None if meters_ptr is None else int(meters_ptr))
-        _check(self._lib.tbf_limit_device(
-            self._h, None if L_ptr is None else C.c_void_p(int(L_ptr)), None if R_ptr is None else C.c_void_p(int(R_ptr)),
-            int(in_stride), int(frames), None if c is None else c.ctypes.data, C.byref(lo),
-            None if stream is None else C.c_void_p(int(stream))))
+        cp, _c = _counts_arg(counts, self.n_rows)
+        lo = LimitOut(_ptr(outL_ptr), _ptr(outR_ptr), int(out_stride), _ptr(meters_ptr))
+        _check(self._lib.tbf_limit_device(self._h, _ptr(L_ptr), _ptr(R_ptr), int(in_stride), int(frames), cp, C.byref(lo),
+                                          _ptr(stream)))
 
     def reset(self, rows=None, stream=None):
         """tbf_limiter_reset: the rows (None: all) start anew, ordered on the stream"""
-        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
-        _check(self._lib.tbf_limiter_reset(self._h, 0 if r is None else len(r), None if r is None else r.ctypes.data,
-                                           None if stream is None else C.c_void_p(int(stream))))
+        n, rp, _r = _rows_arg(rows)
+        _check(self._lib.tbf_limiter_reset(self._h, n, rp, _ptr(stream)))
 
     def time(self, enable=None):
         """tbf_debug_limit_time: enable True / False switches the event pair around every call's
         launches on / off; None returns (milliseconds, launch sets) since the last query."""
-        f = self._lib.tbf_debug_limit_time
-        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_uint64)]
-        if enable is not None:
-            _check(f(self._h, 1 if enable else -1, None, None))
-            return None
-        ms, n = C.c_double(), C.c_uint64()
-        _check(f(self._h, 0, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
+        return _stage_time(self._lib.tbf_debug_limit_time, self._h, enable)
 
     def close(self):
         """tbf_limiter_destroy (the engine does it for the limiters still alive when it closes)"""
@@ -331,22 +355,16 @@ class Loudness:
         """tbf_loudness_device: the meter's rows of the device planes L_ptr / R_ptr (row r at
         r * in_stride floats; L_ptr == R_ptr: a pair of equal channels) take `frames` frames, or
         counts[r] (host array) of them; the planes are only read."""
-        c = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
-        if c is not None and len(c) != self.n_rows:
-            raise ValueError(f"{len(c)} counts for {self.n_rows} rows")
-        _check(self._lib.tbf_loudness_device(
-            self._h, None if L_ptr is None else C.c_void_p(int(L_ptr)), None if R_ptr is None else C.c_void_p(int(R_ptr)),
-            int(in_stride), int(frames), None if c is None else c.ctypes.data,
-            None if stream is None else C.c_void_p(int(stream))))
+        cp, _c = _counts_arg(counts, self.n_rows)
+        _check(self._lib.tbf_loudness_device(self._h, _ptr(L_ptr), _ptr(R_ptr), int(in_stride), int(frames), cp, _ptr(stream)))
 
     def read(self, rows=None):
         """tbf_loudness_read: LOUDNESS_RESULT_DTYPE records of the rows (None: all), after the
         meter's last call has passed its stream"""
         from .params import LOUDNESS_RESULT_DTYPE
-        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
-        out = np.zeros(self.n_rows if r is None else len(r), LOUDNESS_RESULT_DTYPE)
-        _check(self._lib.tbf_loudness_read(self._h, 0 if r is None else len(r), None if r is None else r.ctypes.data,
-                                           out.ctypes.data))
+        n, rp, _r = _rows_arg(rows)
+        out = np.zeros(self.n_rows if rows is None else n, LOUDNESS_RESULT_DTYPE)
+        _check(self._lib.tbf_loudness_read(self._h, n, rp, out.ctypes.data))
         return out
 
     def hops(self, row):
@@ -370,30 +388,21 @@ class Loudness:
 
     def reset(self, rows=None, stream=None):
         """tbf_loudness_reset: the rows (None: all) start anew, ordered on the stream"""
-        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
-        _check(self._lib.tbf_loudness_reset(self._h, 0 if r is None else len(r), None if r is None else r.ctypes.data,
-                                            None if stream is None else C.c_void_p(int(stream))))
+        n, rp, _r = _rows_arg(rows)
+        _check(self._lib.tbf_loudness_reset(self._h, n, rp, _ptr(stream)))
 
     def timing(self, enable=None):
         """tbf_debug_loudness_time: enable True / False switches the event pair around every call's
         launch on / off; None returns (milliseconds, launch sets) since the last query."""
-        f = self._lib.tbf_debug_loudness_time
-        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_uint64)]
-        if enable is not None:
-            _check(f(self._h, 1 if enable else -1, None, None))
-            return None
-        ms, n = C.c_double(), C.c_uint64()
-        _check(f(self._h, 0, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
+        return _stage_time(self._lib.tbf_debug_loudness_time, self._h, enable)
 
     def range(self, rows=None):
         """tbf_loudness_range: (loudness range in LU [k] float64, the short-term windows behind it [k]
         uint32) of the rows (None: all), after the meter's last call has passed its stream"""
-        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
-        k = self.n_rows if r is None else len(r)
+        n, rp, _r = _rows_arg(rows)
+        k = self.n_rows if rows is None else n
         lra, win = np.zeros(k, np.float64), np.zeros(k, np.uint32)
-        _check(self._lib.tbf_loudness_range(self._h, 0 if r is None else len(r), None if r is None else r.ctypes.data,
-                                            lra.ctypes.data, win.ctypes.data))
+        _check(self._lib.tbf_loudness_range(self._h, n, rp, lra.ctypes.data, win.ctypes.data))
         return lra, win
 
     def close(self):
@@ -421,22 +430,16 @@ class TruePeak:
         """tbf_true_peak_device: the meter's rows of the device planes L_ptr / R_ptr (row r at
         r * in_stride floats; L_ptr == R_ptr: a pair of equal channels) take `frames` frames, or
         counts[r] (host array) of them; the planes are only read."""
-        c = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
-        if c is not None and len(c) != self.n_rows:
-            raise ValueError(f"{len(c)} counts for {self.n_rows} rows")
-        _check(self._lib.tbf_true_peak_device(
-            self._h, None if L_ptr is None else C.c_void_p(int(L_ptr)), None if R_ptr is None else C.c_void_p(int(R_ptr)),
-            int(in_stride), int(frames), None if c is None else c.ctypes.data,
-            None if stream is None else C.c_void_p(int(stream))))
+        cp, _c = _counts_arg(counts, self.n_rows)
+        _check(self._lib.tbf_true_peak_device(self._h, _ptr(L_ptr), _ptr(R_ptr), int(in_stride), int(frames), cp, _ptr(stream)))
 
     def read(self, rows=None):
         """tbf_true_peak_read: TRUE_PEAK_RESULT_DTYPE records of the rows (None: all), after the
         meter's last call has passed its stream"""
         from .params import TRUE_PEAK_RESULT_DTYPE
-        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
-        out = np.zeros(self.n_rows if r is None else len(r), TRUE_PEAK_RESULT_DTYPE)
-        _check(self._lib.tbf_true_peak_read(self._h, 0 if r is None else len(r), None if r is None else r.ctypes.data,
-                                            out.ctypes.data))
+        n, rp, _r = _rows_arg(rows)
+        out = np.zeros(self.n_rows if rows is None else n, TRUE_PEAK_RESULT_DTYPE)
+        _check(self._lib.tbf_true_peak_read(self._h, n, rp, out.ctypes.data))
         return out
 
     def gains(self, ceiling_dbtp):
@@ -452,21 +455,13 @@ class TruePeak:
 
     def reset(self, rows=None, stream=None):
         """tbf_true_peak_reset: the rows (None: all) start anew, ordered on the stream"""
-        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
-        _check(self._lib.tbf_true_peak_reset(self._h, 0 if r is None else len(r), None if r is None else r.ctypes.data,
-                                             None if stream is None else C.c_void_p(int(stream))))
+        n, rp, _r = _rows_arg(rows)
+        _check(self._lib.tbf_true_peak_reset(self._h, n, rp, _ptr(stream)))
 
     def timing(self, enable=None):
         """tbf_debug_true_peak_time: enable True / False switches the event pair around every call's
         launch on / off; None returns (milliseconds, launches) since the last query."""
-        f = self._lib.tbf_debug_true_peak_time
-        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_uint64)]
-        if enable is not None:
-            _check(f(self._h, 1 if enable else -1, None, None))
-            return None
-        ms, n = C.c_double(), C.c_uint64()
-        _check(f(self._h, 0, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
+        return _stage_time(self._lib.tbf_debug_true_peak_time, self._h, enable)
 
     def close(self):
         """tbf_true_peak_destroy (the engine does it for the meters still alive when it closes)"""
@@ -834,14 +829,7 @@ class Engine:
     def cabinet_time(self, enable=None):
         """tbf_debug_cabinet_time: enable True / False switches the event pair around every
         k_cabinet launch on / off; None returns (milliseconds, launches) since the last query."""
-        f = self._lib.tbf_debug_cabinet_time
-        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_uint64)]
-        if enable is not None:
-            _check(f(self._h, 1 if enable else -1, None, None))
-            return None
-        ms, n = C.c_double(), C.c_uint64()
-        _check(f(self._h, 0, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
+        return _stage_time(self._lib.tbf_debug_cabinet_time, self._h, enable)
 
     def _cabinet_host(self, nblocks, wet, rotors, call):
         shape = (self.n_instances, nblocks * 128)
@@ -951,14 +939,7 @@ class Engine:
     def resample_time(self, enable=None):
         """tbf_debug_resample_time: enable True / False switches the event pair around every
         k_resample launch on / off; None returns (milliseconds, launches) since the last query."""
-        f = self._lib.tbf_debug_resample_time
-        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_uint64)]
-        if enable is not None:
-            _check(f(self._h, 1 if enable else -1, None, None))
-            return None
-        ms, n = C.c_double(), C.c_uint64()
-        _check(f(self._h, 0, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
+        return _stage_time(self._lib.tbf_debug_resample_time, self._h, enable)
 
     def _resampled_host(self, nblocks, raw, call):
         n, frames = self.n_instances, self.resampled_frames(nblocks)
@@ -1046,14 +1027,7 @@ class Engine:
     def pcm_time(self, enable=None):
         """tbf_debug_pcm_time: enable True / False switches the event pair around every k_pcm
         launch on / off; None returns (milliseconds, launches) since the last query."""
-        f = self._lib.tbf_debug_pcm_time
-        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_uint64)]
-        if enable is not None:
-            _check(f(self._h, 1 if enable else -1, None, None))
-            return None
-        ms, n = C.c_double(), C.c_uint64()
-        _check(f(self._h, 0, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
+        return _stage_time(self._lib.tbf_debug_pcm_time, self._h, enable)
 
     @staticmethod
     def _pcm_out(out_ptr, out_stride_bytes, fmt, flags, seed, frame0, row_frame0, meters_ptr):
@@ -1165,14 +1139,7 @@ class Engine:
     def mix_time(self, enable=None):
         """tbf_debug_mix_time: enable True / False switches the event pair around every k_mix
         launch on / off; None returns (milliseconds, launches) since the last query."""
-        f = self._lib.tbf_debug_mix_time
-        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_uint64)]
-        if enable is not None:
-            _check(f(self._h, 1 if enable else -1, None, None))
-            return None
-        ms, n = C.c_double(), C.c_uint64()
-        _check(f(self._h, 0, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
+        return _stage_time(self._lib.tbf_debug_mix_time, self._h, enable)
 
     def mix_device(self, n_rows, L_ptr, R_ptr, in_stride, frames, rows, n_buses, outL_ptr, outR_ptr, out_stride, counts=None,
                    stream=None):
