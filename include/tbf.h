@@ -1001,6 +1001,124 @@ int tbf_debug_true_peak_grid (uint32_t n_rows, uint32_t frames, uint32_t* tile_f
 /* k_tpeak's own time, as tbf_debug_loudness_time: one launch per call that took frames */
 int tbf_debug_true_peak_time (tbf_true_peak* tp, int32_t enable, double* ms, uint64_t* launches);
 
+/* ---- Bus equaliser: parametric bands on planes, band-pipelined on the device ----
+ * A stage between two pairs of float32 device planes: tone shaping of a bus, between the mixdown and
+ * the limiter: a rumble high-pass, a shelf, a notch or a bell per row.  Like the mixdown, the
+ * limiter and the meters it is specified here, not restated from the reference, which equalises
+ * nothing but the whirl's own filters, and it is defined to the bit.
+ * Parameters per equaliser, fixed at creation: rate_hz, an integer in [8000, 192000]; max_bands in
+ * 1 .. 8 (TBF_EQ_MAX_BANDS); n_rows >= 1.  Derived: P, the smallest of 1, 2, 4, 8 that is >=
+ * max_bands, the lanes k_eq gives a row and channel; no P changes a bit.
+ * Bands: a row has nb <= max_bands bands {type, hz, q, gain_db}, none at creation.  The types are
+ * the reference designer's (src/eqcomp.cpp): 0 LPF, 1 HPF, 2 BPF0 (peak gain Q), 3 BPF1 (0 dB peak),
+ * 4 notch, 5 APF, 6 PEQ, 7 low shelf, 8 high shelf.  Accepted: 0.1 < q < 6 and 0.0002 < hz / rate_hz <
+ * 0.4998, which is the guard of the reference's setIIRFilter, and |gain_db| <= 24.  Anything else,
+ * a NaN included, is refused with -22 and a tbf_last_error that names the row and the band; nothing
+ * is silently kept.
+ * Coefficients: five doubles {b0, b1, b2, a1, a2} per band, computed on the host in double with
+ * libm by the RBJ designer that the whirl's filters use (eqCompute, csrc/tbf_eq.h) and normalised by
+ * a0 as it does; the kernel receives them and never derives them.  With A = pow (10, gain_db / 40),
+ * w = 2*pi*hz / rate_hz, alpha = sin (w) / (2*q), beta = sqrt (A) / q, each of b0, b1, b2, a1, a2 is
+ * the listed value divided by a0:
+ *     LPF    b (1-cos w)/2, 1-cos w, (1-cos w)/2              a 1+alpha, -2 cos w, 1-alpha
+ *     HPF    b (1+cos w)/2, -(1+cos w), (1+cos w)/2           a as LPF
+ *     BPF0   b sin w/2, 0, -sin w/2                           a as LPF
+ *     BPF1   b alpha, 0, -alpha                               a as LPF
+ *     notch  b 1, -2 cos w, 1                                 a as LPF
+ *     APF    b 1-alpha, -2 cos w, 1+alpha                     a as LPF
+ *     PEQ    b 1+alpha*A, -2 cos w, 1-alpha*A                 a 1+alpha/A, -2 cos w, 1-alpha/A
+ *     low    b A((A+1)-(A-1)cos w+beta sin w), 2A((A-1)-(A+1)cos w), A((A+1)-(A-1)cos w-beta sin w)
+ *            a (A+1)+(A-1)cos w+beta sin w, -2((A-1)+(A+1)cos w), (A+1)+(A-1)cos w-beta sin w
+ *     high   b A((A+1)+(A-1)cos w+beta sin w), -2A((A-1)+(A+1)cos w), A((A+1)+(A-1)cos w-beta sin w)
+ *            a (A+1)-(A-1)cos w+beta sin w, 2((A-1)-(A+1)cos w), (A+1)-(A-1)cos w-beta sin w
+ * Per row, per channel, per frame, v = (double) sample, then for each band b = 0 .. nb - 1 in order,
+ * in transposed direct form II, every *, + and - one IEEE double operation, with no contraction, no
+ * fma and no flushing:
+ *     y = b0*v + s1;   s1 = (b1*v + s2) - a1*y;   s2 = b2*v - a2*y;   v = y
+ * and the output is (float) v, one round-to-nearest.  A row with nb = 0 passes through: every
+ * non-NaN input comes out as its own bits, and a NaN stays a NaN.  NaN and Inf are literal: a
+ * poisoned row stays poisoned until it is reset, and it touches no other row.  Which NaN comes out
+ * (its sign and payload) is not part of the definition: hosts and the device differ there.
+ * State: two doubles per row, channel and band (32 B x max_bands per row), zero at creation and at
+ * reset.  It belongs to the equaliser object, not to an instance: tbf_instances_* do not know it,
+ * tbf_debug_device_bytes does not count it, and it is not saved.
+ * The order is part of the definition.  A band's frames form one serial chain, and band b of frame
+ * n needs only band b - 1 of frame n and its own state of frame n - 1: the kernel runs a row and
+ * channel's bands as a pipeline over adjacent lanes, one frame apart, and drains it before a call
+ * ends.  It parallelises over rows, channels and bands, never over a row's time, and keeps no
+ * transition matrices.  So a row's output has the same bits however its frames are cut into calls,
+ * whatever P is, and whatever rows stand beside it.
+ * Left out: parameter ramps (tbf_eq_set switches a row's coefficients between two calls, as the
+ * reference's setIIRFilter does between two blocks), saving an equaliser's state, linear-phase
+ * filters, and band lists per channel. */
+#define TBF_EQ_MAX_BANDS 8u
+#define TBF_EQ_LPF 0
+#define TBF_EQ_HPF 1
+#define TBF_EQ_BPF0 2
+#define TBF_EQ_BPF1 3
+#define TBF_EQ_NOTCH 4
+#define TBF_EQ_APF 5
+#define TBF_EQ_PEQ 6
+#define TBF_EQ_LOW 7
+#define TBF_EQ_HIGH 8
+typedef struct tbf_eq tbf_eq;
+typedef struct tbf_eq_config {
+	uint32_t rate_hz, max_bands;
+} tbf_eq_config;
+typedef struct tbf_eq_band {
+	int32_t type, reserved; /* TBF_EQ_*; reserved is ignored */
+	double  hz, q, gain_db; /* gain_db matters to PEQ and the shelves only, and is checked for all */
+} tbf_eq_band;
+/* An equaliser of n_rows rows, none with a band, on e's device; e owns it: tbf_engine_destroy
+ * releases the ones still alive.  -22: a NULL pointer, a rate_hz or max_bands out of range,
+ * n_rows == 0.  A host-only engine validates, then returns -19.  -12 when the device cannot hold
+ * the state. */
+int tbf_eq_create (tbf_engine* e, uint32_t n_rows, const tbf_eq_config* cfg, tbf_eq** out);
+int tbf_eq_destroy (tbf_eq* eq);
+/* The state of the rows `rows` (host memory, n of them; NULL: all rows, n ignored) is zero again,
+ * ordered on `stream` (NULL: the engine's own); their bands stay.  -22: a row index >= n_rows. */
+int tbf_eq_reset (tbf_eq* eq, uint32_t n, const uint32_t* rows, void* stream);
+/* New band lists for the rows `rows` (n of them; NULL: all rows in order, n ignored): row k of the
+ * list takes n_bands[k] <= max_bands bands, which stand packed in `bands`, row k's behind those of
+ * the rows before it (bands may be NULL when every n_bands[k] is 0).  Ordered on `stream` (NULL: the
+ * engine's own) as tbf_eq_reset is: it takes effect from the next tbf_eq_device on, and the state is
+ * kept, as the reference's setIIRFilter keeps its filter's z.  The upload is staged in the
+ * equaliser's own tables, and the call waits for `stream` before it returns, so the staging outlives
+ * the copy and the caller's arrays are free at once.  Every band of every row is checked before
+ * anything changes: -22 (see above) leaves every row as it was. */
+int tbf_eq_set (tbf_eq* eq, uint32_t n, const uint32_t* rows, const tbf_eq_band* bands, const uint32_t* n_bands, void* stream);
+/* The read-back: a row's bands in use into nb and their coefficients, five doubles {b0, b1, b2, a1,
+ * a2} per band, into coeffs (room for `cap` bands).  From the host's tables: no wait.  -28 when cap
+ * is too small, with nb set and nothing else written. */
+int tbf_eq_bands (const tbf_eq* eq, uint32_t row, double* coeffs, uint32_t cap, uint32_t* nb);
+/* One call: the equaliser's n_rows rows of d_L / d_R (device memory, row r at r * in_stride floats;
+ * any 4-byte-aligned pointers and odd strides; d_L == d_R allowed: mono in, two equal planes out)
+ * into d_outL / d_outR (row r at r * out_stride floats) on `stream` (NULL: the engine's own),
+ * ordered as tbf_render_device.  Row r takes counts[r] <= frames frames (counts: host memory,
+ * uploaded before the call returns, for which the call waits for `stream`; NULL: `frames` each, and
+ * no wait); a row with count 0 keeps its state.  Output rows are written in [0, count) and left
+ * alone behind it; the inputs are only read.  Calls on one equaliser are the caller's to order.
+ * -22, with a tbf_last_error that names the argument: a NULL pointer, in_stride or out_stride <
+ * frames, a misaligned pointer, counts[r] > frames, an output that overlaps an input or the other
+ * output.  Validation comes first: a refused call moves no state. */
+int tbf_eq_device (tbf_eq* eq, const float* d_L, const float* d_R, uint64_t in_stride, uint32_t frames, float* d_outL, float* d_outR,
+                   uint64_t out_stride, const uint32_t* counts, void* stream);
+/* test hook: the five coefficients of one band at a rate.  Needs no engine.  -22 as tbf_eq_set
+ * (the error names row 0 band 0). */
+int tbf_debug_eq_coeffs (uint32_t rate_hz, const tbf_eq_band* band, double* c5);
+/* test hook: the host restatement of the definition on one row, from the header the kernel is
+ * built from (csrc/tbf_eq.h): n frames of L / R (L == R allowed) through nb <= 8 bands with the
+ * coefficients coeffs[nb][5], behind `state` = L's {s1, s2} per band followed by R's (4 nb doubles,
+ * read and then replaced), into outL / outR.  Needs no engine and no device. */
+int tbf_debug_eq_ref (const double* coeffs, uint32_t nb, const float* L, const float* R, uint64_t n, double* state, float* outL,
+                      float* outR);
+/* test hook: how k_eq lays an equaliser of max_bands out: P, the rows of a wave (32 / P), the frames
+ * of a row staged in LDS at a time, and the workgroup's LDS bytes.  No layout changes a bit.  Any
+ * out pointer may be NULL.  -22: max_bands out of range. */
+int tbf_debug_eq_grid (uint32_t max_bands, uint32_t* lanes, uint32_t* rows_per_wave, uint32_t* tile_frames, uint32_t* lds_bytes);
+/* k_eq's own time, as tbf_debug_loudness_time: one launch per call that took frames */
+int tbf_debug_eq_time (tbf_eq* eq, int32_t enable, double* ms, uint64_t* launches);
+
 int tbf_synchronize (tbf_engine* e);
 /* Which exact-but-slow paths the kernels took since the engine's first render (cumulative,
  * informational; the results are bit-identical either way).  Waits for the engine's

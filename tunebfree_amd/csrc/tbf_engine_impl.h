@@ -25,6 +25,7 @@
 
 #include "../../include/tbf.h"
 #include "tbf_cabinet.h"
+#include "tbf_eq.h"
 #include "tbf_host.h"
 #include "tbf_limit.h"
 #include "tbf_loud.h"
@@ -336,6 +337,23 @@ struct tbf_true_peak {
 	StageTimer                 timer; /* tbf_debug_true_peak_time: an event pair around every launch */
 };
 
+/* A bus equaliser (tbf_eq_create, csrc/tbf_eq.cpp): per row the bands in use and their
+ * coefficients, on the host (what tbf_eq_set last gave, and tbf_eq_bands reads back) and on the
+ * device, and per row, channel and band the two state doubles (k_eq, csrc/tbf_eq.hip). */
+struct tbf_eq {
+	tbf_engine*           eng = nullptr;
+	tbf_eq_config         cfg = {0u, 0u};
+	uint32_t              nRows = 0;
+	DevBuf<double>        state;   /* [row][channel][max_bands][2] */
+	DevBuf<double>        dcoef;   /* [row][max_bands][5] */
+	DevBuf<uint32_t>      dnb;     /* [row] */
+	DevBuf<uint32_t>      dcounts; /* the call's counts on the device */
+	std::vector<double>   coef;    /* dcoef's host copy */
+	std::vector<uint32_t> nb;      /* dnb's host copy */
+	std::vector<uint32_t> counts;  /* the call's counts */
+	StageTimer            timer;   /* tbf_debug_eq_time: an event pair around every launch */
+};
+
 struct tbf_engine {
 	tbf_engine_config                       cfg;
 	Config                                  conf; /* cfg keys (tbf_config_set) for tables built from now on */
@@ -579,6 +597,8 @@ struct tbf_engine {
 	std::vector<std::unique_ptr<tbf_loudness>> loudness;
 	/* the true-peak meters still alive (csrc/tbf_tpeak.cpp), likewise, and behind the loudness meters */
 	std::vector<std::unique_ptr<tbf_true_peak>> truePeaks;
+	/* the bus equalisers still alive (csrc/tbf_eq.cpp), likewise, and behind the true-peak meters */
+	std::vector<std::unique_ptr<tbf_eq>> eqs;
 };
 
 namespace tbf {

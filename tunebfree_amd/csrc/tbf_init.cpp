@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <limits>
 
+#include "tbf_eq.h"
 #include "tbf_host.h"
 #include "tbf_rand.h"
 
@@ -583,43 +584,8 @@ static const double kIr[5][26][2] = {
 };
 static const int kIrN[5] = {26, 24, 23, 24, 24};
 
-/* RBJ designer, src/eqcomp.cpp:98-203 (only the types the whirl uses by default are
- * exercised, all nine are kept for configurability) */
-static void eqCompute (int type, double fqHz, double Q, double dbG, double* C, double SampleRateD)
-{
-	double A = pow (10.0, (dbG / 40.0)), omega = (2.0 * M_PI * fqHz) / SampleRateD;
-	double sin_ = sin (omega), cos_ = cos (omega), alpha = sin_ / (2.0 * Q), beta = sqrt (A) / Q;
-	switch (type) {
-		case 0: C[0] = (1.0 - cos_) / 2.0; C[1] = 1.0 - cos_; C[2] = (1.0 - cos_) / 2.0; C[3] = 1.0 + alpha; C[4] = -2.0 * cos_; C[5] = 1.0 - alpha; break;
-		case 1: C[0] = (1.0 + cos_) / 2.0; C[1] = -(1.0 + cos_); C[2] = (1.0 + cos_) / 2.0; C[3] = 1.0 + alpha; C[4] = -2.0 * cos_; C[5] = 1.0 - alpha; break;
-		case 2: C[0] = sin_ / 2.0; C[1] = 0.0; C[2] = -sin_ / 2.0; C[3] = 1.0 + alpha; C[4] = -2.0 * cos_; C[5] = 1.0 - alpha; break;
-		case 3: C[0] = alpha; C[1] = 0.0; C[2] = -alpha; C[3] = 1.0 + alpha; C[4] = -2.0 * cos_; C[5] = 1.0 - alpha; break;
-		case 4: C[0] = 1.0; C[1] = -2.0 * cos_; C[2] = 1.0; C[3] = 1.0 + alpha; C[4] = -2.0 * cos_; C[5] = 1.0 - alpha; break;
-		case 5: C[0] = 1.0 - alpha; C[1] = -2.0 * cos_; C[2] = 1.0 + alpha; C[3] = 1.0 + alpha; C[4] = -2.0 * cos_; C[5] = 1.0 - alpha; break;
-		case 6: C[0] = 1.0 + (alpha * A); C[1] = -2.0 * cos_; C[2] = 1.0 - (alpha * A); C[3] = 1.0 + (alpha / A); C[4] = -2.0 * cos_; C[5] = 1.0 - (alpha / A); break;
-		case 7:
-			C[0] = A * ((A + 1) - ((A - 1) * cos_) + (beta * sin_));
-			C[1] = (2.0 * A) * ((A - 1) - ((A + 1) * cos_));
-			C[2] = A * ((A + 1) - ((A - 1) * cos_) - (beta * sin_));
-			C[3] = (A + 1) + ((A - 1) * cos_) + (beta * sin_);
-			C[4] = -2.0 * ((A - 1) + ((A + 1) * cos_));
-			C[5] = (A + 1) + ((A - 1) * cos_) - (beta * sin_);
-			break;
-		case 8:
-			C[0] = A * ((A + 1) + ((A - 1) * cos_) + (beta * sin_));
-			C[1] = -(2.0 * A) * ((A - 1) + ((A + 1) * cos_));
-			C[2] = A * ((A + 1) + ((A - 1) * cos_) - (beta * sin_));
-			C[3] = (A + 1) - ((A - 1) * cos_) + (beta * sin_);
-			C[4] = 2.0 * ((A - 1) - ((A + 1) * cos_));
-			C[5] = (A + 1) - ((A - 1) * cos_) - (beta * sin_);
-			break;
-	}
-	C[0] /= C[3];
-	C[1] /= C[3];
-	C[2] /= C[3];
-	C[4] /= C[3];
-	C[5] /= C[3];
-}
+/* the RBJ designer eqCompute (src/eqcomp.cpp:98-203) is csrc/tbf_eq.h's, which the bus equaliser
+ * calls too; only the types the whirl uses by default are exercised here */
 
 /* setIIRFilter (src/whirl.cpp:147-172) -> {a1, a2, b0, b1, b2}: out-of-range settings
  * leave the coefficients as they were */

@@ -108,6 +108,11 @@ class LoudnessResult(C.Structure):
                 ("hops", C.c_uint32), ("blocks", C.c_uint32), ("gated", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class EqConfig(C.Structure):
+    """tbf_eq_config: the rate (in [8000, 192000]) and the most bands of a row (1 .. 8)"""
+    _fields_ = [("rate_hz", C.c_uint32), ("max_bands", C.c_uint32)]
+
+
 class TruePeakConfig(C.Structure):
     """tbf_true_peak_config: the oversampling factor (1, 2 or 4)"""
     _fields_ = [("oversample", C.c_uint32), ("reserved", C.c_uint32)]
@@ -222,10 +227,17 @@ SIGNATURES = {
     "tbf_true_peak_reset": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tbf_true_peak_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tbf_true_peak_read": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tbf_eq_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(EqConfig), C.POINTER(C.c_void_p)]),
+    "tbf_eq_destroy": (C.c_int, [C.c_void_p]),
+    "tbf_eq_reset": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tbf_eq_set": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tbf_eq_bands": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, _u32p]),
+    "tbf_eq_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                C.c_void_p, C.c_void_p]),
 }
 # the stages' timing hooks (_stage_time), which share one signature; debug calls stay out of SIGNATURES
 STAGE_TIME = {f"tbf_debug_{stage}_time": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_uint64)])
-              for stage in ("cabinet", "resample", "pcm", "mix", "limit", "loudness", "true_peak")}
+              for stage in ("cabinet", "resample", "pcm", "mix", "limit", "loudness", "true_peak", "eq")}
 
 # tbf_engine_config.chain_mode of the effects-only chains (include/tbf.h TBF_CHAIN_FX*)
 CHAIN_FX, CHAIN_FX_TAP_PREAMP, CHAIN_FX_TAP_REVERB = 4, 5, 6
@@ -409,6 +421,67 @@ class Loudness:
         """tbf_loudness_destroy (the engine does it for the meters still alive when it closes)"""
         if self._h and getattr(self._eng, "_h", None):
             _check(self._lib.tbf_loudness_destroy(self._h))
+        self._h = None
+
+
+def _eq_band_lists(bands, n):
+    """Equalizer.set's bands for n rows as (packed EQ_BAND_DTYPE records, uint32 counts): one list of
+    records for all the rows, or one list per row"""
+    from .params import EQ_BAND_DTYPE
+    bands = list(bands)
+    rowwise = bool(bands) and all(isinstance(r, (list, tuple)) or (isinstance(r, np.ndarray) and r.ndim == 1) for r in bands)
+    per_row = [list(r) for r in bands] if rowwise else [bands] * n
+    if len(per_row) != n:
+        raise ValueError(f"{len(per_row)} band lists for {n} rows")
+    flat = np.array([b for r in per_row for b in r], dtype=EQ_BAND_DTYPE).reshape(-1)
+    return flat, np.array([len(r) for r in per_row], dtype=np.uint32)
+
+
+class Equalizer:
+    """A bus equaliser (Engine.equalizer): n_rows rows, each with its own list of up to max_bands
+    biquad bands (params.eq_band), between two pairs of device planes; its state belongs to it, not
+    to the engine's instances."""
+
+    def __init__(self, eng, handle, n_rows, cfg):
+        self._eng, self._lib, self._h = eng, eng._lib, handle
+        self.n_rows, self.rate_hz, self.max_bands = n_rows, cfg.rate_hz, cfg.max_bands
+
+    def set(self, bands, rows=None, stream=None):
+        """tbf_eq_set: new bands for the rows (None: all): `bands` is one list of params.eq_band
+        records for all of them, or one list per row; from the next process_device on, state kept"""
+        n, rp, _r = _rows_arg(rows)
+        flat, nb = _eq_band_lists(bands, self.n_rows if rows is None else n)
+        _check(self._lib.tbf_eq_set(self._h, n, rp, flat.ctypes.data if len(flat) else None, nb.ctypes.data, _ptr(stream)))
+
+    def bands(self, row):
+        """tbf_eq_bands: the coefficients of the row's bands in use, [nb, 5] float64 (b0, b1, b2, a1, a2)"""
+        n = C.c_uint32()
+        c = np.zeros((self.max_bands, 5), np.float64)
+        _check(self._lib.tbf_eq_bands(self._h, int(row), c.ctypes.data, self.max_bands, C.byref(n)))
+        return c[:n.value].copy()
+
+    def process_device(self, L_ptr, R_ptr, in_stride, frames, outL_ptr, outR_ptr, out_stride, counts=None, stream=None):
+        """tbf_eq_device: the equaliser's rows of the device planes L_ptr / R_ptr (row r at
+        r * in_stride floats; L_ptr == R_ptr: mono), `frames` frames per row or counts[r] (host
+        array) of them, into outL_ptr / outR_ptr, out_stride floats apart."""
+        cp, _c = _counts_arg(counts, self.n_rows)
+        _check(self._lib.tbf_eq_device(self._h, _ptr(L_ptr), _ptr(R_ptr), int(in_stride), int(frames), _ptr(outL_ptr),
+                                       _ptr(outR_ptr), int(out_stride), cp, _ptr(stream)))
+
+    def reset(self, rows=None, stream=None):
+        """tbf_eq_reset: the state of the rows (None: all) is zero again, ordered on the stream"""
+        n, rp, _r = _rows_arg(rows)
+        _check(self._lib.tbf_eq_reset(self._h, n, rp, _ptr(stream)))
+
+    def timing(self, enable=None):
+        """tbf_debug_eq_time: enable True / False switches the event pair around every call's
+        launch on / off; None returns (milliseconds, launch sets) since the last query."""
+        return _stage_time(self._lib.tbf_debug_eq_time, self._h, enable)
+
+    def close(self):
+        """tbf_eq_destroy (the engine does it for the equalisers still alive when it closes)"""
+        if self._h and getattr(self._eng, "_h", None):
+            _check(self._lib.tbf_eq_destroy(self._h))
         self._h = None
 
 
@@ -1319,6 +1392,58 @@ class Engine:
         lra, win = C.c_double(), C.c_uint32()
         _check(f(int(rate_hz), e.ctypes.data if len(e) else None, len(e), C.byref(lra), C.byref(win)))
         return lra.value, win.value
+
+    def equalizer(self, n_rows, max_bands=8, rate_hz=None):
+        """tbf_eq_create: a bus equaliser of n_rows rows of up to max_bands (1 .. 8) bands each on this
+        engine's device, designed at rate_hz (None: the engine's rate); no row has a band until
+        Equalizer.set; the engine releases it when it closes"""
+        cfg = EqConfig(int(round(self.sample_rate)) if rate_hz is None else int(rate_hz), int(max_bands))
+        h = C.c_void_p()
+        _check(self._lib.tbf_eq_create(self._h, int(n_rows), C.byref(cfg), C.byref(h)))
+        return Equalizer(self, h, int(n_rows), cfg)
+
+    @staticmethod
+    def eq_coeffs(band, rate_hz):
+        """tbf_debug_eq_coeffs: b0, b1, b2, a1, a2 of one params.eq_band record at a rate"""
+        from .params import EQ_BAND_DTYPE
+        f = load_library().tbf_debug_eq_coeffs
+        f.restype, f.argtypes = C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p]
+        b = np.array(band, dtype=EQ_BAND_DTYPE).reshape(1)
+        c = np.zeros(5, np.float64)
+        _check(f(int(rate_hz), b.ctypes.data, c.ctypes.data))
+        return c
+
+    @staticmethod
+    def eq_ref(L, R, coeffs, state=None):
+        """tbf_debug_eq_ref: the host restatement of the equaliser on one row (no device needed):
+        L, R [n] float32 (the same array twice: mono) through the bands coeffs [nb, 5], state None
+        (a new row) or the [2, nb, 2] doubles an earlier call returned; returns (outL, outR, state)."""
+        f = load_library().tbf_debug_eq_ref
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        mono = L is R
+        L = np.ascontiguousarray(L, dtype=np.float32)
+        R = L if mono else np.ascontiguousarray(R, dtype=np.float32)
+        if L.ndim != 1 or L.shape != R.shape:
+            raise ValueError(f"rows of shape {L.shape} and {R.shape}: want two of [n]")
+        c = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1, 5)
+        st = np.zeros((2, len(c), 2), np.float64) if state is None else np.array(state, np.float64)
+        if st.shape != (2, len(c), 2):
+            raise ValueError(f"state of shape {st.shape}: want [2, {len(c)}, 2]")
+        oL, oR = np.full(len(L), np.nan, np.float32), np.full(len(L), np.nan, np.float32)
+        _check(f(c.ctypes.data if len(c) else None, len(c), L.ctypes.data, R.ctypes.data, len(L),
+                 st.ctypes.data if len(c) else None, oL.ctypes.data, oR.ctypes.data))
+        return oL, oR, st
+
+    @staticmethod
+    def eq_grid(max_bands):
+        """tbf_debug_eq_grid: (P lanes per row and channel, rows per wave, frames per LDS tile, LDS
+        bytes per workgroup) of k_eq for an equaliser of max_bands"""
+        f = load_library().tbf_debug_eq_grid
+        f.restype, f.argtypes = C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, _u32p]
+        p, r, t, b = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(f(int(max_bands), C.byref(p), C.byref(r), C.byref(t), C.byref(b)))
+        return p.value, r.value, t.value, b.value
 
     def true_peak(self, n_rows, rate_hz=None, oversample=None):
         """tbf_true_peak_create: a true-peak meter of n_rows rows on this engine's device, at the

@@ -47,6 +47,21 @@ LOUDNESS_RESULT_DTYPE = np.dtype([("integrated", "<f8"), ("momentary_max", "<f8"
 TRUE_PEAK_RESULT_DTYPE = np.dtype([("sample_peak", "<f4", (2,)), ("inter_peak", "<f4", (2,)), ("frames", "<u8"),
                                    ("dbtp", "<f8")])
 
+# the bus equaliser (Engine.equalizer): the band types (TBF_EQ_*, the RBJ designer's nine), the most
+# bands of a row (TBF_EQ_MAX_BANDS), and tbf_eq_band as a numpy record (32 B, as the C struct)
+EQ_LPF, EQ_HPF, EQ_BPF0, EQ_BPF1, EQ_NOTCH, EQ_APF, EQ_PEQ, EQ_LOW, EQ_HIGH = range(9)
+EQ_MAX_BANDS = 8
+EQ_BAND_DTYPE = np.dtype([("type", "<i4"), ("reserved", "<i4"), ("hz", "<f8"), ("q", "<f8"), ("gain_db", "<f8")])
+
+
+def eq_band(kind, hz, q=0.7071, gain_db=0.0):
+    """one tbf_eq_band record for Equalizer.set / Engine.eq_coeffs: kind one of EQ_LPF .. EQ_HIGH,
+    the frequency in Hz, the Q, and the gain in dB (PEQ and the shelves).  Nothing is checked here:
+    the library refuses what lies outside its ranges."""
+    b = np.zeros((), EQ_BAND_DTYPE)
+    b["type"], b["hz"], b["q"], b["gain_db"] = int(kind), float(hz), float(q), float(gain_db)
+    return b
+
 
 def mix_rows(bus, gain=1.0, pan=0.0):
     """tbf_mix_row records for Engine.mix_device / .render_mix / .process_mix: row r goes to bus
