@@ -1119,6 +1119,133 @@ int tbf_debug_eq_grid (uint32_t max_bands, uint32_t* lanes, uint32_t* rows_per_w
 /* k_eq's own time, as tbf_debug_loudness_time: one launch per call that took frames */
 int tbf_debug_eq_time (tbf_eq* eq, int32_t enable, double* ms, uint64_t* launches);
 
+/* ---- Bus compressor: recursive attack and release on planes, on the device ----
+ * A stage between two pairs of float32 device planes: the dynamics of a bus, between the equaliser
+ * and the limiter: threshold, ratio and knee as a gain curve, attack, release and make-up per row,
+ * and an optional key pair for ducking.  Like the mixdown, the equaliser, the limiter and the meters
+ * it is specified here, not restated from the reference, which has no dynamics processor (DESIGN.md
+ * section 7), and it is defined to the bit.
+ * Per compressor, fixed at creation: n_rows >= 1 rows and n_curves gain curves, 1 ..
+ * TBF_COMP_MAX_CURVES = 8.  Per row four parameters: curve (default 0), attack, a float32
+ * coefficient a (default 0), release, a float32 coefficient r (default 0), and makeup, a float32 m
+ * (default 1); and one state float g, 1.0f at creation and at reset.
+ * Curve: a curve is data, TBF_COMP_POINTS = 769 float32 gains pt[0 .. 768] on a grid of
+ * TBF_COMP_SEG = 32 segments per octave over the 24 octaves from 2^-16 to 2^8: point i is the gain
+ * at the level 2^(-16 + i/32) * (1 + (i%32)/32) (i/32 the integer quotient).  Every curve is all
+ * 1.0f at creation.  The kernel never derives a curve.  With u the bit pattern of the level p, a
+ * float32 >= 0 and never NaN:
+ *     i  = (u >> 18) - (111 << 5)
+ *     fr = (float) (u & 0x3FFFF) * 2^-18                     exact
+ *     t  = fmaf (fr, pt[i+1] - pt[i], pt[i])                 for 0 <= i < 768: one float32
+ *                                                            subtraction and one fmaf
+ *     t  = pt[0] for p < 2^-16, and t = pt[768] for p >= 2^8, +Inf included.
+ * A grid level returns its own point; hard knees are smoothed over one segment.
+ * Per frame n of a row, in this order, every operation one float32 operation, denormals kept:
+ *     p[n] = limit_peak (kL[n], kR[n])      the limiter's: the larger magnitude, NaN skipped, so p
+ *                                           is never NaN; k is the key pair when the call gives
+ *                                           one, otherwise the input pair
+ *     t[n] = the row's curve at p[n], as above
+ *     d    = g[n-1] - t[n];   g[n] = fmaf (d > 0 ? a : r, d, t[n])
+ *                                           the attack coefficient applies while the gain must fall
+ *     y[n] = (g[n] * m) * x[n]              for each channel: two multiplies in that order; NaN and
+ *                                           Inf in x are literal
+ * The latency is 0 frames.  Consequences: a row on a flat curve with m = 1 comes out as its own
+ * bits (g stays exactly 1.0f, and a NaN stays a NaN); g is always finite and in [0, 1], because the
+ * points are, so a NaN in the audio cannot poison the state; and, the recurrence being the only
+ * thing that crosses a frame, a row has the same bits however its frames are cut into calls,
+ * whatever layout the kernel chose, and whatever rows stand beside it.  Which NaN comes out (its
+ * sign and payload) is not part of the definition.
+ * Accepted: every point finite and in [0, 1] (-0.0f is not: a gain's bits order as its value); a
+ * and r in [0, 1); m finite and in [0,
+ * TBF_COMP_MAX_MAKEUP = 256]; curve < n_curves.  Anything else, a NaN included, is refused with -22
+ * and a tbf_last_error that names the row or the point; nothing has changed when a call is refused.
+ * Designer (host, double, libm): tbf_comp_curve_design (threshold_db T, ratio R, knee_db W) fills the
+ * 769 points: with x = 20 log10 (level),
+ *     2 (x - T) < -W:    y = x
+ *     2 |x - T| <= W:    y = x + (1/R - 1) (x - T + W/2)^2 / (2 W)
+ *     otherwise:         y = T + (x - T) / R
+ * and gain = min (1, 10^((y - x) / 20)), rounded once to float.  Accepted: -90 <= T <= 0, 1 <= R <=
+ * +Inf (1/R = 0: a limiter curve), 0 <= W <= 40.  The designer is held to a tolerance, not to bits.
+ * Gates, expanders and any other shape are the caller's own 769 points.
+ * State: one float per row.  It belongs to the compressor object, not to an instance:
+ * tbf_instances_* do not know it, tbf_debug_device_bytes does not count it, and it is not saved.
+ * Left out: look-ahead (the limiter has it), RMS or K-weighted detection, per-channel (unlinked)
+ * gain, parameter ramps, saving a compressor's state, and upward gain from the curve (points above
+ * 1). */
+#define TBF_COMP_MAX_CURVES 8u
+#define TBF_COMP_SEG 32u
+#define TBF_COMP_POINTS 769u
+#define TBF_COMP_MAX_MAKEUP 256.0f
+typedef struct tbf_comp tbf_comp;
+typedef struct tbf_comp_config {
+	uint32_t n_curves;
+} tbf_comp_config;
+typedef struct tbf_comp_row {
+	uint32_t curve;
+	float    attack, release, makeup;
+} tbf_comp_row;
+typedef struct tbf_comp_meter {
+	float    min_gain; /* the smallest g[n] of the call's frames of the row; 1.0f when it took none */
+	uint32_t frames;   /* the row's frames of the call */
+} tbf_comp_meter;
+/* A compressor of n_rows rows, every curve flat and every row at its defaults, on e's device; e owns
+ * it: tbf_engine_destroy releases the ones still alive.  -22: a NULL pointer, n_curves out of range,
+ * n_rows == 0.  A host-only engine validates, then returns -19.  -12 when the device cannot hold
+ * the tables. */
+int tbf_comp_create (tbf_engine* e, uint32_t n_rows, const tbf_comp_config* cfg, tbf_comp** out);
+int tbf_comp_destroy (tbf_comp* comp);
+/* The g of the rows `rows` (host memory, n of them; NULL: all rows, n ignored) is 1.0f again,
+ * ordered on `stream` (NULL: the engine's own); their parameters stay.  -22: a row index >= n_rows. */
+int tbf_comp_reset (tbf_comp* comp, uint32_t n, const uint32_t* rows, void* stream);
+/* New points pts[0 .. 768] for curve `curve`.  Ordered on `stream` (NULL: the engine's own) as
+ * tbf_comp_reset is: it takes effect from the next tbf_comp_device on, and every g is kept.  The
+ * upload is staged in the compressor's own tables, and the call waits for `stream` before it returns,
+ * so the staging outlives the copy and the caller's array is free at once.  Every point is checked
+ * before anything changes: -22 (see above) leaves the curve as it was. */
+int tbf_comp_curve_set (tbf_comp* comp, uint32_t curve, const float* pts, void* stream);
+/* New parameters for the rows `rows` (n of them; NULL: all rows in order, n ignored): row k of the
+ * list takes params[k].  Ordered, staged and waited for as tbf_comp_curve_set; every g is kept.
+ * Every row is checked before anything changes: -22 leaves every row as it was. */
+int tbf_comp_rows_set (tbf_comp* comp, uint32_t n, const uint32_t* rows, const tbf_comp_row* params, void* stream);
+/* The read-back, from the host's tables: no wait. */
+int tbf_comp_curve_get (const tbf_comp* comp, uint32_t curve, float* pts);
+int tbf_comp_row_get (const tbf_comp* comp, uint32_t row, tbf_comp_row* out);
+/* One call: the compressor's n_rows rows of d_L / d_R (device memory, row r at r * in_stride floats;
+ * any 4-byte-aligned pointers and odd strides; d_L == d_R allowed) into d_outL / d_outR (row r at
+ * r * out_stride floats) on `stream` (NULL: the engine's own), ordered as tbf_render_device.  The key
+ * pair d_keyL / d_keyR (row r at r * key_stride floats; d_keyL == d_keyR allowed) is optional: both
+ * NULL, and the input is its own key, or both set.  Row r takes counts[r] <= frames frames (counts:
+ * host memory, uploaded before the call returns, for which the call waits for `stream`; NULL:
+ * `frames` each, and no wait); a row with count 0 keeps its g.  Output rows are written in [0, count)
+ * and left alone behind it; the inputs and the key are only read.  d_meters (device memory, or NULL:
+ * nothing is written) takes one tbf_comp_meter for every row.  Calls on one compressor are the
+ * caller's to order.  -22, with a tbf_last_error that names the argument: a NULL pointer, one key
+ * pointer without the other, a stride < frames, a misaligned pointer, counts[r] > frames, an output
+ * that overlaps an input, a key or the other output.  Validation comes first: a refused call moves no
+ * state. */
+int tbf_comp_device (tbf_comp* comp, const float* d_L, const float* d_R, uint64_t in_stride, uint32_t frames, const float* d_keyL,
+                     const float* d_keyR, uint64_t key_stride, float* d_outL, float* d_outR, uint64_t out_stride, const uint32_t* counts,
+                     tbf_comp_meter* d_meters, void* stream);
+/* The designer (see above) into pts[0 .. 768].  Needs no engine.  -22: a NULL pts, or a threshold,
+ * ratio or knee outside its range, NaN included; the error names the argument. */
+int tbf_comp_curve_design (double threshold_db, double ratio, double knee_db, float* pts);
+/* test hook: the host restatement of the definition on one row, from the header the kernel is built
+ * from (csrc/tbf_comp.h): n frames of L / R (L == R allowed) keyed by keyL / keyR (both NULL: by
+ * themselves) through the curve pts[769] with the coefficients and the make-up, behind *g (read and
+ * then replaced), into outL / outR, and every g[n] into gains when that is not NULL.  The curve and
+ * the parameters are checked as the setters check them (the error names row 0).  Needs no engine
+ * and no device. */
+int tbf_debug_comp_ref (const float* pts, float attack, float release, float makeup, const float* L, const float* R, const float* keyL,
+                        const float* keyR, uint64_t n, float* g, float* outL, float* outR, float* gains);
+/* test hook: t for n levels (each >= 0 and not NaN, else -22) on the curve pts[769].  No engine. */
+int tbf_debug_comp_lookup (const float* pts, const float* levels, uint64_t n, float* t);
+/* test hook: how k_comp lays a compressor of n_rows rows and n_curves curves out: the rows of a
+ * wave, the frames of a row staged in LDS at a time, and the workgroup's LDS bytes.  No layout
+ * changes a bit.  Any out pointer may be NULL.  -22: n_rows == 0 or n_curves out of range. */
+int tbf_debug_comp_grid (uint32_t n_rows, uint32_t n_curves, uint32_t* rows_per_wave, uint32_t* tile_frames, uint32_t* lds_bytes);
+/* k_comp's own time, as tbf_debug_loudness_time: one launch per call that took frames */
+int tbf_debug_comp_time (tbf_comp* comp, int32_t enable, double* ms, uint64_t* launches);
+
 int tbf_synchronize (tbf_engine* e);
 /* Which exact-but-slow paths the kernels took since the engine's first render (cumulative,
  * informational; the results are bit-identical either way).  Waits for the engine's

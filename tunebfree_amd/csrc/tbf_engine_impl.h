@@ -25,6 +25,7 @@
 
 #include "../../include/tbf.h"
 #include "tbf_cabinet.h"
+#include "tbf_comp.h"
 #include "tbf_eq.h"
 #include "tbf_host.h"
 #include "tbf_limit.h"
@@ -354,6 +355,24 @@ struct tbf_eq {
 	StageTimer            timer;   /* tbf_debug_eq_time: an event pair around every launch */
 };
 
+/* A bus compressor (tbf_comp_create, csrc/tbf_comp.cpp): the curves and every row's parameters, on
+ * the host (what tbf_comp_curve_set and tbf_comp_rows_set last gave, and the getters read back) and
+ * on the device, and per row the gain g (k_comp, csrc/tbf_comp.hip). */
+struct tbf_comp {
+	tbf_engine*               eng = nullptr;
+	tbf_comp_config           cfg = {0u};
+	uint32_t                  nRows = 0;
+	DevBuf<float>             state;   /* [row]: g */
+	DevBuf<float>             dcurves; /* [n_curves][TBF_COMP_POINTS] */
+	DevBuf<tbf_comp_row>      drows;   /* [row] */
+	DevBuf<uint32_t>          dcounts; /* [row]: the call's counts */
+	std::vector<float>        curves;  /* dcurves' host copy */
+	std::vector<tbf_comp_row> rows;    /* drows' host copy */
+	std::vector<float>        ones;    /* nRows times 1.0f: what a reset copies */
+	std::vector<uint32_t>     counts;  /* the call's counts */
+	StageTimer                timer;   /* tbf_debug_comp_time: an event pair around every launch */
+};
+
 struct tbf_engine {
 	tbf_engine_config                       cfg;
 	Config                                  conf; /* cfg keys (tbf_config_set) for tables built from now on */
@@ -599,6 +618,8 @@ struct tbf_engine {
 	std::vector<std::unique_ptr<tbf_true_peak>> truePeaks;
 	/* the bus equalisers still alive (csrc/tbf_eq.cpp), likewise, and behind the true-peak meters */
 	std::vector<std::unique_ptr<tbf_eq>> eqs;
+	/* the bus compressors still alive (csrc/tbf_comp.cpp), likewise, and behind the equalisers */
+	std::vector<std::unique_ptr<tbf_comp>> comps;
 };
 
 namespace tbf {

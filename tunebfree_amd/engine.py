@@ -108,6 +108,11 @@ class LoudnessResult(C.Structure):
                 ("hops", C.c_uint32), ("blocks", C.c_uint32), ("gated", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class CompConfig(C.Structure):
+    """tbf_comp_config: the gain curves of a compressor (1 .. 8)"""
+    _fields_ = [("n_curves", C.c_uint32)]
+
+
 class EqConfig(C.Structure):
     """tbf_eq_config: the rate (in [8000, 192000]) and the most bands of a row (1 .. 8)"""
     _fields_ = [("rate_hz", C.c_uint32), ("max_bands", C.c_uint32)]
@@ -234,10 +239,20 @@ SIGNATURES = {
     "tbf_eq_bands": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, _u32p]),
     "tbf_eq_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                 C.c_void_p, C.c_void_p]),
+    "tbf_comp_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(CompConfig), C.POINTER(C.c_void_p)]),
+    "tbf_comp_destroy": (C.c_int, [C.c_void_p]),
+    "tbf_comp_reset": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tbf_comp_curve_set": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tbf_comp_rows_set": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tbf_comp_curve_get": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "tbf_comp_row_get": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "tbf_comp_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                  C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tbf_comp_curve_design": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_void_p]),
 }
 # the stages' timing hooks (_stage_time), which share one signature; debug calls stay out of SIGNATURES
 STAGE_TIME = {f"tbf_debug_{stage}_time": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_uint64)])
-              for stage in ("cabinet", "resample", "pcm", "mix", "limit", "loudness", "true_peak", "eq")}
+              for stage in ("cabinet", "resample", "pcm", "mix", "limit", "loudness", "true_peak", "eq", "comp")}
 
 # tbf_engine_config.chain_mode of the effects-only chains (include/tbf.h TBF_CHAIN_FX*)
 CHAIN_FX, CHAIN_FX_TAP_PREAMP, CHAIN_FX_TAP_REVERB = 4, 5, 6
@@ -482,6 +497,82 @@ class Equalizer:
         """tbf_eq_destroy (the engine does it for the equalisers still alive when it closes)"""
         if self._h and getattr(self._eng, "_h", None):
             _check(self._lib.tbf_eq_destroy(self._h))
+        self._h = None
+
+
+class Compressor:
+    """A bus compressor (Engine.compressor): n_rows rows, each with a gain curve (one of n_curves,
+    769 points each: params.comp_curve), an attack and a release coefficient and a make-up
+    (params.comp_row), between two pairs of device planes, with an optional key pair; its state, one
+    gain per row, belongs to it, not to the engine's instances."""
+
+    def __init__(self, eng, handle, n_rows, cfg):
+        self._eng, self._lib, self._h = eng, eng._lib, handle
+        self.n_rows, self.n_curves = n_rows, cfg.n_curves
+
+    def set_curve(self, i, pts, stream=None):
+        """tbf_comp_curve_set: the 769 points of curve i; from the next process_device on, every g kept"""
+        from .params import COMP_POINTS
+        p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1)
+        if len(p) != COMP_POINTS:
+            raise ValueError(f"{len(p)} points: want {COMP_POINTS}")
+        _check(self._lib.tbf_comp_curve_set(self._h, int(i), p.ctypes.data, _ptr(stream)))
+
+    def set_rows(self, params, rows=None, stream=None):
+        """tbf_comp_rows_set: new parameters for the rows (None: all): one params.comp_row record for
+        all of them, or one per row; from the next process_device on, every g kept"""
+        from .params import COMP_ROW_DTYPE
+        n, rp, _r = _rows_arg(rows)
+        want = self.n_rows if rows is None else n
+        p = np.atleast_1d(np.asarray(params, dtype=COMP_ROW_DTYPE)).reshape(-1)
+        if len(p) == 1:
+            p = np.repeat(p, want)
+        if len(p) != want:
+            raise ValueError(f"{len(p)} parameter records for {want} rows")
+        p = np.ascontiguousarray(p)
+        _check(self._lib.tbf_comp_rows_set(self._h, n, rp, p.ctypes.data, _ptr(stream)))
+
+    def curve(self, i):
+        """tbf_comp_curve_get: the 769 points of curve i, float32"""
+        from .params import COMP_POINTS
+        p = np.zeros(COMP_POINTS, np.float32)
+        _check(self._lib.tbf_comp_curve_get(self._h, int(i), p.ctypes.data))
+        return p
+
+    def row(self, r):
+        """tbf_comp_row_get: row r's parameters, one params.COMP_ROW_DTYPE record"""
+        from .params import COMP_ROW_DTYPE
+        p = np.zeros(1, COMP_ROW_DTYPE)
+        _check(self._lib.tbf_comp_row_get(self._h, int(r), p.ctypes.data))
+        return p[0]
+
+    def process_device(self, L_ptr, R_ptr, in_stride, frames, outL_ptr, outR_ptr, out_stride, counts=None, key=None,
+                       meters_ptr=None, stream=None):
+        """tbf_comp_device: the compressor's rows of the device planes L_ptr / R_ptr (row r at
+        r * in_stride floats; L_ptr == R_ptr: mono), `frames` frames per row or counts[r] (host
+        array) of them, into outL_ptr / outR_ptr, out_stride floats apart; key (kL_ptr, kR_ptr,
+        stride): the planes the gain follows in place of the input; meters_ptr: device memory for one
+        params.COMP_METER_DTYPE record per row."""
+        cp, _c = _counts_arg(counts, self.n_rows)
+        kl, kr, ks = (None, None, 0) if key is None else key
+        _check(self._lib.tbf_comp_device(self._h, _ptr(L_ptr), _ptr(R_ptr), int(in_stride), int(frames), _ptr(kl), _ptr(kr),
+                                         int(ks), _ptr(outL_ptr), _ptr(outR_ptr), int(out_stride), cp, _ptr(meters_ptr),
+                                         _ptr(stream)))
+
+    def reset(self, rows=None, stream=None):
+        """tbf_comp_reset: the gain of the rows (None: all) is 1 again, ordered on the stream"""
+        n, rp, _r = _rows_arg(rows)
+        _check(self._lib.tbf_comp_reset(self._h, n, rp, _ptr(stream)))
+
+    def timing(self, enable=None):
+        """tbf_debug_comp_time: enable True / False switches the event pair around every call's
+        launch on / off; None returns (milliseconds, launch sets) since the last query."""
+        return _stage_time(self._lib.tbf_debug_comp_time, self._h, enable)
+
+    def close(self):
+        """tbf_comp_destroy (the engine does it for the compressors still alive when it closes)"""
+        if self._h and getattr(self._eng, "_h", None):
+            _check(self._lib.tbf_comp_destroy(self._h))
         self._h = None
 
 
@@ -1444,6 +1535,70 @@ class Engine:
         p, r, t, b = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
         _check(f(int(max_bands), C.byref(p), C.byref(r), C.byref(t), C.byref(b)))
         return p.value, r.value, t.value, b.value
+
+    def compressor(self, n_rows, n_curves=1):
+        """tbf_comp_create: a bus compressor of n_rows rows and n_curves (1 .. 8) gain curves on this
+        engine's device; every curve is flat and every row at its defaults until Compressor.set_curve
+        and .set_rows; the engine releases it when it closes"""
+        cfg = CompConfig(int(n_curves))
+        h = C.c_void_p()
+        _check(self._lib.tbf_comp_create(self._h, int(n_rows), C.byref(cfg), C.byref(h)))
+        return Compressor(self, h, int(n_rows), cfg)
+
+    @staticmethod
+    def comp_ref(L, R, pts, attack=0.0, release=0.0, makeup=1.0, g=1.0, key=None):
+        """tbf_debug_comp_ref: the host restatement of the compressor on one row (no device needed):
+        L, R [n] float32 (the same array twice: mono) through the curve pts [769] with the float32
+        coefficients and make-up, behind the gain g, keyed by key = (kL, kR) or by themselves;
+        returns (outL, outR, g behind the last frame, gains [n])."""
+        f = load_library().tbf_debug_comp_ref
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        mono = L is R
+        L = np.ascontiguousarray(L, dtype=np.float32)
+        R = L if mono else np.ascontiguousarray(R, dtype=np.float32)
+        if L.ndim != 1 or L.shape != R.shape:
+            raise ValueError(f"rows of shape {L.shape} and {R.shape}: want two of [n]")
+        kl = kr = None
+        if key is not None:
+            kl = np.ascontiguousarray(key[0], dtype=np.float32)
+            kr = kl if key[1] is key[0] else np.ascontiguousarray(key[1], dtype=np.float32)
+            if kl.shape != L.shape or kr.shape != L.shape:
+                raise ValueError(f"key rows of shape {kl.shape} and {kr.shape}: want {L.shape}")
+        p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1)
+        if len(p) != 769:
+            raise ValueError(f"{len(p)} points: want 769")
+        gs = np.array([g], np.float32)
+        oL, oR = np.full(len(L), np.nan, np.float32), np.full(len(L), np.nan, np.float32)
+        gains = np.full(len(L), np.nan, np.float32)
+        _check(f(p.ctypes.data, float(np.float32(attack)), float(np.float32(release)), float(np.float32(makeup)), L.ctypes.data,
+                 R.ctypes.data, None if kl is None else kl.ctypes.data, None if kr is None else kr.ctypes.data, len(L),
+                 gs.ctypes.data, oL.ctypes.data, oR.ctypes.data, gains.ctypes.data))
+        return oL, oR, gs[0], gains
+
+    @staticmethod
+    def comp_lookup(pts, levels):
+        """tbf_debug_comp_lookup: the curve pts [769] at the levels (float32, >= 0), float32"""
+        f = load_library().tbf_debug_comp_lookup
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1)
+        if len(p) != 769:
+            raise ValueError(f"{len(p)} points: want 769")
+        lv = np.ascontiguousarray(levels, dtype=np.float32).reshape(-1)
+        t = np.full(len(lv), np.nan, np.float32)
+        _check(f(p.ctypes.data, lv.ctypes.data, len(lv), t.ctypes.data))
+        return t
+
+    @staticmethod
+    def comp_grid(n_rows, n_curves=1):
+        """tbf_debug_comp_grid: (rows per wave, frames per LDS tile, LDS bytes per workgroup) of k_comp
+        for a compressor of n_rows rows and n_curves curves"""
+        f = load_library().tbf_debug_comp_grid
+        f.restype, f.argtypes = C.c_int, [C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p]
+        r, t, b = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(f(int(n_rows), int(n_curves), C.byref(r), C.byref(t), C.byref(b)))
+        return r.value, t.value, b.value
 
     def true_peak(self, n_rows, rate_hz=None, oversample=None):
         """tbf_true_peak_create: a true-peak meter of n_rows rows on this engine's device, at the

@@ -53,6 +53,41 @@ EQ_LPF, EQ_HPF, EQ_BPF0, EQ_BPF1, EQ_NOTCH, EQ_APF, EQ_PEQ, EQ_LOW, EQ_HIGH = ra
 EQ_MAX_BANDS = 8
 EQ_BAND_DTYPE = np.dtype([("type", "<i4"), ("reserved", "<i4"), ("hz", "<f8"), ("q", "<f8"), ("gain_db", "<f8")])
 
+# the bus compressor (Engine.compressor): the most curves (TBF_COMP_MAX_CURVES), the points of a curve
+# (TBF_COMP_POINTS: 32 segments an octave from 2^-16 to 2^8), the largest make-up, and tbf_comp_row and
+# tbf_comp_meter as numpy records (16 B and 8 B, as the C structs)
+COMP_MAX_CURVES, COMP_SEG, COMP_POINTS, COMP_MAX_MAKEUP = 8, 32, 769, 256.0
+COMP_ROW_DTYPE = np.dtype([("curve", "<u4"), ("attack", "<f4"), ("release", "<f4"), ("makeup", "<f4")])
+COMP_METER_DTYPE = np.dtype([("min_gain", "<f4"), ("frames", "<u4")])
+
+
+def comp_levels():
+    """the levels of a compressor curve's 769 points, float64: point i at 2^(-16 + i // 32) (1 + (i % 32) / 32)"""
+    i = np.arange(COMP_POINTS)
+    return np.ldexp(1.0 + (i % COMP_SEG) / COMP_SEG, i // COMP_SEG - 16)
+
+
+def comp_curve(threshold_db, ratio, knee_db=0.0):
+    """tbf_comp_curve_design: the 769 float32 points of a compressor curve with the threshold in dB
+    (-90 .. 0), the ratio (1 .. inf) and the soft knee's width in dB (0 .. 40), for
+    Compressor.set_curve; the library refuses what lies outside."""
+    from .engine import _check, load_library
+    pts = np.zeros(COMP_POINTS, np.float32)
+    _check(load_library().tbf_comp_curve_design(float(threshold_db), float(ratio), float(knee_db), pts.ctypes.data))
+    return pts
+
+
+def comp_row(curve=0, attack_ms=0.0, release_ms=0.0, makeup_db=0.0, rate=48000):
+    """one tbf_comp_row record for Compressor.set_rows: the curve's index, the attack and release
+    times as float32 coefficients exp(-1 / (ms * 1e-3 * rate)) computed in float64 (0 ms: 0), and
+    the make-up 10^(dB / 20) as float32.  Nothing is checked here: the library refuses what lies
+    outside its ranges."""
+    def coef(ms):
+        return 0.0 if ms == 0 else float(np.exp(-1.0 / (float(ms) * 1e-3 * float(rate))))
+    r = np.zeros((), COMP_ROW_DTYPE)
+    r["curve"], r["attack"], r["release"], r["makeup"] = int(curve), coef(attack_ms), coef(release_ms), 10.0 ** (float(makeup_db) / 20.0)
+    return r
+
 
 def eq_band(kind, hz, q=0.7071, gain_db=0.0):
     """one tbf_eq_band record for Equalizer.set / Engine.eq_coeffs: kind one of EQ_LPF .. EQ_HIGH,
