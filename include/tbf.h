@@ -799,6 +799,68 @@ int tbf_debug_limit_grid (const tbf_limiter_config* cfg, uint32_t* frames_per_la
  * one launch set per call that took frames */
 int tbf_debug_limit_time (tbf_limiter* lim, int32_t enable, double* ms, uint64_t* launches);
 
+/* -- Bus limiter, addition: a true-peak detector --
+ * A limiter may be created with a detector that sees the oversampled waveform: oversample F in
+ * {2, 4}, the interpolator and its phases those of the true-peak meter below (tpeak_phase: {0, 1, 2, 3}
+ * for F = 4, {0, 2} for F = 2; a caller picks F from its rate as there: 4 below 96 kHz, 2 below
+ * 192 kHz; at or above 192 kHz the plain limiter is the one to use).  Let E = 6.  For a row, all
+ * frames before its first being +0.0f:
+ *     yc[n][p] = the meter's chain: acc = +0.0f; for j = 0 .. 11 ascending: acc = fmaf (h[p][j], xc[n-j], acc)
+ *                                                                                  c in {L, R}
+ *     p[n]  = 0;  for v in { xL[n-E], xR[n-E], yL[n][p], yR[n][p] for every phase p used }:
+ *                     if (fabsf (v) > p[n]) p[n] = fabsf (v)      (a NaN is skipped; exact in any order)
+ *     t[n], m[n], g[n]   exactly as above: c / p[n] or 1.0f, the minimum over W = A + H, the
+ *                        ascending chain of A adds, * 1/A
+ *     yL[n] = g[n] * xL[n-D-E], clamped to [-c, c] as above; likewise yR       D = A - 1
+ * Why E = 6: the interpolated values of frame n lie between the input frames n-6 and n-5, where the
+ * table's main taps are (j = 6 for phases 0 and 1, j = 5 for phases 2 and 3).  Pairing them with
+ * the sample E = 6 frames back makes p[n] the peak of one stretch of the oversampled waveform, from
+ * sample n-6 up to but not including sample n-5.  The audio is delayed by the same E, so g[n] <=
+ * t[n-D] (up to rounding, as above) still covers the sample it multiplies.
+ * Consequences:
+ *   - The latency is D + E = A + 5 frames (tbf_limiter_latency reports it).
+ *   - The history is Hn_tp = 2 A + H + 9 frames per row and channel: g[n] reaches t[n-Hn] with
+ *     Hn = 2 A + H - 2, and t[f] reaches x[f-11].
+ *   - |y| <= c stays unconditional, through the clamp.
+ *   - A row whose p never exceeds c has g == 1.0f and comes out as its own bits, A + 5 frames late,
+ *     -0.0f and subnormals unchanged.
+ *   - A row whose samples stay under c but whose interpolated values do not is reduced.
+ *   - A NaN sample is skipped, and so is every interpolated value whose window it touches (the
+ *     chain's result is a NaN, which compares false): for those twelve frames p falls back to the
+ *     sample peaks.  An Inf is literal: a sample Inf gives t = 0; in a chain it gives Inf or
+ *     (Inf - Inf) a NaN, which is skipped.
+ *   - An inter-sample peak between x[k] and x[k+1] belongs to p[k+6].  The gain of x[k] covers it
+ *     for any H (g[k+D+E] <= t[k+6]); the gain of x[k+1], g[k+1+D+E], sums m[k+7 .. k+A+6], whose
+ *     windows reach back to t[k+6] only when H >= 1.  So both neighbours of an inter-sample peak
+ *     are turned down by its target only with H >= 1; with H = 0 the later one may already be one
+ *     step of the release up.
+ *   - The true peak of the output is not bounded in general: twelve samples with twelve gains enter
+ *     one interpolated value.  It is bounded where the gain is constant: there y = g x up to one
+ *     rounding a sample, the chains are linear, and the output's interpolated values are g times
+ *     the input's up to the products' and the chains' roundings, within c (1 + 2^-18) for the
+ *     annex's table (sum |h| < 2.03).
+ * The meters are the same three and are exact.  The state is raw input only, in two sides as
+ * above; it belongs to the limiter object and is not saved.  tbf_limit_device, tbf_limiter_reset,
+ * tbf_limiter_destroy and tbf_debug_limit_time serve both kinds. */
+typedef struct tbf_limiter_detect {
+	uint32_t oversample, reserved; /* F in {2, 4}; 0 */
+} tbf_limiter_detect;
+/* As tbf_limiter_create, with the detector above.  -22 in addition: det NULL, an oversample that is
+ * neither 2 nor 4, reserved != 0.  A host-only engine validates, then returns -19.  -12 when the
+ * device cannot hold the state (16 B x Hn_tp per row). */
+int tbf_limiter_create_tp (tbf_engine* e, uint32_t n_rows, const tbf_limiter_config* cfg, const tbf_limiter_detect* det,
+                           tbf_limiter** out);
+/* test hook: the host restatement of the definition with the detector on one row, from the headers
+ * the kernel is built from (limit_target, limit_out and limit_tp_peak of csrc/tbf_limit.h, tpeak_y
+ * of csrc/tbf_tpeak.h): as tbf_debug_limit_ref, the histories Hn_tp floats each, oldest first, read
+ * and then replaced. */
+int tbf_debug_limit_tp_ref (const tbf_limiter_config* cfg, const tbf_limiter_detect* det, const float* L, const float* R, uint64_t n,
+                            float* histL, float* histR, float* outL, float* outR, tbf_limit_meter* meter);
+/* test hook: how k_limit_tp lays a configuration out, as tbf_debug_limit_grid: the history is
+ * Hn_tp and the LDS bytes include the raw samples of one pass */
+int tbf_debug_limit_tp_grid (const tbf_limiter_config* cfg, const tbf_limiter_detect* det, uint32_t* frames_per_lane,
+                             uint32_t* tile_frames, uint32_t* history, uint32_t* lds_bytes);
+
 /* ---- Loudness meter: BS.1770 integrated loudness of planes, on the device ----
  * A stage beside any two float32 device planes: it reads them and writes only its own memory.
  * ITU-R BS.1770-4 integrated loudness with EBU R128 gating, for a stereo pair with both channel
@@ -950,7 +1012,8 @@ int tbf_debug_loudness_range (uint32_t rate_hz, const double* e, uint32_t n_hops
  * State: 200 B per row (two sides of 2 x 11 floats of history, four words of peaks, one record of
  * the call).  It belongs to the meter object, not to an instance: tbf_instances_* do not know it,
  * tbf_debug_device_bytes does not count it, and it is not saved.
- * Left out: detection inside the limiter, a per-hop series, surround weights, saving a meter. */
+ * Left out: a per-hop series, surround weights, saving a meter.  (Detection inside the limiter is
+ * tbf_limiter_create_tp, in the limiter's section.) */
 typedef struct tbf_true_peak tbf_true_peak;
 typedef struct tbf_true_peak_config {
 	uint32_t oversample, reserved;

@@ -292,11 +292,14 @@ using namespace tbf; /* private header: the engine's own translation units only 
 /* A bus limiter (tbf_limiter_create, csrc/tbf_limit.cpp): its rows' state and the staging of a
  * call's counts.  The state is input only: per row two history buffers of 2 x Hn floats (L, R),
  * of which rows[r].side is the live one; a call reads it, writes the other and flips the side of
- * every row that took frames (k_limit, csrc/tbf_limit.hip). */
+ * every row that took frames (k_limit, csrc/tbf_limit.hip).  With a true-peak detector
+ * (tbf_limiter_create_tp: oversample 2 or 4, 0 for the plain kind) Hn is limit_tp_history and the
+ * launch is k_limit_tp's (csrc/tbf_limit_tp.hip). */
 struct tbf_limiter {
 	tbf_engine*                eng = nullptr;
 	tbf_limiter_config         cfg = {0.0f, 0u, 0u};
 	uint32_t                   nRows = 0, Hn = 0;
+	uint32_t                   oversample = 0;
 	DevBuf<float>              hist;  /* [row][side][channel][Hn] */
 	DevBuf<tbf_limit_row>      drows; /* the call's rows on the device */
 	std::vector<tbf_limit_row> rows;  /* .side persists, .count is the call's */

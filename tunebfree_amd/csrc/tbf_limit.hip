@@ -41,6 +41,10 @@
  * integer atomicAdd per wave, skipped when they would change nothing.  Integer minima and sums
  * do not depend on order, so the meters are exact.  k_limit_meters sets them to {1.0f, 0, 0} in
  * front of k_limit on the same stream.
+ *
+ * k_limit_tp (csrc/tbf_limit_tp.hip, the limiter with a true-peak detector) restates the minimum,
+ * the sum, the write and the meters of this file word for word, so that this kernel's
+ * instructions stay as they are: a fix to either copy belongs in both.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>

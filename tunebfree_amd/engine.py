@@ -83,6 +83,11 @@ class LimiterConfig(C.Structure):
     _fields_ = [("ceiling", C.c_float), ("ahead", C.c_uint32), ("hold", C.c_uint32)]
 
 
+class LimiterDetect(C.Structure):
+    """tbf_limiter_detect: the oversampling factor (2 or 4) of a limiter's true-peak detector"""
+    _fields_ = [("oversample", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class LimitMeter(C.Structure):
     """tbf_limit_meter: the least gain, the frames below unity and the clamped samples of a row in
     one call; arrays of them are LIMIT_METER_DTYPE records"""
@@ -215,6 +220,8 @@ SIGNATURES = {
     "tbf_process_mix_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
                                          C.c_void_p, C.c_uint32, C.POINTER(MixOut), C.c_void_p]),
     "tbf_limiter_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(LimiterConfig), C.POINTER(C.c_void_p)]),
+    "tbf_limiter_create_tp": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(LimiterConfig), C.POINTER(LimiterDetect),
+                                        C.POINTER(C.c_void_p)]),
     "tbf_limiter_destroy": (C.c_int, [C.c_void_p]),
     "tbf_limiter_reset": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tbf_limiter_latency": (C.c_int, [C.c_void_p, _u32p]),
@@ -321,25 +328,38 @@ def _counts_arg(counts, n_rows):
     return c.ctypes.data, c
 
 
+def limiter_oversample(rate_hz):
+    """the oversampling factor of a limiter's true-peak detector for a rate, as true_peak_oversample:
+    4 below 96 kHz, 2 below 192 kHz; at or above 192 kHz there is nothing to interpolate"""
+    f = true_peak_oversample(rate_hz)
+    if f == 1:
+        raise ValueError(f"no true-peak detector at {rate_hz} Hz: at or above 192 kHz use the plain limiter (oversample=None)")
+    return f
+
+
 class Limiter:
     """A bus limiter (Engine.limiter): n_rows rows of look-ahead peak limiting behind any two
-    device planes; its state belongs to it, not to the engine's instances."""
+    device planes; its state belongs to it, not to the engine's instances.  oversample is None for
+    the plain kind, 2 or 4 for one with a true-peak detector."""
 
-    def __init__(self, eng, handle, n_rows, cfg):
+    def __init__(self, eng, handle, n_rows, cfg, oversample=None):
         self._eng, self._lib, self._h = eng, eng._lib, handle
         self.n_rows, self.ceiling, self.ahead, self.hold = n_rows, cfg.ceiling, cfg.ahead, cfg.hold
+        self.oversample = oversample
 
     @property
     def latency(self):
-        """tbf_limiter_latency: the frames by which the output trails the input (ahead - 1)"""
+        """tbf_limiter_latency: the frames by which the output trails the input (ahead - 1, with a
+        true-peak detector ahead + 5)"""
         d = C.c_uint32()
         _check(self._lib.tbf_limiter_latency(self._h, C.byref(d)))
         return d.value
 
     @property
     def history(self):
-        """the frames of input a row keeps per channel (2 * ahead + hold - 2)"""
-        return 2 * self.ahead + self.hold - 2
+        """the frames of input a row keeps per channel (2 * ahead + hold - 2, with a true-peak
+        detector 11 more)"""
+        return 2 * self.ahead + self.hold - 2 + (11 if self.oversample else 0)
 
     def process_device(self, L_ptr, R_ptr, in_stride, frames, outL_ptr, outR_ptr, out_stride, counts=None, meters_ptr=None,
                        stream=None):
@@ -1365,48 +1385,62 @@ class Engine:
             None if in_ptr is None else C.c_void_p(int(in_ptr)), int(in_stride), r.ctypes.data if len(r) else None,
             int(n_buses), C.byref(mo), None if stream is None else C.c_void_p(int(stream))))
 
-    def limiter(self, n_rows, ceiling, ahead=64, hold=0):
+    def limiter(self, n_rows, ceiling, ahead=64, hold=0, oversample=None):
         """tbf_limiter_create: a look-ahead peak limiter of n_rows rows on this engine's device
         (ceiling in float32; ahead a power of two in [2, LIMIT_MAX_AHEAD]; hold in
-        [0, LIMIT_MAX_HOLD] frames); the engine releases it when it closes"""
+        [0, LIMIT_MAX_HOLD] frames); the engine releases it when it closes.  oversample 2 or 4
+        (limiter_oversample(rate) picks one): tbf_limiter_create_tp, the same limiter with a
+        true-peak detector, 6 frames more latency and 11 more of history."""
         cfg = LimiterConfig(float(ceiling), int(ahead), int(hold))
         h = C.c_void_p()
-        _check(self._lib.tbf_limiter_create(self._h, int(n_rows), C.byref(cfg), C.byref(h)))
-        return Limiter(self, h, int(n_rows), cfg)
+        if oversample is None:
+            _check(self._lib.tbf_limiter_create(self._h, int(n_rows), C.byref(cfg), C.byref(h)))
+            return Limiter(self, h, int(n_rows), cfg)
+        det = LimiterDetect(int(oversample), 0)
+        _check(self._lib.tbf_limiter_create_tp(self._h, int(n_rows), C.byref(cfg), C.byref(det), C.byref(h)))
+        return Limiter(self, h, int(n_rows), cfg, int(oversample))
 
     @staticmethod
-    def limit_ref(L, R, ceiling, ahead=64, hold=0, hist=None):
+    def limit_ref(L, R, ceiling, ahead=64, hold=0, hist=None, oversample=None):
         """tbf_debug_limit_ref: the host restatement of the limiter on one row (no device needed):
         L, R [n] float32 (the same array twice: mono), hist None (a new row) or the (histL, histR)
-        an earlier call returned; returns (outL, outR, LIMIT_METER_DTYPE record, (histL, histR))."""
-        f = load_library().tbf_debug_limit_ref
+        an earlier call returned; returns (outL, outR, LIMIT_METER_DTYPE record, (histL, histR)).
+        oversample 2 or 4: tbf_debug_limit_tp_ref, the limiter with a true-peak detector, whose
+        histories are 11 frames longer."""
+        tp = oversample is not None
+        f = load_library().tbf_debug_limit_tp_ref if tp else load_library().tbf_debug_limit_ref
         f.restype = C.c_int
-        f.argtypes = [C.POINTER(LimiterConfig), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
-                      C.c_void_p, C.c_void_p]
+        f.argtypes = [C.POINTER(LimiterConfig)] + ([C.POINTER(LimiterDetect)] if tp else []) + \
+            [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        head = (C.byref(LimiterDetect(int(oversample), 0)),) if tp else ()
         mono = L is R
         L = np.ascontiguousarray(L, dtype=np.float32)
         R = L if mono else np.ascontiguousarray(R, dtype=np.float32)
         if L.ndim != 1 or L.shape != R.shape:
             raise ValueError(f"rows of shape {L.shape} and {R.shape}: want two of [n]")
         cfg = LimiterConfig(float(ceiling), int(ahead), int(hold))
-        hn = max(2 * int(ahead) + int(hold) - 2, 0)
+        hn = max(2 * int(ahead) + int(hold) - 2, 0) + (11 if tp else 0)
         hL, hR = (np.zeros(hn, np.float32), np.zeros(hn, np.float32)) if hist is None else \
             (np.array(hist[0], np.float32), np.array(hist[1], np.float32))
         oL, oR = np.full(len(L), np.nan, np.float32), np.full(len(L), np.nan, np.float32)
         m = np.zeros(1, LIMIT_METER_DTYPE)
-        _check(f(C.byref(cfg), L.ctypes.data, R.ctypes.data, len(L), hL.ctypes.data, hR.ctypes.data, oL.ctypes.data,
+        _check(f(C.byref(cfg), *head, L.ctypes.data, R.ctypes.data, len(L), hL.ctypes.data, hR.ctypes.data, oL.ctypes.data,
                  oR.ctypes.data, m.ctypes.data))
         return oL, oR, m[0], (hL, hR)
 
     @staticmethod
-    def limit_grid(ceiling, ahead=64, hold=0):
+    def limit_grid(ceiling, ahead=64, hold=0, oversample=None):
         """tbf_debug_limit_grid: (frames per lane, frames per workgroup tile, history frames Hn, LDS
-        bytes per workgroup) of k_limit under a configuration"""
-        f = load_library().tbf_debug_limit_grid
-        f.restype, f.argtypes = C.c_int, [C.POINTER(LimiterConfig), _u32p, _u32p, _u32p, _u32p]
+        bytes per workgroup) of k_limit under a configuration; oversample 2 or 4:
+        tbf_debug_limit_tp_grid, the same of k_limit_tp"""
+        tp = oversample is not None
+        f = load_library().tbf_debug_limit_tp_grid if tp else load_library().tbf_debug_limit_grid
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(LimiterConfig)] + ([C.POINTER(LimiterDetect)] if tp else []) + [_u32p, _u32p, _u32p, _u32p]
+        head = (C.byref(LimiterDetect(int(oversample), 0)),) if tp else ()
         cfg = LimiterConfig(float(ceiling), int(ahead), int(hold))
         g, t, h, b = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
-        _check(f(C.byref(cfg), C.byref(g), C.byref(t), C.byref(h), C.byref(b)))
+        _check(f(C.byref(cfg), *head, C.byref(g), C.byref(t), C.byref(h), C.byref(b)))
         return g.value, t.value, h.value, b.value
 
     def loudness(self, n_rows, rate_hz=None, max_hops=6000):
